@@ -12,12 +12,19 @@ default for a registered SRS (KZG commit keys never change) is a FIXED-BASE tabl
 that path are the `fixed_base` object, with what the table costs (levels, bytes of HBM, build time -- paid once per SRS, outside
 its timed region) in `fixed_base.precompute`.
 
-Alongside, untimed by `value`: NTT 2^22 (configs[2]), round 3, batch commit, PlonkKzgSnark::prove on the reference's bench
-circuit (configs[3]; 10 timed repetitions as plonk/benches/bench.rs:25), the same proof in shim-only mode (host pointers,
-INTEGRATION.md section 2), UltraPlonk/BN254, the C++ host, and the CPU restatement on the host cores -- including ONE CPU proof
-of the same 2^20-gate circuit, so that the line itself carries the GPU/CPU ratio the north star is quoted on.
+A plain run does only that: set-up, W warm-up steps, K timed steps, the outputs (--dump-outputs) and the line.  With --full, and
+untimed by `value`: the fixed-base leg (run before the headline's steps), NTT 2^22 (configs[2]), round 3, batch commit,
+PlonkKzgSnark::prove on the reference's bench circuit (configs[3]; 10 timed repetitions as plonk/benches/bench.rs:25), the same
+proof in shim-only mode (host pointers), UltraPlonk/BN254, the C++ host, the sharded and replicated
+proofs of N > 1, and the CPU restatement on the host cores -- including ONE CPU proof of the same 2^20-gate circuit, so that the
+line itself carries the GPU/CPU ratio the north star is quoted on.  Without --full those objects are null.
 
-    python bench.py [--gpus N --steps K --warmup W] [--log-n 20] [--no-cpu-baseline]
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last step computed to DIR/msm_point_affine.npy -- the MSM's
+point (the Jacobian a caller receives, normalised to canonical affine x, y), float64 of shape (2, 24): 16-bit limbs, least
+significant first, exact in float64; (0, 0) is the point at infinity.  Bases and scalars come from fixed seeds, so two builds
+run with the same arguments can be compared output for output.
+
+    python bench.py [--gpus N --steps K --warmup W] [--log-n 20] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts its own N workers: this process touches no GPU, runs
@@ -139,7 +146,15 @@ def main():
     ap.add_argument("--secondary-timeout", type=int, default=420, help="N > 1: seconds after which a stalled secondary (sharded prove) section "
                     "is abandoned, the headline line printed as it stands and the process ended with a non-zero code (0 disables)")
     ap.add_argument("--ultra-sharded-log-n", type=int, default=22, help="N > 1: UltraPlonk/BN254 sharded prove leg (config C5: 22; 0 disables)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg (fixed-base, NTT, round 3, batch commit, proofs, C++ host, "
+                    "CPU baseline; the --no-* switches pick among them); without it the run is the headline's W + K steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the point of the last timed step to DIR/msm_point_affine.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:                                                 # a plain run: nothing but what the headline needs
+        args.no_fixed_base = args.no_batch = args.no_ntt = args.no_plonk = args.no_cpu_baseline = True
+        args.link_batch = False
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))                     # before torch or the library are even imported: no GPU call in this process
@@ -280,6 +295,11 @@ def main():
     # the headline steps run with the fixed-base table OFF: nothing is precomputed per base (BASELINE configs[1], ark-ec's VariableBaseMSM)
     L.mzk_msm_set_precompute(0)
     elapsed, result, acc_avg_ms, phases, (c_bits, n_win, n_buckets) = timed_steps()
+    if args.dump_outputs and rank == 0:            # the last step's point as canonical affine coordinates in 16-bit limbs (exact in float64)
+        xy = mj.kzg.jacobian_to_affine(curve, np.asarray(result).reshape(1, -1))[0]
+        limbs = [[(v >> (16 * j)) & 0xFFFF for j in range(24)] for v in mj.params.fq_from_mont(curve, xy)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_point_affine.npy"), np.array(limbs, dtype=np.float64))
     alg_bytes = 128.0 * n                          # N * (2*|Fq| + 32) bytes per BLS12-381 MSM
 
     def msm_roofline(acc_ms, windows, pmc_prefix):
