@@ -111,6 +111,33 @@ MZK_API int32_t mzk_srs_lagrange_from_srs(uint64_t srs_handle, uint32_t log_n, u
  * the slice's size -- and hands it to mzk_prover_create as its commit key (see there).  The source stays registered. */
 MZK_API int32_t mzk_srs_slice(uint64_t handle, uint64_t first, uint64_t n_points, uint64_t* out_handle);
 MZK_API int32_t mzk_srs_download(uint64_t handle, uint64_t first, uint64_t n_points, uint64_t* out_xy_mont);
+/* ---- serialized SRS: the G1 records of ark-serialize 0.4 (CanonicalSerialize of UnivariateProverParam / UnivariateUniversalParams)
+ * Records only: the container (u64 LE count, the trailing G2 elements h and beta_h) belongs to the caller.  Sizes and flags:
+ *   BLS12-381  compressed 48 B: x big-endian; byte 0: 0x80 compressed (must be set), 0x40 infinity, 0x20 y is the larger
+ *              uncompressed 96 B: x BE || y BE; byte 0: 0x80 and 0x20 must be clear, 0x40 infinity
+ *   BN254      compressed 32 B: x little-endian; byte 31: 0x80 y is the larger, 0x40 infinity, both set = invalid
+ *              uncompressed 64 B: x LE (no flags) || y LE with those flags in byte 63 (0x80 written as ark writes it, ignored on read)
+ * ("y is the larger": y > q - y on canonical integers.)  Checks, as ark's deserialize_* (MZK_SER_VALIDATE) / deserialize_*_unchecked:
+ * always the flag rules, x, y < q, and for compressed records that x^3 + b is a square; MZK_SER_VALIDATE adds on-curve for uncompressed
+ * records and, on BLS12-381, membership in G1 (the endomorphism test phi(P) = -[u^2]P, equivalent to [r]P = O).
+ * UNLIKE ark, a point at infinity is always refused (MZK_ERR_ENCODING): the affine SRS has no usable infinity -- (0, 0) would corrupt the
+ * mixed additions of an MSM -- and a KZG power at infinity means beta = 0.  So is an uncompressed (0, 0) read without validation.
+ * On MZK_ERR_ENCODING *out_bad_index (nullable) is the lowest failing index and mzk_last_error() reads "point <i>: <reason>", the first
+ * check that point failed in the order flags, range, square / on-curve, subgroup, infinity; otherwise *out_bad_index = UINT64_MAX.
+ * On any failure no handle exists and nothing stays allocated.  One thread per point decodes (csrc/srs_io.hip), then the internal table
+ * is built as by mzk_srs_register; threading and device binding are those of mzk_srs_register[_dev].  n_points = 0 is valid.
+ * The host variant stages the records whole: one copy, one decode (profile regions srs_load.copy / .decode / .table). */
+#define MZK_SER_COMPRESSED 1u
+#define MZK_SER_VALIDATE 2u
+MZK_API int32_t mzk_srs_register_serialized(int32_t curve_id, const uint8_t* point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
+                                            uint64_t* out_bad_index);
+/* The same from device memory (any alignment), read on `stream`; synchronises it. */
+MZK_API int32_t mzk_srs_register_serialized_dev(int32_t curve_id, const void* d_point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
+                                                uint64_t* out_bad_index, void* stream);
+/* Points [first, first + n_points) of any SRS handle as records (flags: MZK_SER_COMPRESSED or 0) into out_bytes (host,
+ * n_points * record bytes); (0, 0) is written as ark writes infinity.  Synchronises. */
+MZK_API int32_t mzk_srs_serialize(uint64_t handle, uint64_t first, uint64_t n_points, uint32_t flags, uint8_t* out_bytes);
+
 MZK_API int32_t mzk_srs_len(uint64_t handle, uint64_t* out_n_points);
 
 /* ---- MSM: replaces <E::G1 as VariableBaseMSM>::msm_bigint(bases, bigints)
@@ -384,6 +411,7 @@ MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uin
  * refused by mzk_prover_create with MZK_ERR_UNSUPPORTED. */
 #define MZK_ERR_WRONG_QUOTIENT_DEGREE (-9) /* PlonkError::WrongQuotientPolyDegree: the witness does not satisfy the circuit */
 #define MZK_ERR_STATE (-10)                /* prover rounds called out of order */
+#define MZK_ERR_ENCODING (-11)             /* invalid point encoding: mzk_last_error() = "point <i>: <reason>" (mzk_srs_register_serialized) */
 
 /* Several devices / processes: this prover is rank `rank` of `world` -- it commits over the SRS points
  * [rank (n+3) / world ..) of every polynomial, evaluates ceil(W / world) residue classes of the quotient, runs rounds 4-5 on its

@@ -16,5 +16,5 @@ from . import params  # noqa: F401
 from .lib import MzkError, lib_path, load  # noqa: F401
 from .domain import Radix2EvaluationDomain  # noqa: F401
 from . import batch, linking, plonk, poly, prover, rng, sharding, snark, transcript  # noqa: F401
-from .kzg import (Commitment, PCSError, UnivariateKzgPCS, UnivariateProverParam,  # noqa: F401
-                  jacobian_to_affine, msm_bigint, msm_bigint_batch)
+from .kzg import (Commitment, PCSError, SerializationError, UnivariateKzgPCS, UnivariateProverParam,  # noqa: F401
+                  UnivariateUniversalParams, jacobian_to_affine, msm_bigint, msm_bigint_batch)

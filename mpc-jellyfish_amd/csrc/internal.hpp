@@ -153,6 +153,14 @@ int32_t srs_lagrange_generate_dispatch(int curve, const uint32_t* beta_canon, co
 void jac_to_affine_host_dispatch(int curve, const uint64_t* xyz, uint64_t n, uint64_t* xy);
 void jac_sum_host_dispatch(int curve, const uint64_t* xyz, uint64_t n, uint64_t* out);
 
+// srs_io.hip: serialized G1 records (srs_io.cuh) <-> the boundary form of Srs::d_xy.  Decode reports the lowest failing index and the
+// first check it failed (srs_bad_reason); *out_bad = ~0 when every point decoded.  Both run on `st`; decode synchronises it.
+uint64_t srs_record_bytes(int curve, bool compressed);
+const char* srs_bad_reason(int k);
+int32_t srs_decode_dispatch(int curve, const uint8_t* d_in, uint64_t n, bool compressed, bool validate, uint32_t* d_xy, uint64_t* out_bad, int* out_reason,
+                            hipStream_t st);
+int32_t srs_encode_dispatch(int curve, const uint32_t* d_xy, uint64_t n, bool compressed, uint8_t* d_out, hipStream_t st);
+
 // poly.hip
 int32_t poly_eval_dispatch(int curve, const uint32_t* d_coeffs, uint64_t stride, uint64_t len, uint32_t batch, const uint32_t* x_mont, uint32_t* out_host,
                            hipStream_t st);

@@ -291,6 +291,7 @@ const char* mzk_strerror(int32_t code) {
         case MZK_ERR_LOOKUP: return "Plookup: lookup value outside the table";
         case MZK_ERR_WRONG_QUOTIENT_DEGREE: return "WrongQuotientPolyDegree";
         case MZK_ERR_STATE: return "prover rounds called out of order";
+        case MZK_ERR_ENCODING: return "invalid point encoding";
         default: return "unknown error";
     }
 }
@@ -330,6 +331,101 @@ int32_t mzk_srs_register_dev(int32_t curve_id, const void* d_xy_mont, uint64_t n
     *out_handle = handle_make(cx_->logical, cx_->next_handle++);
     cx_->srs[*out_handle] = s;
     return MZK_OK;
+}
+// ---- serialized SRS (srs_io.hip) ----
+namespace {
+// decode n records at d_bytes (device) into a new SRS of the current context; on any failure nothing stays allocated
+int32_t srs_register_decoded(int32_t curve_id, const uint8_t* d_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
+                             uint64_t* out_bad_index, hipStream_t st) {
+    Srs s{curve_id, n_points, nullptr, nullptr, nullptr, 0};
+    HIP_TRY(hipMalloc((void**)&s.d_xy, n_points ? (size_t)n_points * 2 * fq_words(curve_id) * 4 : 4));
+    uint64_t bad = ~0ull;
+    int reason = -1;
+    int32_t rc;
+    {
+        ProfScope ps("srs_load.decode", st);
+        rc = srs_decode_dispatch(curve_id, d_bytes, n_points, flags & MZK_SER_COMPRESSED, flags & MZK_SER_VALIDATE, s.d_xy, &bad, &reason, st);
+    }
+    if (out_bad_index) *out_bad_index = bad;
+    if (rc == MZK_OK && reason >= 0) {
+        set_error("point " + std::to_string(bad) + ": " + srs_bad_reason(reason));
+        rc = MZK_ERR_ENCODING;
+    }
+    if (rc == MZK_OK) {
+        ProfScope ps("srs_load.table", st);
+        rc = srs_build_internal(s, st);
+    }
+    if (rc != MZK_OK) {
+        (void)hipFree(s.d_xy);
+        if (s.d_int) (void)hipFree(s.d_int);
+        return rc;
+    }
+    *out_handle = handle_make(cur().logical, cur().next_handle++);
+    cur().srs[*out_handle] = s;
+    return MZK_OK;
+}
+}  // namespace
+int32_t mzk_srs_register_serialized(int32_t curve_id, const uint8_t* point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
+                                    uint64_t* out_bad_index) {
+    ENTER_CUR();
+    if ((curve_id != 0 && curve_id != 1) || !out_handle || (!point_bytes && n_points) || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
+        set_error("bad argument");
+        return MZK_ERR_INVALID_ARG;
+    }
+    // whole staging: one copy of the records, then one decode launch (the copy / decode split)
+    const size_t bytes = (size_t)n_points * srs_record_bytes(curve_id, flags & MZK_SER_COMPRESSED);
+    uint8_t* d_bytes = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_bytes, bytes ? bytes : 4));
+    hipError_t e;
+    {
+        ProfScope ps("srs_load.copy", nullptr);
+        e = bytes ? hipMemcpy(d_bytes, point_bytes, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    }
+    if (e != hipSuccess) {
+        (void)hipFree(d_bytes);
+        set_error(std::string("hipMemcpy of the SRS records: ") + hipGetErrorString(e));
+        return MZK_ERR_HIP;
+    }
+    const int32_t rc = srs_register_decoded(curve_id, d_bytes, n_points, flags, out_handle, out_bad_index, nullptr);
+    (void)hipFree(d_bytes);
+    return rc;
+}
+int32_t mzk_srs_register_serialized_dev(int32_t curve_id, const void* d_point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
+                                        uint64_t* out_bad_index, void* stream) {
+    ENTER_CUR();
+    if ((curve_id != 0 && curve_id != 1) || !out_handle || (!d_point_bytes && n_points) || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
+        set_error("bad argument");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return srs_register_decoded(curve_id, reinterpret_cast<const uint8_t*>(d_point_bytes), n_points, flags, out_handle, out_bad_index, (hipStream_t)stream);
+}
+int32_t mzk_srs_serialize(uint64_t handle, uint64_t first, uint64_t n_points, uint32_t flags, uint8_t* out_bytes) {
+    ENTER_HANDLE(handle);
+    auto it = cx_->srs.find(handle);
+    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
+    const Srs& s = it->second;
+    if (first > s.n || n_points > s.n - first || (flags & ~MZK_SER_COMPRESSED) || (!out_bytes && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (!n_points) return MZK_OK;
+    const size_t bytes = (size_t)n_points * srs_record_bytes(s.curve, flags & MZK_SER_COMPRESSED);
+    uint8_t* d_out = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_out, bytes));
+    HIP_TRY(hipDeviceSynchronize());
+    int32_t rc;
+    {
+        ProfScope ps("srs_save.encode", nullptr);
+        rc = srs_encode_dispatch(s.curve, s.d_xy + first * 2 * fq_words(s.curve), n_points, flags & MZK_SER_COMPRESSED, d_out, nullptr);
+    }
+    hipError_t e = hipSuccess;
+    if (rc == MZK_OK) {
+        ProfScope ps("srs_save.copy", nullptr);
+        e = hipMemcpy(out_bytes, d_out, bytes, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d_out);
+    if (rc == MZK_OK && e != hipSuccess) {
+        set_error(std::string("hipMemcpy of the SRS records: ") + hipGetErrorString(e));
+        rc = MZK_ERR_HIP;
+    }
+    return rc;
 }
 // a new SRS holding the points [first, first + n_points) of a registered one (on its device): a rank of a multi-GPU prover keeps only
 // the range it commits over -- 1 / G of the points and of the fixed-base table, whose window then follows the slice's size

@@ -41,6 +41,32 @@ using mzk::h64::inv;
 using mzk::h64::pow_u64;
 using mzk::h64::root_of_unity;
 
+// ---- a serialized setup: CanonicalSerialize of UnivariateUniversalParams, compressed (srs.rs:18-27) ---------------------------
+// u64 LE count, `count` G1 records (48 B on BLS12-381, 32 B on BN254), then h and beta_h (G2: 96 / 64 B each).  The container is checked
+// here (exact length); the G1 records are decoded and validated on the device (mzk_srs_register_serialized); the G2 elements are kept
+// as bytes -- the prover never reads them.
+struct SrsFile {
+    std::vector<uint8_t> bytes;
+    uint64_t count = 0;
+    static SrsFile read(const char* path, int curve_id) {
+        SrsFile f;
+        FILE* fp = std::fopen(path, "rb");
+        if (!fp) throw std::runtime_error(std::string("--srs: cannot open ") + path);
+        uint8_t chunk[1 << 16];
+        size_t got;
+        while ((got = std::fread(chunk, 1, sizeof chunk, fp)) > 0) f.bytes.insert(f.bytes.end(), chunk, chunk + got);
+        std::fclose(fp);
+        const uint64_t g1 = curve_id == MZK_CURVE_BLS12_381 ? 48 : 32, g2 = 2 * g1, size = f.bytes.size();
+        if (size < 8 + 2 * g2) throw std::runtime_error("--srs: the file is shorter than an empty UnivariateUniversalParams");
+        for (int i = 0; i < 8; i++) f.count |= (uint64_t)f.bytes[i] << (8 * i);
+        if (f.count > (size - 8 - 2 * g2) / g1 || 8 + f.count * g1 + 2 * g2 != size)
+            throw std::runtime_error("--srs: " + std::to_string(size) + " bytes do not hold a compressed UnivariateUniversalParams of " + std::to_string(f.count) +
+                                     " powers");
+        return f;
+    }
+    const uint8_t* points() const { return bytes.data() + 8; }
+};
+
 // ---- rand_chacha ChaCha{8,12,20}Rng and ark-ff's Fp::rand ------------------------------------------------
 struct ChaChaRng {
     uint32_t key[8];

@@ -2,6 +2,9 @@
 // include/mzk.h, no Python, no HIP in this translation unit (g++ builds it).
 //   mzk_prove <curve: 0 BLS12-381 | 1 BN254> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree]
 //   mzk_prove <curve> file <circuit file> [reps] [--gpus G] [--host-witness] ...
+// --srs FILE (turbo, ultra, file): commit over the powers of a setup file -- CanonicalSerialize of UnivariateUniversalParams, compressed --
+// decoded and validated on every device, instead of the testing SRS [beta^i] G.  The trapdoor is still drawn (and discarded) from the rng,
+// so the blinders are those of a run without --srs.  A file with fewer than n + 3 powers is an error.
 // `file`: ANY finalised circuit -- public inputs, every gate type, copy constraints, lookups -- as the arrays `Arithmetization` exposes
 // (format: BenchCircuitHost::read in mzk_prover.hpp; mpc-jellyfish_amd/circuit_io.py writes it).
 // Prints one JSON line: proof bytes (hex), wall time per proof, per-round times of one profiled proof.
@@ -27,6 +30,7 @@ struct Options {
     int host_witness = 0;         // --host-witness: every proof uploads its W x n wire values from page-locked host memory;
                                   // --host-witness-vars: only the witness vector, gathered per wire on the device
     bool check_agree = false;     // --check-agree: every rank's proof bytes are compared (tests)
+    const char* srs_path = nullptr;  // --srs FILE: the commit key from a serialized setup
     bool slice_srs = true;        // --no-slice: with --gpus G every rank keeps the whole commit key (and its table) instead of its point range
     int lagrange = -1;            // round 1 commits the wires from their VALUES over the Lagrange-basis key derived from the SRS (same proof
                                   // bytes): -1 = from 2^18 gates on (below, the heavy-bucket paths of small scalars cost more than they save: 2^15 gates 3.93 against 3.73 ms) when a sample of the witness
@@ -48,12 +52,13 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     }
     ChaChaRng rng = test_rng();
     const Fr beta = fr_rand<typename C::Fr>(rng);                       // the SRS trapdoor: first draw of the bench's rng (bench.rs:50-54)
-    const auto beta_c = canonical(beta);
+    const auto beta_c = canonical(beta);                                // (drawn with --srs too, then unused: the same blinders follow)
+    const SrsFile srs_file = opt.srs_path ? SrsFile::read(opt.srs_path, C::ID) : SrsFile();
     ShardedProver<C> sp(opt.gpus);
     double circuit_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     t0 = std::chrono::steady_clock::now();
     const bool lagrange = opt.lagrange < 0 ? (host.log_n >= 18 && host.witness_is_small()) : opt.lagrange != 0;
-    sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs);                           // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
+    sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr);                           // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
     const double preprocess_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     Proof<C> proof = sp.prove(rng, false, opt.check_agree);             // the proof whose bytes are printed (and warm-up)
     const std::vector<uint8_t> bytes = proof.serialize_compressed();
@@ -176,12 +181,13 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--lagrange") opt.lagrange = 1;
         else if (a == "--no-lagrange") opt.lagrange = 0;
         else if (a == "--no-slice") opt.slice_srs = false;
+        else if (a == "--srs" && i + 1 < argc_in) opt.srs_path = argv_in[++i];
         else args.push_back(argv_in[i]);
     }
     const int argc = (int)args.size();
     char** argv = args.data();
     if (opt.gpus < 1 || opt.gpus > 16) { std::fprintf(stderr, "mzk_prove: --gpus 1..16\n"); return 2; }
-    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--no-lagrange]\n", argv[0]); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
     const int curve = std::atoi(argv[1]);
     if (std::string(argv[2]) == "link") {
         if (argc < 8) { std::fprintf(stderr, "usage: %s <curve 0|1> link <num_gates_1> <num_gates_2> <alignment> <offset> <size> [reps]\n", argv[0]); return 2; }

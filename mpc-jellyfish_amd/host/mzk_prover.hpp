@@ -635,9 +635,17 @@ struct ShardedProver {
     // lagrange: also the key over the Lagrange basis of the gate domain -- round 1 then commits from the wire values
     // slice_srs (several devices): every rank keeps ONLY its point range of the commit key(s) -- mzk_srs_slice -- i.e. 1 / G of the SRS and of
     // its fixed-base table, built with the window that suits the slice (2^17-point shards at G = 8: window 16 and fused small batches)
-    void setup(const BenchCircuitHost<C>& host, const std::array<uint64_t, 4>& beta_canonical, int host_witness = 0, bool lagrange = true, bool slice_srs = true) {
+    // srs_file (nullable): the commit key is the file's first n + 3 powers, decoded and validated on every device, instead of [beta^i] G
+    void setup(const BenchCircuitHost<C>& host, const std::array<uint64_t, 4>& beta_canonical, int host_witness = 0, bool lagrange = true, bool slice_srs = true,
+               const SrsFile* srs_file = nullptr) {
+        if (srs_file && srs_file->count < host.n + 3)
+            throw std::runtime_error("--srs: the file holds " + std::to_string(srs_file->count) + " powers, the circuit needs n + 3 = " + std::to_string(host.n + 3));
         each([&](int r) {
-            check(mzk_srs_generate_for_testing(C::ID, beta_canonical.data(), host.n + 3, &srs[r]), "mzk_srs_generate_for_testing");
+            if (srs_file)
+                check(mzk_srs_register_serialized(C::ID, srs_file->points(), host.n + 3, MZK_SER_COMPRESSED | MZK_SER_VALIDATE, &srs[r], nullptr),
+                      "mzk_srs_register_serialized");
+            else
+                check(mzk_srs_generate_for_testing(C::ID, beta_canonical.data(), host.n + 3, &srs[r]), "mzk_srs_generate_for_testing");
             if (lagrange) {                                               // from the SRS's points alone (no trapdoor): an inverse NTT over the group
                 const auto t0 = std::chrono::steady_clock::now();
                 check(mzk_srs_lagrange_from_srs(srs[r], (uint32_t)host.log_n, 3, &srs_lagrange[r]), "mzk_srs_lagrange_from_srs");

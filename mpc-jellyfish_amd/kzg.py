@@ -5,6 +5,8 @@
     trim                                    srs.rs:77-93   -> UnivariateProverParam.trim
     commit / batch_commit                   mod.rs:90-131  -> UnivariateKzgPCS.commit / batch_commit
     <G1 as VariableBaseMSM>::msm_bigint     mod.rs:109-111 -> msm_bigint
+    CanonicalSerialize / Deserialize        srs.rs:18-40   -> UnivariateProverParam.serialize / deserialize,
+                                                              UnivariateUniversalParams (points decoded on the GPU)
 
 Polynomials are (len,4) uint64 Montgomery coefficient arrays, low order first (DensePolynomial);
 commitments are affine points x||y (Montgomery limbs), (0,0) = infinity.  Error behaviour follows
@@ -22,6 +24,55 @@ from .params import CurveParams, curve as _curve, fq_to_mont, int_to_limbs
 
 class PCSError(Exception):
     """primitives/src/pcs/errors.rs:16-33 (InvalidParameters is the only variant raised here)."""
+
+
+class SerializationError(ValueError):
+    """A serialized setup that ark-serialize would refuse, or that holds a point at infinity (include/mzk.h, MZK_ERR_ENCODING).
+    .index: the lowest failing point (None for container errors); .reason: what failed."""
+
+    def __init__(self, reason: str, index: int | None = None):
+        super().__init__(reason if index is None else f"point {index}: {reason}")
+        self.index, self.reason = index, reason
+
+
+_SER_COMPRESSED, _SER_VALIDATE = 1, 2
+_ERR_ENCODING = -11
+
+
+def g1_record_bytes(curve, compress: bool = True) -> int:
+    """Bytes of one G1 point in ark-serialize 0.4: 48 / 96 on BLS12-381, 32 / 64 on BN254 (compressed / uncompressed)."""
+    return (48 if _curve(curve).curve_id == 0 else 32) * (1 if compress else 2)
+
+
+def g2_record_bytes(curve, compress: bool = True) -> int:
+    """Bytes of one G2 point: 96 / 192 on BLS12-381, 64 / 128 on BN254."""
+    return 2 * g1_record_bytes(curve, compress)
+
+
+def _as_bytes(data):
+    """Any host buffer (bytes, bytearray, memoryview, numpy uint8 incl. np.memmap) as a flat uint8 array, without a copy where possible;
+    a CUDA uint8 tensor is returned as is."""
+    if _is_torch(data):
+        import torch
+        if data.dtype != torch.uint8 or not data.is_cuda or data.dim() != 1 or not data.is_contiguous():
+            raise ValueError("expected a contiguous 1-D uint8 CUDA tensor")
+        return data
+    a = data if isinstance(data, np.ndarray) else np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
+    if a.dtype != np.uint8:
+        raise ValueError("expected uint8 data")
+    return np.ascontiguousarray(a.reshape(-1))
+
+
+def _vec_header(buf, rec: int, what: str) -> tuple[int, int]:
+    """(count, bytes of the Vec<G1Affine> image) from its u64 LE length prefix; raises SerializationError on a short buffer."""
+    total = buf.shape[0]
+    if total < 8:
+        raise SerializationError(f"{what}: {total} bytes, shorter than the 8-byte length prefix")
+    head = buf[:8].cpu().numpy() if _is_torch(buf) else buf[:8]
+    count = int.from_bytes(bytes(head), "little")
+    if count > (total - 8) // rec:
+        raise SerializationError(f"{what}: the prefix counts {count} points, the data holds {(total - 8) // rec} ({total} bytes)")
+    return count, 8 + count * rec
 
 
 class Commitment:
@@ -108,6 +159,49 @@ class UnivariateProverParam:
             raise PCSError("InvalidParameters: supported degree larger than the SRS")
         return UnivariateProverParam(self.curve, self.handle, supported_degree + 1, self.offset, owner=False)
 
+    @classmethod
+    def deserialize(cls, curve, data, compress: bool = True, validate: bool = True) -> "UnivariateProverParam":
+        """The CanonicalDeserialize image of `UnivariateProverParam` (a Vec<G1Affine>: u64 LE count, then the points; srs.rs:36-40) ->
+        a key on the GPU, decoded and checked there (mzk_srs_register_serialized).  compress / validate select ark's
+        deserialize_{compressed,uncompressed}[_unchecked]; unlike ark a point at infinity is always refused.  data: bytes, memoryview,
+        a numpy uint8 array (np.memmap of a file included), or a 1-D uint8 CUDA tensor (decoded in place on the current stream).
+        Raises SerializationError (container length before any device call; a bad point with its lowest index and reason)."""
+        c = _curve(curve)
+        buf = _as_bytes(data)
+        count, used = _vec_header(buf, g1_record_bytes(c, compress), "UnivariateProverParam")
+        if used != buf.shape[0]:
+            raise SerializationError(f"UnivariateProverParam: {buf.shape[0] - used} trailing bytes after {count} points")
+        return cls._register_records(c, buf, 8, count, compress, validate)
+
+    @classmethod
+    def _register_records(cls, c, buf, offset: int, count: int, compress: bool, validate: bool) -> "UnivariateProverParam":
+        L = _lib.ensure_init()
+        h, bad = C.c_uint64(), C.c_uint64()
+        flags = (_SER_COMPRESSED if compress else 0) | (_SER_VALIDATE if validate else 0)
+        if _is_torch(buf):
+            import torch
+            st = torch.cuda.current_stream(buf.device).cuda_stream
+            rc = L.mzk_srs_register_serialized_dev(c.curve_id, C.c_void_p(buf.data_ptr() + offset), count, flags, C.byref(h), C.byref(bad),
+                                                   C.c_void_p(st))
+        else:
+            rc = L.mzk_srs_register_serialized(c.curve_id, C.c_void_p(buf.ctypes.data + offset) if count else None, count, flags, C.byref(h),
+                                               C.byref(bad))
+        if rc == _ERR_ENCODING:
+            msg = L.mzk_last_error().decode()
+            raise SerializationError(msg.split(": ", 1)[1] if ": " in msg else msg, bad.value)
+        _lib.check(rc, "mzk_srs_register_serialized")
+        return cls(c, h.value, count)
+
+    def serialize(self, compress: bool = True) -> bytes:
+        """CanonicalSerialize of this key (a trimmed view: its own `length` points from `offset`), encoded on the GPU."""
+        rec = g1_record_bytes(self.curve, compress)
+        out = np.empty(8 + self.length * rec, dtype=np.uint8)
+        out[:8] = np.frombuffer(self.length.to_bytes(8, "little"), dtype=np.uint8)
+        if self.length:
+            _lib.check(_lib.ensure_init().mzk_srs_serialize(self.handle, self.offset, self.length, _SER_COMPRESSED if compress else 0,
+                                                            C.c_void_p(out.ctypes.data + 8)), "mzk_srs_serialize")
+        return out.tobytes()
+
     def powers_of_g(self, first: int = 0, count: int | None = None) -> np.ndarray:
         count = self.length - first if count is None else count
         out = np.empty((count, 2, self.curve.fq_limbs), dtype=np.uint64)
@@ -119,6 +213,40 @@ class UnivariateProverParam:
         if self._owner and self.handle:
             _lib.check(_lib.load().mzk_srs_release(self.handle), "mzk_srs_release")
             self.handle = 0
+
+
+class UnivariateUniversalParams:
+    """srs.rs:18-27: powers_of_g (a UnivariateProverParam on the GPU), then h and beta_h (G2).  The G2 elements are kept as the bytes they
+    were read as -- only their length is checked; the prover never reads them, and decoding or validating G2 is not done here.
+    `compressed`: the mode the container was read in, and the one serialize() writes back."""
+
+    def __init__(self, powers_of_g: UnivariateProverParam, h: bytes, beta_h: bytes, compressed: bool = True):
+        self.powers_of_g, self.h, self.beta_h, self.compressed = powers_of_g, bytes(h), bytes(beta_h), compressed
+        g2 = g2_record_bytes(powers_of_g.curve, compressed)
+        if len(self.h) != g2 or len(self.beta_h) != g2:
+            raise SerializationError(f"UnivariateUniversalParams: G2 elements are {g2} bytes in this mode")
+
+    @classmethod
+    def deserialize(cls, curve, data, compress: bool = True, validate: bool = True) -> "UnivariateUniversalParams":
+        """CanonicalDeserialize of the whole setup (derive order: powers_of_g, h, beta_h).  The points are decoded as by
+        UnivariateProverParam.deserialize; h and beta_h are length-checked and kept as bytes.  Container length errors (truncation,
+        trailing bytes, a count that does not fit) raise SerializationError before any device call."""
+        c = _curve(curve)
+        buf = _as_bytes(data)
+        count, used = _vec_header(buf, g1_record_bytes(c, compress), "UnivariateUniversalParams")
+        g2 = g2_record_bytes(c, compress)
+        if buf.shape[0] != used + 2 * g2:
+            raise SerializationError(f"UnivariateUniversalParams: {buf.shape[0]} bytes, expected {used + 2 * g2} for {count} points")
+        tail = buf[used:]
+        tail = bytes(tail.cpu().numpy()) if _is_torch(tail) else bytes(tail)
+        pp = UnivariateProverParam._register_records(c, buf, 8, count, compress, validate)
+        return cls(pp, tail[:g2], tail[g2:], compress)
+
+    def serialize(self) -> bytes:
+        return self.powers_of_g.serialize(self.compressed) + self.h + self.beta_h
+
+    def release(self):
+        self.powers_of_g.release()
 
 
 def _is_torch(x) -> bool:

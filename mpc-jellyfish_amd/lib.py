@@ -36,6 +36,9 @@ _SIGS = {
     "mzk_srs_slice": [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_srs_download": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p],
     "mzk_srs_len": [C.c_uint64, C.POINTER(C.c_uint64)],
+    "mzk_srs_register_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "mzk_srs_register_serialized_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p],
+    "mzk_srs_serialize": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p],
     "mzk_msm": [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p],
     "mzk_msm_dev": [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p],
     "mzk_msm_batch": [C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32, C.c_void_p],
