@@ -1,5 +1,5 @@
-// ntt.hip -- host side of the NTT: plan cache and pass launches.  The passes run on the reduced-radix
-// kernel of ntt_fx.cuh; ntt.cuh keeps the 32-bit-limb kernel it was derived from (same decomposition).
+// ntt.hip -- host side of the NTT: the plan cache (one per device context), the arguments of each pass and the pass launches.
+// The kernels and the plan tables are in ntt_fx.cuh; the decomposition, its constants and the radix chooser in ntt.cuh.
 #include <cstdlib>
 #include <map>
 #include <memory>
@@ -31,8 +31,9 @@ struct PlanKey {
         return has_coset && std::memcmp(coset, o.coset, sizeof coset) < 0;
     }
 };
-std::map<PlanKey, std::unique_ptr<NttPlanDev>> g_plans_of[MAX_CTX];      // one plan cache per device context
-#define g_plans (g_plans_of[cur().logical])
+using PlanMap = std::map<PlanKey, std::unique_ptr<NttPlanDev>>;
+PlanMap g_plans_of[MAX_CTX];                     // one plan cache per device context
+PlanMap& plans() { return g_plans_of[cur().logical]; }        // the calling thread's context's
 std::atomic<uint64_t> g_plan_clock{0};           // LRU clock shared by the device threads of one process
 // A plan holds device tables (up to tens of MB for the largest domains) and is keyed by the coset offset: a caller sweeping
 // offsets (per-proof random cosets, the multiprover's public-polynomial FFTs) must not grow the cache without bound.
@@ -58,15 +59,16 @@ int32_t get_plan(int curve, int log_n, bool inverse, const uint32_t* coset, int 
     key.curve = curve; key.log_n = log_n; key.inverse = inverse ? 1 : 0; key.scale = scale;
     key.has_coset = coset != nullptr;
     if (coset) std::memcpy(key.coset, coset, 32);
-    auto it = g_plans.find(key);
-    if (it != g_plans.end()) { it->second->last_used = ++g_plan_clock; *out = it->second.get(); return MZK_OK; }
-    if (g_plans.size() >= NTT_MAX_PLANS) {                       // evict the least recently used plan (its kernels may still be in flight)
-        auto victim = g_plans.begin();
-        for (auto p = g_plans.begin(); p != g_plans.end(); ++p)
+    PlanMap& cache = plans();
+    auto it = cache.find(key);
+    if (it != cache.end()) { it->second->last_used = ++g_plan_clock; *out = it->second.get(); return MZK_OK; }
+    if (cache.size() >= NTT_MAX_PLANS) {                       // evict the least recently used plan (its kernels may still be in flight)
+        auto victim = cache.begin();
+        for (auto p = cache.begin(); p != cache.end(); ++p)
             if (p->second->last_used < victim->second->last_used) victim = p;
         HIP_TRY(hipDeviceSynchronize());
         free_plan(victim->second.get());
-        g_plans.erase(victim);
+        cache.erase(victim);
     }
     auto pl = std::make_unique<NttPlanDev>();
     nttx_build_plan<X>(pl->h, log_n, inverse, coset, scale);
@@ -80,60 +82,64 @@ int32_t get_plan(int curve, int log_n, bool inverse, const uint32_t* coset, int 
     pl->h.f_lo = {}; pl->h.f_hi = {};
     pl->last_used = ++g_plan_clock;
     *out = pl.get();
-    g_plans[key] = std::move(pl);
+    cache[key] = std::move(pl);
     return MZK_OK;
 }
 
-// how many workgroups of the persistent pass one launch keeps resident (per device context; the occupancy query costs ~50 us)
-template <class X, bool TW_LDS>
-int32_t persistent_grid(size_t lds, unsigned* out) {
-    static unsigned cached[MAX_CTX][4] = {};                             // by LDS size class
-    const int cls = lds >= 48 * 1024 ? 0 : (lds >= 36 * 1024 ? 1 : (lds >= 18 * 1024 ? 2 : 3));
-    unsigned& slot = cached[cur().logical][cls];
-    if (!slot) {
-        int per_cu = 0, dev = 0, cus = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)nttx_pass_persistent_kernel<X, TW_LDS>, NTTX_THREADS, lds));
-        HIP_TRY(hipGetDevice(&dev));
-        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (per_cu < 1) per_cu = 1;
-        slot = (unsigned)(per_cu * cus);
-    }
-    *out = slot;
-    return MZK_OK;
+// Everything of pass k's arguments but the twiddle tables (the caller knows where those go).  h: the plan's shape (of any class: the
+// classes' plans agree in it); tile_log: log2 of the elements a workgroup stages; the rest as ntt_dev's parameters.
+// Pass 1 reads the caller's buffer (or d_src), middle passes run in place on scratch, the last pass writes back to the caller's buffer;
+// a single-pass transform goes data -> scratch (packed) and the caller copies it back.
+NttxPassArgs pass_args(const NttxPlanHost& h, int k, int tile_log, uint32_t* d_data, uint64_t stride, uint32_t* scratch, uint64_t in_len,
+                       const uint32_t* d_src, uint64_t src_stride, const uint32_t* d_patch, int skip_batch) {
+    NttxPassArgs a;
+    std::memset(&a, 0, sizeof a);
+    const int K = h.n_pass, lr = h.log_radix[k];
+    const uint64_t N = 1ull << h.log_n;
+    a.log_n = h.log_n; a.log_r = lr;
+    for (int q = 0; q < k; q++) a.log_p += h.log_radix[q];
+    a.log_s = h.log_n - a.log_p - lr;
+    a.n_pass = K; a.is_first = k == 0; a.is_final = k == K - 1;
+    for (int q = 0; q < K; q++) a.log_radix[q] = h.log_radix[q];
+    a.log_lb = h.log_lb;
+    a.in_len = in_len;
+    a.n = N;
+    if (a.is_first && !a.is_final && !d_patch)                      // zero-padded input: leading stages of pass 1 are copies
+        while (a.skip < lr && in_len <= (N >> (a.skip + 1))) a.skip++;
+    int lc = tile_log - lr;
+    if (lc < 0) lc = 0;
+    if (a.is_final) lc = K == 1 ? 0 : (lc < h.log_radix[0] ? lc : h.log_radix[0]);
+    else lc = lc < a.log_s ? lc : a.log_s;
+    a.log_c = lc;
+    const bool from_data = k == 0, to_data = (k == K - 1) && K > 1;
+    a.in = from_data ? (d_src ? const_cast<uint32_t*>(d_src) : d_data) : scratch;
+    a.in_stride = from_data ? (d_src ? src_stride : stride) : N;
+    a.patch = from_data ? d_patch : nullptr;
+    a.skip_batch = skip_batch;
+    a.in_planes = from_data ? 0 : 1;
+    a.out = to_data ? d_data : scratch;
+    a.out_stride = to_data ? stride : N;
+    a.out_planes = (to_data || K == 1) ? 0 : 1;
+    return a;
+}
+size_t pass_lds_bytes(const NttxPassArgs& a) {                       // the tile in three planes of 16 + 16 + 4 bytes per element
+    const size_t tile = (size_t)1 << (a.log_r + a.log_c);
+    return 2 * tile * 16 + tile * 4;
 }
 
 template <class X>
-int32_t launch_pass(const NttxPassArgs& a, unsigned long long n_tiles, uint32_t batch, hipStream_t st, bool r4) {
-    const size_t tile = (size_t)1 << (a.log_r + a.log_c);
-    const size_t lds = 2 * tile * 16 + tile * 4;
+int32_t launch_pass(const NttxPassArgs& a, uint32_t batch, hipStream_t st, bool r4) {
+    const unsigned n_tiles = (unsigned)(a.n >> (a.log_r + a.log_c));
+    const size_t lds = pass_lds_bytes(a);
     static bool attr_set[MAX_CTX] = {};                                  // per device (function attributes live in the device's code object)
     if (!attr_set[cur().logical]) {
         HIP_TRY(hipFuncSetAttribute((const void*)nttx_pass_kernel<X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
         HIP_TRY(hipFuncSetAttribute((const void*)nttx_pass_kernel<X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIP_TRY(hipFuncSetAttribute((const void*)nttx_pass_persistent_kernel<X, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
-        HIP_TRY(hipFuncSetAttribute((const void*)nttx_pass_persistent_kernel<X, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
         attr_set[cur().logical] = true;
     }
     ProfScope ps("ntt_pass", st);
-    // MZK_NTT_PERSISTENT = 1 / 2: the persistent pass with / without LDS-staged twiddles (ntt_fx.cuh) -- built and MEASURED in round 3
-    // (profiles/r03_ntt_experiments.txt): 0.647 / 0.679 ms per 2^22 transform against 0.603 ms for one tile per workgroup, which
-    // therefore stays the default.  Its 113 VGPRs (prefetched elements live across the stages) leave 2 workgroups per CU instead of 4.
-    static const int mode = std::getenv("MZK_NTT_PERSISTENT") ? std::atoi(std::getenv("MZK_NTT_PERSISTENT")) : 0;
-    const unsigned long long total = n_tiles * batch;
-    unsigned resident = 0;
-    const bool tw_lds = !a.is_final && mode != 2;                         // (mode 2: persistent without LDS-staged twiddles)
-    const size_t lds_p = lds + (tw_lds ? (((size_t)1 << a.log_r) - 1) * FS_TW_WORDS * 4 : 0);
-    if (mode) MZK_TRY((tw_lds ? persistent_grid<X, true>(lds_p, &resident) : persistent_grid<X, false>(lds_p, &resident)));
-    if (mode && total >= 3ull * resident && tile <= 2 * NTTX_THREADS && !a.patch && a.skip_batch < 0) {
-        int log_tiles = 0;
-        while ((1ull << log_tiles) < n_tiles) log_tiles++;
-        if (tw_lds) hipLaunchKernelGGL((nttx_pass_persistent_kernel<X, true>), dim3(resident), dim3(NTTX_THREADS), lds_p, st, a, log_tiles, total);
-        else hipLaunchKernelGGL((nttx_pass_persistent_kernel<X, false>), dim3(resident), dim3(NTTX_THREADS), lds_p, st, a, log_tiles, total);
-    } else if (r4) {
-        hipLaunchKernelGGL((nttx_pass_kernel<X, true>), dim3((unsigned)n_tiles, batch), dim3(NTTX_THREADS), lds, st, a);
-    } else {
-        hipLaunchKernelGGL((nttx_pass_kernel<X, false>), dim3((unsigned)n_tiles, batch), dim3(NTTX_THREADS), lds, st, a);
-    }
+    if (r4) hipLaunchKernelGGL((nttx_pass_kernel<X, true>), dim3(n_tiles, batch), dim3(NTTX_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((nttx_pass_kernel<X, false>), dim3(n_tiles, batch), dim3(NTTX_THREADS), lds, st, a);
     HIP_TRY(hipGetLastError());
     return MZK_OK;
 }
@@ -165,51 +171,20 @@ int32_t ntt_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n, bool in
     uint32_t* scratch = g_ws.ntt_scratch.as<uint32_t>();
     ProfScope total("ntt_total", st);
     const int K = pl->h.n_pass;
-    int log_p = 0;
     // transforms of at least 2^21 points take 2048-element tiles and stage pairs in registers (ntt_fx.cuh, R4): -4 % at 2^22, -7 % at 2^24;
     // smaller ones the 1024-element radix-2 form, which fills the chip with twice as many workgroups -- also in batches (the seven
     // 2^20-point class transforms of the quotient round measured 5.56-5.72 ms without and 5.75-5.78 ms with R4: profiles/r04_ntt_radix4.txt).
     // MZK_NTT_NO_RADIX4=1: the round-3 form everywhere (A/B).
     static const bool no_r4 = std::getenv("MZK_NTT_NO_RADIX4") != nullptr;
     const bool r4 = !no_r4 && N >= (1ull << 21);
-    static const int tile_rt = std::getenv("MZK_NTT_TILE_LOG_RT") ? std::atoi(std::getenv("MZK_NTT_TILE_LOG_RT")) : 0;      // (experiment switch, see ntt.cuh)
-    const int tile_log = r4 ? (tile_rt >= 11 && tile_rt <= 12 ? tile_rt : 11) : NTT_TILE_LOG;
     for (int k = 0; k < K; k++) {
-        NttxPassArgs a;
-        std::memset(&a, 0, sizeof a);
-        const int lr = pl->h.log_radix[k];
-        a.log_n = log_n; a.log_r = lr; a.log_p = log_p; a.log_s = log_n - log_p - lr;
-        a.n_pass = K; a.is_first = k == 0; a.is_final = k == K - 1;
-        for (int q = 0; q < K; q++) a.log_radix[q] = pl->h.log_radix[q];
-        a.log_lb = pl->h.log_lb;
+        NttxPassArgs a = pass_args(pl->h, k, r4 ? 11 : NTT_TILE_LOG, d_data, stride, scratch, in_len, d_src, src_stride, d_patch, skip_batch);
         a.stage_tw = pl->d_stage[k];
         a.t_full = pl->d_tfull[k];
         a.f_lo = pl->d_flo;             // non-null only for an inverse coset transform
         a.f_hi = pl->d_fhi;
         a.f_one = pl->h.final_factor ? pl->d_fone : nullptr;
-        a.in_len = in_len;
-        a.n = N;
-        if (a.is_first && !a.is_final && !d_patch)                      // zero-padded input: leading stages of pass 1 are copies
-            while (a.skip < lr && in_len <= (N >> (a.skip + 1))) a.skip++;
-        int lc = tile_log - lr;
-        if (lc < 0) lc = 0;
-        if (a.is_final) lc = K == 1 ? 0 : (lc < pl->h.log_radix[0] ? lc : pl->h.log_radix[0]);
-        else lc = lc < a.log_s ? lc : a.log_s;
-        a.log_c = lc;
-        // pass 1 reads the caller's buffer, middle passes run in place on scratch, the last pass
-        // writes back to the caller's buffer (K = 1: data -> scratch, copied back below)
-        const bool from_data = k == 0, to_data = (k == K - 1) && K > 1;
-        a.in = from_data ? (d_src ? const_cast<uint32_t*>(d_src) : d_data) : scratch;
-        a.in_stride = from_data ? (d_src ? src_stride : stride) : N;
-        a.patch = from_data ? d_patch : nullptr;
-        a.skip_batch = skip_batch;
-        a.in_planes = from_data ? 0 : 1;
-        a.out = to_data ? d_data : scratch;
-        a.out_stride = to_data ? stride : N;
-        a.out_planes = (to_data || K == 1) ? 0 : 1;
-        const unsigned long long n_tiles = N >> (lr + lc);
-        MZK_TRY((launch_pass<X>(a, n_tiles, batch, st, r4)));
-        log_p += lr;
+        MZK_TRY((launch_pass<X>(a, batch, st, r4)));
     }
     if (K == 1)
         HIP_TRY(hipMemcpy2DAsync(d_data, stride * 32, scratch, N * 32, N * 32, batch, hipMemcpyDeviceToDevice, st));
@@ -242,17 +217,10 @@ int32_t ntt_classes_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n,
     MZK_TRY(g_ws.ntt_scratch.reserve((size_t)batch * N * 36));
     uint32_t* scratch = g_ws.ntt_scratch.as<uint32_t>();
     ProfScope total("ntt_total", st);
-    int log_p = 0;
     for (int k = 0; k < K; k++) {
-        NttxPassArgs a;
-        std::memset(&a, 0, sizeof a);
+        const NttxPassArgs a = pass_args(pl[0]->h, k, NTT_TILE_LOG, d_data, stride, scratch, in_len, d_src, src_stride, d_patch, skip_batch);
         NttxClasses mc;
         std::memset(&mc, 0, sizeof mc);
-        const int lr = pl[0]->h.log_radix[k];
-        a.log_n = log_n; a.log_r = lr; a.log_p = log_p; a.log_s = log_n - log_p - lr;
-        a.n_pass = K; a.is_first = k == 0; a.is_final = k == K - 1;
-        for (int q = 0; q < K; q++) a.log_radix[q] = pl[0]->h.log_radix[q];
-        a.log_lb = pl[0]->h.log_lb;
         mc.rows = rows;
         mc.shared_in = d_src ? 1 : 0;
         for (int c = 0; c < n_classes; c++) {
@@ -262,30 +230,10 @@ int32_t ntt_classes_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n,
             mc.f_hi[c] = pl[c]->d_fhi;
             mc.f_one[c] = pl[c]->h.final_factor ? pl[c]->d_fone : nullptr;
         }
-        a.in_len = in_len;
-        a.n = N;
-        if (a.is_first && !d_patch)
-            while (a.skip < lr && in_len <= (N >> (a.skip + 1))) a.skip++;
-        int lc = NTT_TILE_LOG - lr;
-        if (lc < 0) lc = 0;
-        if (a.is_final) lc = lc < pl[0]->h.log_radix[0] ? lc : pl[0]->h.log_radix[0];
-        else lc = lc < a.log_s ? lc : a.log_s;
-        a.log_c = lc;
-        const bool from_data = k == 0, to_data = k == K - 1;
-        a.in = from_data ? (d_src ? const_cast<uint32_t*>(d_src) : d_data) : scratch;
-        a.in_stride = from_data ? (d_src ? src_stride : stride) : N;
-        a.patch = from_data ? d_patch : nullptr;
-        a.skip_batch = skip_batch;
-        a.in_planes = from_data ? 0 : 1;
-        a.out = to_data ? d_data : scratch;
-        a.out_stride = to_data ? stride : N;
-        a.out_planes = to_data ? 0 : 1;
-        const unsigned long long n_tiles = N >> (lr + lc);
-        const size_t tile = (size_t)1 << (lr + lc);
+        const unsigned n_tiles = (unsigned)(N >> (a.log_r + a.log_c));
         ProfScope ps("ntt_pass", st);
-        hipLaunchKernelGGL((nttx_pass_classes_kernel<X>), dim3((unsigned)n_tiles, (unsigned)batch), dim3(NTTX_THREADS), 2 * tile * 16 + tile * 4, st, a, mc);
+        hipLaunchKernelGGL((nttx_pass_classes_kernel<X>), dim3(n_tiles, (unsigned)batch), dim3(NTTX_THREADS), pass_lds_bytes(a), st, a, mc);
         HIP_TRY(hipGetLastError());
-        log_p += lr;
     }
     MZK_TRY(ws_release(st));
     return MZK_OK;
@@ -311,8 +259,8 @@ int32_t ntt_dispatch(int curve, uint32_t* d_data, uint64_t in_len, int log_n, bo
 }
 
 void ntt_release_plans() {
-    for (auto& kv : g_plans) free_plan(kv.second.get());
-    g_plans.clear();
+    for (auto& kv : plans()) free_plan(kv.second.get());
+    plans().clear();
 }
 
 }  // namespace mzk
