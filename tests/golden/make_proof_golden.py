@@ -1,4 +1,4 @@
-"""tests/golden/make_proof_golden.py -- generates tests/golden/proof_vectors.json on the CPU.
+"""tests/golden/make_proof_golden.py -- generates tests/golden/proof_vectors.json (and its siblings, see __main__) on the CPU.
 
 Whole proofs of the reference's bench circuit (plonk/benches/bench.rs:29-46) by the big-int restatements alone
 (oracle/pyref_circuit.py builds the circuit, oracle/pyref_snark.py proves it with schoolbook polynomial arithmetic), with the
@@ -73,30 +73,35 @@ def build(curve_id, plonk_type, num_gates, range_bits, rng=None, want_core=False
 GENERAL_CASES = [(0, "TurboPlonk", 4, 11), (1, "TurboPlonk", 5, 12), (1, "UltraPlonk", 4, 13), (0, "UltraPlonk", 5, 14)]
 
 
-def general_instance(curve_id, plonk_type, log_n, seed):
+# the same four shapes with gates="all": every selector column non-zero (q_lc[2..3], q_hash[1..2] and q_ecc are zero in GENERAL_CASES)
+FULL_CASES = [(0, "TurboPlonk", 4, 21), (1, "TurboPlonk", 5, 22), (1, "UltraPlonk", 4, 23), (0, "UltraPlonk", 5, 24)]
+
+
+def general_instance(curve_id, plonk_type, log_n, seed, gates="hot"):
     """The circuit of one general case: (selector values, sigma values, k, wire values, public-input vector, public input, tables | None)."""
     import random
     pc = P.CURVES[curve_id]
     rnd = random.Random(seed)
     tables = None
     if plonk_type == "UltraPlonk":
-        sel, sigma, k, w, pi, tables = PC.general_ultra_circuit(pc, log_n, rnd)
+        sel, sigma, k, w, pi, tables = PC.general_ultra_circuit(pc, log_n, rnd, gates=gates)
     else:
-        sel, sigma, k, w, pi = PC.general_circuit(pc, log_n, rnd)
+        sel, sigma, k, w, pi = PC.general_circuit(pc, log_n, rnd, gates=gates)
     pub = pi[:4]                                                          # the public input sits on rows 0 .. 3 (row 3 is non-zero)
     assert pub[3] != 0 and not any(pi[4:])
     return sel, sigma, k, w, pi, pub, tables
 
 
-def build_general(curve_id, plonk_type, log_n, seed):
+def build_general(curve_id, plonk_type, log_n, seed, gates="hot"):
     """A whole proof of a GENERAL circuit -- a non-zero public input, addition / multiplication / x^5 gates, copy constraints over all
     wires, key and range lookups (UltraPlonk) -- by the schoolbook prover, `test_rng` drawing the SRS trapdoor and then the blinders as in
     `build`.  The same instance is rebuilt from (log_n, seed) by the GPU tests, which must emit these bytes from the Python mirror, the
-    round-level C ABI and `mzk_prove file`."""
+    round-level C ABI and `mzk_prove file`.  gates="all" (FULL_CASES): linear combinations and x^5 over four wires, the ecc product and
+    rows carrying all thirteen gate terms at once; the record then names the mode and counts each selector's non-zero entries."""
     pc = P.CURVES[curve_id]
     ultra = plonk_type == "UltraPlonk"
     W = 6 if ultra else 5
-    sel, sigma, k, w, pi, pub, tables = general_instance(curve_id, plonk_type, log_n, seed)
+    sel, sigma, k, w, pi, pub, tables = general_instance(curve_id, plonk_type, log_n, seed, gates)
     rng = RNG.test_rng()
     srs_beta = RNG.fr_rand(pc, rng)
     blind = RNG.draw_blinders(pc, rng, W, ultra)
@@ -111,6 +116,9 @@ def build_general(curve_id, plonk_type, log_n, seed):
            "selector_comms": [g1(p).hex() for p in vk["selector_comms"]], "sigma_comms": [g1(p).hex() for p in vk["sigma_comms"]],
            "plookup_comms": {name: g1(p).hex() for name, p in vk["plookup"].items()} if ultra else None,
            "challenges": {name: "%x" % v for name, v in out["challenges"].items()}, "proof": out["proof"].hex()}
+    if gates != "hot":
+        rec["gates_mode"] = gates
+        rec["selector_nonzero"] = [sum(1 for v in col if v) for col in sel]
     return rec
 
 
@@ -138,6 +146,32 @@ def build_batch(curve_id, plonk_type, gates, range_bits):
     out = PS.batch_prove(pc, n.bit_length() - 1, instances, [[] for _ in gates], quot, srs_beta, FS.StandardTranscript(pc, b"PlonkProof"),
                          g1, lambda x: FS.fr_bytes(pc, x))
     return {"curve": curve_id, "plonk_type": plonk_type, "gates": list(gates), "range_bit_len": range_bits, "domain_size": n, "srs_beta": "%x" % srs_beta,
+            "challenges": {name: "%x" % v for name, v in out["challenges"].items()}, "batch_proof": out["proof"].hex()}
+
+
+# (curve, plonk type, log2 domain size, builder seeds): general circuits with gates="all", so that alpha_base != 1 scales live q_ecc / q_hash terms
+FULL_BATCH_CASES = [(0, "TurboPlonk", 4, (31, 32))]
+
+
+def build_full_batch(curve_id, plonk_type, log_n, seeds):
+    """PlonkKzgSnark::batch_prove over all-selector general circuits of one domain size, each with its non-zero public input, by the
+    restatements; `test_rng` draws as in build_batch."""
+    pc = P.CURVES[curve_id]
+    ultra = plonk_type == "UltraPlonk"
+    W = 6 if ultra else 5
+    rng = RNG.test_rng()
+    srs_beta = RNG.fr_rand(pc, rng)
+    blinds, quot = RNG.draw_batch_blinders(pc, rng, W, [ultra] * len(seeds))
+    instances, pubs, counts = [], [], []
+    for seed, bl in zip(seeds, blinds):
+        sel, sigma, k, w, pi, pub, tables = general_instance(curve_id, plonk_type, log_n, seed, "all")
+        instances.append({"selector_vals": sel, "sigma_vals": sigma, "k": k, "wire_vals": w, "pi_vals": pi, "blind": bl, "plookup": tables})
+        pubs.append(pub)
+        counts.append([sum(1 for v in col if v) for col in sel])
+    out = PS.batch_prove(pc, log_n, instances, pubs, quot, srs_beta, FS.StandardTranscript(pc, b"PlonkProof"), lambda p: FS.g1_bytes(pc, p),
+                         lambda x: FS.fr_bytes(pc, x))
+    return {"curve": curve_id, "plonk_type": plonk_type, "log_n": log_n, "seeds": list(seeds), "domain_size": 1 << log_n, "gates_mode": "all",
+            "srs_beta": "%x" % srs_beta, "public_inputs": [["%x" % x for x in pub] for pub in pubs], "selector_nonzero": counts,
             "challenges": {name: "%x" % v for name, v in out["challenges"].items()}, "batch_proof": out["proof"].hex()}
 
 
@@ -180,6 +214,10 @@ if __name__ == "__main__":
     with open(os.path.join(HERE, "general_proof_vectors.json"), "w") as f:
         json.dump(general, f, indent=1)
     print("wrote", len(general), "general-circuit proof vectors:", [(v["plonk_type"], v["domain_size"], v["gates"]) for v in general])
+    full = {"proofs": [build_general(*case, gates="all") for case in FULL_CASES], "batches": [build_full_batch(*case) for case in FULL_BATCH_CASES]}
+    with open(os.path.join(HERE, "full_selector_proof_vectors.json"), "w") as f:
+        json.dump(full, f, indent=1)
+    print("wrote", len(full["proofs"]), "all-selector proof vectors and", len(full["batches"]), "batch vector:", [v["selector_nonzero"] for v in full["proofs"]])
     batches = [build_batch(*case) for case in BATCH_CASES]
     with open(os.path.join(HERE, "batch_vectors.json"), "w") as f:
         json.dump(batches, f, indent=1)

@@ -73,23 +73,47 @@ def test_golden_proof_vectors_over_the_reference_testing_setup(pyref, mj, index)
     assert not V.verify(pc, fresh(), vk, [], bytes(bad), g, int(vec["srs_beta"], 16))
 
 
-@pytest.mark.parametrize("index", [0, 1, 2, 3])
-def test_golden_general_circuit_proof_vectors(pyref, index):
+def full_selector_vectors():
+    """tests/golden/full_selector_proof_vectors.json: {"proofs": four single proofs, "batches": one aggregated proof}"""
+    return load_golden("full_selector_proof_vectors")
+
+
+def general_vectors(name):
+    """the list of single-proof vectors of either general-circuit file"""
+    return full_selector_vectors()["proofs"] if name == "full_selector_proof_vectors" else load_golden(name)
+
+
+GENERAL_FILES = [pytest.param("general_proof_vectors", i, id=str(i)) for i in range(4)] + [pytest.param("full_selector_proof_vectors", i, id="all-%d" % i) for i in range(4)]
+
+
+@pytest.mark.parametrize("name,index", GENERAL_FILES)
+def test_golden_general_circuit_proof_vectors(pyref, name, index):
     """tests/golden/general_proof_vectors.json: whole proofs of GENERAL circuits (non-zero public input, addition / multiplication / x^5
     gates, copy constraints, key + range lookups) by the schoolbook prover -- regenerated identically; the restated reference verifier
-    accepts them with their public input in the pairing form, and rejects a changed public input or proof byte."""
+    accepts them with their public input in the pairing form, and rejects a changed public input or proof byte.  Those circuits leave
+    q_lc[2..3], q_hash[1..2] and q_ecc zero; tests/golden/full_selector_proof_vectors.json holds the same four shapes with gates="all",
+    every selector column non-zero (both files oracle-derived, parity with the Rust code unpinned).  For the latter the verifier must
+    also REFUSE a verifying key in which the commitment to q_ecc, q_lc[2], q_lc[3], q_hash[1] or q_hash[2] is replaced by the identity:
+    its check depends on those terms, which is what lets the device comparison against these bytes see them."""
     import pyref_verifier as V
-    vec = load_golden("general_proof_vectors")[index]
+    full = name == "full_selector_proof_vectors"
+    vec = general_vectors(name)[index]
     gen = _generator()
-    assert (vec["curve"], vec["plonk_type"], vec["log_n"], vec["seed"]) == gen.GENERAL_CASES[index]
-    assert gen.build_general(*gen.GENERAL_CASES[index]) == vec, "tests/golden/general_proof_vectors.json is stale: run tests/golden/make_proof_golden.py"
+    cases = gen.FULL_CASES if full else gen.GENERAL_CASES
+    assert (vec["curve"], vec["plonk_type"], vec["log_n"], vec["seed"]) == cases[index]
+    assert gen.build_general(*cases[index], **({"gates": "all"} if full else {})) == vec, "tests/golden/%s.json is stale: run tests/golden/make_proof_golden.py" % name
     g = vec["gates"]
     assert g["addition"] and g["multiplication"] and g["x^5"] and g["constant"] and (g["lookup"] > 0) == (vec["plonk_type"] == "UltraPlonk")
+    if full:
+        assert vec["gates_mode"] == "all" and len(vec["selector_nonzero"]) == (14 if vec["plonk_type"] == "UltraPlonk" else 13) and all(vec["selector_nonzero"])
+    else:
+        assert "gates_mode" not in vec
     pc = pyref.CURVES[vec["curve"]]
     pub = [int(x, 16) for x in vec["public_input"]]
     assert any(pub)
     vk = golden_vk(V, pc, vec)
     vk["num_inputs"] = len(pub)
+    assert all(cm is not None for cm in vk["selector_comms"]) == full
     proof = bytes.fromhex(vec["proof"])
     srs_beta = int(vec["srs_beta"], 16)
     fresh = lambda: FS.StandardTranscript(pc, b"PlonkProof")
@@ -101,6 +125,98 @@ def test_golden_general_circuit_proof_vectors(pyref, index):
     bad = bytearray(proof)
     bad[-40 if vec["plookup_comms"] is None else -2] ^= 1
     assert not V.verify(pc, fresh(), vk, pub, bytes(bad), pyref.g1_gen(pc), srs_beta)
+    if full:
+        pr = V.deserialize_proof(pc, proof)
+        for j in (12, 2, 7, 3, 8):
+            comms = list(vk["selector_comms"])
+            comms[j] = None
+            # past the transcript (which absorbs the key): the proof's own challenges, so that only the linearisation term is missing
+            assert not V.batch_verify_opening_proof(pc, pyref.g1_gen(pc), srs_beta, V.prepare_pcs_info(pc, dict(vk, selector_comms=comms), pub, pr, ch)), j
+            assert not V.verify(pc, fresh(), dict(vk, selector_comms=comms), pub, proof, pyref.g1_gen(pc), srs_beta), j
+
+
+def _trapdoor_vk(pyref, pc, n, k, sel, sigma, num_inputs, srs_beta):
+    """VerifyingKey of a TurboPlonk circuit given by its values, committed through the trapdoor"""
+    log_n = n.bit_length() - 1
+    G = pyref.g1_gen(pc)
+    commit = lambda vals: pyref.g1_mul(pc, pyref.poly_eval(pc, pyref.ntt_fast(pc, list(vals), log_n, 1, inverse=True), srs_beta), G) if any(vals) else None
+    return {"domain_size": n, "num_inputs": num_inputs, "k": list(k), "selector_comms": [commit(s) for s in sel], "sigma_comms": [commit(s) for s in sigma], "plookup": None}
+
+
+def test_golden_full_selector_batch_vector(pyref):
+    """tests/golden/full_selector_proof_vectors.json "batches": one BatchProof over two all-selector TurboPlonk circuits, each with its
+    non-zero public input (alpha_base = alpha^3 scales live q_ecc / q_hash / q_lc[2..3] terms of the second) -- regenerated identically,
+    accepted by the restated batch verifier in the pairing form, refused with the keys swapped or one q_ecc commitment dropped."""
+    import pyref_verifier as V
+    (vec,) = full_selector_vectors()["batches"]
+    gen = _generator()
+    (case,) = gen.FULL_BATCH_CASES
+    assert gen.build_full_batch(*case) == vec, "tests/golden/full_selector_proof_vectors.json is stale: run tests/golden/make_proof_golden.py"
+    assert vec["gates_mode"] == "all" and all(len(cnt) == 13 and all(cnt) for cnt in vec["selector_nonzero"])
+    pc = pyref.CURVES[vec["curve"]]
+    srs_beta = int(vec["srs_beta"], 16)
+    vks, pubs = [], []
+    for seed in vec["seeds"]:
+        sel, sigma, k, w, pi, pub, _ = gen.general_instance(vec["curve"], vec["plonk_type"], vec["log_n"], seed, "all")
+        vks.append(_trapdoor_vk(pyref, pc, vec["domain_size"], k, sel, sigma, len(pub), srs_beta))
+        pubs.append(pub)
+    assert [["%x" % x for x in pub] for pub in pubs] == vec["public_inputs"] and all(any(pub) for pub in pubs)
+    blob = bytes.fromhex(vec["batch_proof"])
+    fresh = lambda: FS.StandardTranscript(pc, b"PlonkProof")
+    G = pyref.g1_gen(pc)
+    assert V.verify_batch_proof(pc, fresh(), vks, pubs, blob, None, None, open_key=V.open_key_for_testing(pc, srs_beta))
+    assert not V.verify_batch_proof(pc, fresh(), vks[::-1], pubs, blob, G, srs_beta)
+    for which in (0, 1):
+        comms = list(vks[which]["selector_comms"])
+        comms[12] = None
+        changed = list(vks)
+        changed[which] = dict(vks[which], selector_comms=comms)
+        assert not V.verify_batch_proof(pc, fresh(), changed, pubs, blob, G, srs_beta), which
+
+
+def _gpu_general_cases():
+    """(curve id, UltraPlonk?, log2 domain size, builder seed, instances drawn from that rng) of every general circuit the GPU tests prove"""
+    import general_cases as GC
+    out = [(c, u, l, GC.round_level_seed(c, u, l), 1) for c, u, l in GC.ROUND_LEVEL + GC.ROUND_LEVEL_ALL_ONLY]
+    out += [(c, u, l, GC.unsatisfied_seed(c, u, l), 1) for c, u, l in GC.UNSATISFIED]
+    out += [(c, u, l, GC.batch_seed(c, u, l), 3) for c, u, l in GC.BATCH]
+    out += [(c, u, l, GC.verifier_seed(c, u, l), 1) for c, u, l in GC.VERIFIER]
+    out += [(c, u, l, GC.cpp_file_seed(c, u, l), 1) for c, u, l, _ in GC.CPP_FILE + GC.CPP_FILE_ALL_ONLY]
+    return sorted(set(out))
+
+
+@pytest.mark.parametrize("curve_id,ultra,log_n,seed,count", _gpu_general_cases())
+def test_all_selector_circuits_leave_no_selector_zero(pyref, curve_id, ultra, log_n, seed, count):
+    """Every gates="all" circuit the GPU suite proves (tests/general_cases.py): each of the 13 (14) selector columns has a non-zero entry --
+    q_lc[2..3], q_hash[1..2], q_ecc among them, zero with the default -- and every row satisfies the gate identity, copy cycles through
+    gate inputs included; with the default gates the five are zero, which is the gap the all-selector cases close."""
+    import random
+    import general_cases as GC
+    import pyref_circuit as PC
+    pc = pyref.CURVES[curve_id]
+    for gates in ("all", "hot"):
+        rng = random.Random(seed)
+        for _ in range(count):
+            sel, sigma, k, w, pi, *_ = (PC.general_ultra_circuit if ultra else PC.general_circuit)(pc, log_n, rng, gates=gates)
+            nz = GC.nonzero_selectors(sel)
+            assert len(nz) == (14 if ultra else 13)
+            if gates == "all":
+                assert all(nz), nz
+                assert _copy_constraints_hold(pc, k, log_n, sigma, w)
+            else:
+                assert [j for j, cnt in enumerate(nz) if not cnt] == [2, 3, 7, 8, 12]
+            assert PC.check_gate_rows(pc, sel, w, pi)
+
+
+def _copy_constraints_hold(pc, k, log_n, sigma, w):
+    """every cell holds the value of the cell its sigma value k[wire] * w_n^row names"""
+    w_n, cell = pc.root_of_unity(log_n), {}
+    for j, kj in enumerate(k):
+        x = kj
+        for i in range(1 << log_n):
+            cell[x] = (j, i)
+            x = x * w_n % pc.r
+    return all(w[j][i] == w[cell[v][0]][cell[v][1]] for j, col in enumerate(sigma) for i, v in enumerate(col))
 
 
 @pytest.mark.parametrize("index", [0, 1])

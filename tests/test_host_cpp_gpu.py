@@ -5,6 +5,7 @@ import os
 import subprocess
 
 import pytest
+import general_cases as GC
 import pyref_fs as FS
 
 pytestmark = pytest.mark.gpu
@@ -191,12 +192,14 @@ def test_unsatisfied_witness_at_the_smallest_domain(gpu, mj):
     assert out.returncode == 1 and "WrongQuotientPolyDegree" in out.stderr and "proof_hex" not in out.stdout
 
 
-@pytest.mark.parametrize("curve_id,ultra,log_n,gpus", [(0, False, 6, 1), (1, True, 6, 1), (1, False, 9, 1), (0, True, 8, 1), (0, False, 7, 3), (1, True, 6, 2)])
-def test_cpp_host_proves_a_general_circuit_from_a_file(gpu, mj, pyref, tmp_path, curve_id, ultra, log_n, gpus):
+@pytest.mark.parametrize("curve_id,ultra,log_n,gpus,gates", GC.with_gates(GC.CPP_FILE, GC.CPP_FILE_ALL_ONLY))
+def test_cpp_host_proves_a_general_circuit_from_a_file(gpu, mj, pyref, tmp_path, curve_id, ultra, log_n, gpus, gates):
     """`mzk_prove <curve> file <path>`: ANY finalised circuit -- a non-zero public input, add / mul / x^5 gates, copy constraints over all
     wires, key and range lookups -- handed over as the arrays `Arithmetization` exposes (mpc-jellyfish_amd/circuit_io.py).  The compiled host
     is a thin client of the library's round-level entry points (mzk_prover_*): its bytes must equal the Python mirror's (which sequences
-    the primitives itself) and the restated reference verifier must accept them; on several (virtual) devices the same bytes again."""
+    the primitives itself) and the restated reference verifier must accept them; on several (virtual) devices the same bytes again.
+    gates="all": every selector column non-zero, Turbo and Ultra at 1, 2 and 3 devices -- the one route by which the linearisation
+    polynomial cut by coefficient range and the class-sharded quotient see live q_ecc / q_hash[1..2] / q_lc[2..3]."""
     import random
     from importlib import import_module
     import numpy as np
@@ -205,12 +208,13 @@ def test_cpp_host_proves_a_general_circuit_from_a_file(gpu, mj, pyref, tmp_path,
     io = import_module("mpc-jellyfish_amd.circuit_io")
     c, pc = mj.params.CURVES[curve_id], pyref.CURVES[curve_id]
     n, W = 1 << log_n, 6 if ultra else 5
-    rng = random.Random(31 + curve_id + log_n)
+    rng = random.Random(GC.cpp_file_seed(curve_id, ultra, log_n))
     tabs = None
     if ultra:
-        sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, rng)
+        sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, rng, gates=gates)
     else:
-        sel, sig, k, w, pi = build_circuit(pc, log_n, rng)
+        sel, sig, k, w, pi = build_circuit(pc, log_n, rng, gates=gates)
+    assert all(GC.nonzero_selectors(sel)) == (gates == "all")
     pub = pi[:4]
     path = str(tmp_path / "circuit.bin")
     io.write_circuit(path, c, log_n, sel, sig, k, w, pub_input=pub, tables=tabs)

@@ -13,6 +13,7 @@ import pytest
 import mirror_prover as MP          # the primitive-level sequencing of the rounds: test code since round 5
 
 from conftest import build_circuit, build_ultra_circuit, fr_mont_limbs, load_golden, verifying_key
+import general_cases as GC
 import pyref_fs as FS
 
 pytestmark = pytest.mark.gpu
@@ -26,26 +27,31 @@ def _native(mj):
                                  batch_prove=mj.batch.batch_prove, round3=mj.prover.round3, round5=mj.prover.round5)
 
 
-def _general_instance(mj, pc, c, log_n, ultra, rng):
+def _general_instance(mj, pc, c, log_n, ultra, rng, gates="hot"):
+    """gates="hot": additions, multiplications and x^5 over two wires -- q_lc[2..3], q_hash[1..2] and q_ecc are the zero polynomial;
+    gates="all": every selector column is non-zero (asserted), so every scalar of the linearisation polynomial multiplies a live one."""
     dom = mj.Radix2EvaluationDomain(c, log_n)
     tabs = None
     if ultra:
-        sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, rng)
+        sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, rng, gates=gates)
     else:
-        sel, sig, k, w, pi = build_circuit(pc, log_n, rng)
+        sel, sig, k, w, pi = build_circuit(pc, log_n, rng, gates=gates)
+    assert all(GC.nonzero_selectors(sel)) == (gates == "all")
     kw = {"plookup": {name: dom.ifft(fr_mont_limbs(c, tabs[key])) for name, key in zip(mj.plonk.PLOOKUP_TABLE_POLYS, TABLES)}} if ultra else {}
     sel_p, sig_p = [dom.ifft(fr_mont_limbs(c, s)) for s in sel], [dom.ifft(fr_mont_limbs(c, s)) for s in sig]
     return sel_p, sig_p, k, np.stack([fr_mont_limbs(c, col) for col in w]), pi, kw
 
 
-@pytest.mark.parametrize("curve_id,ultra,log_n", [(0, False, 6), (1, False, 9), (1, True, 6), (0, True, 8), (0, False, 3), (1, True, 4), (0, False, 12)])
-def test_round_level_abi_on_general_circuits(gpu, mj, pyref, curve_id, ultra, log_n):
+@pytest.mark.parametrize("curve_id,ultra,log_n,gates", GC.with_gates(GC.ROUND_LEVEL, GC.ROUND_LEVEL_ALL_ONLY))
+def test_round_level_abi_on_general_circuits(gpu, mj, pyref, curve_id, ultra, log_n, gates):
+    """Every size again with gates="all" (and 2^14 on top: all residue classes in one launch per step, W classes + top coefficients,
+    with degree-(6n+4) q_hash / q_ecc terms): library bytes = mirror bytes, the restated verifier accepts, device wires give the same."""
     import pyref_verifier as V
     N = _native(mj)
     c, pc = mj.params.CURVES[curve_id], pyref.CURVES[curve_id]
     n, r, W = 1 << log_n, c.r, 6 if ultra else 5
-    rng = random.Random(9100 + curve_id + 2 * ultra + log_n)
-    sel_p, sig_p, k, wires, pi, kw = _general_instance(mj, pc, c, log_n, ultra, rng)
+    rng = random.Random(GC.round_level_seed(curve_id, ultra, log_n))
+    sel_p, sig_p, k, wires, pi, kw = _general_instance(mj, pc, c, log_n, ultra, rng, gates)
     srs_beta = rng.randrange(1, r)
     ck = mj.UnivariateProverParam.gen_srs_for_testing(c, srs_beta, n + 2)
     mirror = MP.TurboPlonkProver(c, n, sel_p, sig_p, k, ck, **kw)
@@ -80,15 +86,17 @@ def test_round_level_abi_on_general_circuits(gpu, mj, pyref, curve_id, ultra, lo
     ck.release()
 
 
-@pytest.mark.parametrize("curve_id,ultra,log_n", [(0, False, 6), (1, True, 6), (1, False, 3)])
-def test_unsatisfied_witness_is_rejected_under_the_reference_error_name(gpu, mj, pyref, curve_id, ultra, log_n):
+@pytest.mark.parametrize("curve_id,ultra,log_n,gates", GC.with_gates(GC.UNSATISFIED))
+def test_unsatisfied_witness_is_rejected_under_the_reference_error_name(gpu, mj, pyref, curve_id, ultra, log_n, gates):
     """prover.rs:915-918: WrongQuotientPolyDegree.  With the quotient's top coefficients taken from its numerator the guard is the
-    identity at zeta, at the end of round 5 (the tiny-domain path that keeps the reference's own degree guard in round 3: next test)."""
+    identity at zeta, at the end of round 5 (the tiny-domain path that keeps the reference's own degree guard in round 3: next test).
+    gates="all": one changed cell per kind of row -- wire 2 of a linear combination, wire 1 of a power-5 row, a wire of an ecc row,
+    the output of a row with every term -- each refused."""
     N = _native(mj)
     c, pc = mj.params.CURVES[curve_id], pyref.CURVES[curve_id]
     n, r, W = 1 << log_n, c.r, 6 if ultra else 5
-    rng = random.Random(77 + curve_id)
-    sel_p, sig_p, k, wires, pi, kw = _general_instance(mj, pc, c, log_n, ultra, rng)
+    rng = random.Random(GC.unsatisfied_seed(curve_id, ultra, log_n))
+    sel_p, sig_p, k, wires, pi, kw = _general_instance(mj, pc, c, log_n, ultra, rng, gates)
     ck = mj.UnivariateProverParam.gen_srs_for_testing(c, rng.randrange(1, r), n + 2)
     native = N.NativeProver(c, n, sel_p, sig_p, k, ck, **kw)
     blind = mj.snark.draw_blinders(c, mj.rng.test_rng(), W, ultra)
@@ -99,6 +107,20 @@ def test_unsatisfied_witness_is_rejected_under_the_reference_error_name(gpu, mj,
     with pytest.raises(mj.plonk.PlonkError) as e:
         native.prove(bad, pub, mj.prover.TranscriptChallenges(native, pub), blind)
     assert e.value.kind == "WrongQuotientPolyDegree"
+    if gates == "all":
+        sel = (build_ultra_circuit if ultra else build_circuit)(pc, log_n, random.Random(GC.unsatisfied_seed(curve_id, ultra, log_n)), gates=gates)[0]
+        row = lambda cond: next(i for i in range(n) if cond(lambda j: sel[j][i] != 0))
+        lc = row(lambda nz: nz(2) and not nz(12))
+        pow5 = row(lambda nz: nz(7) and not nz(12))
+        ecc = row(lambda nz: nz(12) and not nz(10))
+        mixed = row(lambda nz: nz(12) and nz(10) and nz(2) and nz(7))
+        assert len({lc, pow5, ecc, mixed}) == 4
+        for wire, at in ((2, lc), (1, pow5), (3, ecc), (4, mixed)):
+            bad = wires.copy()
+            bad[wire, at] = fr_mont_limbs(c, [rng.randrange(r)])[0]
+            with pytest.raises(mj.plonk.PlonkError) as e:
+                native.prove(bad, pub, mj.prover.TranscriptChallenges(native, pub), blind)
+            assert e.value.kind == "WrongQuotientPolyDegree", (wire, at)
     # a public input the circuit does not hold (asserted wrongly as zero included) trips it too
     for wrong in ([], pub[:3] + [(pub[3] + 1) % r]):
         with pytest.raises(mj.plonk.PlonkError):
@@ -249,17 +271,20 @@ def test_golden_proofs_through_the_round_level_abi(gpu, mj, index, lagrange):
     ck.release()
 
 
-@pytest.mark.parametrize("curve_id,ultra,log_n", [(0, False, 5), (1, True, 5)])
-def test_batch_prove_over_native_handles_matches_the_mirror(gpu, mj, pyref, curve_id, ultra, log_n):
-    """PlonkKzgSnark::batch_prove (snark.rs:64-78): K handles, rounds 3 and 5 once over all of them (alpha_base_k = alpha^(3k) / alpha^(7k))."""
+@pytest.mark.parametrize("curve_id,ultra,log_n,gates", GC.with_gates(GC.BATCH))
+def test_batch_prove_over_native_handles_matches_the_mirror(gpu, mj, pyref, curve_id, ultra, log_n, gates):
+    """PlonkKzgSnark::batch_prove (snark.rs:64-78): K handles, rounds 3 and 5 once over all of them (alpha_base_k = alpha^(3k) / alpha^(7k));
+    the restated batch verifier accepts the aggregate.  gates="all": alpha_base scales live q_ecc / q_hash / q_lc[2..3] terms."""
+    import pyref_verifier as V
     N = _native(mj)
     c, pc = mj.params.CURVES[curve_id], pyref.CURVES[curve_id]
     n, r, W = 1 << log_n, c.r, 6 if ultra else 5
-    rng = random.Random(600 + curve_id)
-    ck = mj.UnivariateProverParam.gen_srs_for_testing(c, rng.randrange(1, r), n + 2)
+    rng = random.Random(GC.batch_seed(curve_id, ultra, log_n))
+    srs_beta = rng.randrange(1, r)
+    ck = mj.UnivariateProverParam.gen_srs_for_testing(c, srs_beta, n + 2)
     mirrors, natives, wires_l, pis, pubs, blinds = [], [], [], [], [], []
     for _ in range(3):
-        sel_p, sig_p, k, wires, pi, kw = _general_instance(mj, pc, c, log_n, ultra, rng)
+        sel_p, sig_p, k, wires, pi, kw = _general_instance(mj, pc, c, log_n, ultra, rng, gates)
         mirrors.append(MP.TurboPlonkProver(c, n, sel_p, sig_p, k, ck, **kw))
         natives.append(N.NativeProver(c, n, sel_p, sig_p, k, ck, **kw))
         wires_l.append(wires); pis.append(fr_mont_limbs(c, pi)); pubs.append(pi[:4])
@@ -270,6 +295,11 @@ def test_batch_prove_over_native_handles_matches_the_mirror(gpu, mj, pyref, curv
     got = N.batch_prove(natives, wires_l, pubs, blinds, quot_blind, extra_transcript_init_msg=b"batch")
     assert got.challenges == want.challenges
     assert mj.batch.serialize_batch_proof(c, got) == mj.batch.serialize_batch_proof(c, want)
+    vks = [verifying_key(mj, pc, p, len(pub)) for p, pub in zip(natives, pubs)]
+    blob = mj.batch.serialize_batch_proof(c, got)
+    fresh = lambda: FS.StandardTranscript(pc, b"PlonkProof")
+    assert V.verify_batch_proof(pc, fresh(), vks, pubs, blob, pyref.g1_gen(pc), srs_beta, extra_msg=b"batch")
+    assert not V.verify_batch_proof(pc, fresh(), vks[1:] + vks[:1], pubs, blob, pyref.g1_gen(pc), srs_beta, extra_msg=b"batch")
     # an aggregate of one instance is that instance's plain proof
     one = N.batch_prove(natives[:1], wires_l[:1], pubs[:1], blinds[:1], quot_blind)
     b0 = mj.prover.Blinders(blinds[0].wires, blinds[0].z, quot_blind, blinds[0].h, blinds[0].prod_lookup)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import build_circuit, build_ultra_circuit, fr_mont_limbs, verifying_key
+import general_cases as GC
 import pyref_fs as FS
 
 pytestmark = pytest.mark.gpu
@@ -62,20 +63,22 @@ def test_bench_circuit_proof_verifies(gpu, mj, pyref, curve_id, plonk_type, num_
     ck.release()
 
 
-@pytest.mark.parametrize("curve_id,ultra,log_n", [(0, False, 6), (1, False, 9), (1, True, 6), (0, True, 8)])
-def test_proof_with_public_input_and_copy_constraints_verifies(gpu, mj, pyref, curve_id, ultra, log_n):
-    """A circuit with a non-zero public input, copy constraints over all wires and (Ultra) key/range lookups."""
+@pytest.mark.parametrize("curve_id,ultra,log_n,gates", GC.with_gates(GC.VERIFIER))
+def test_proof_with_public_input_and_copy_constraints_verifies(gpu, mj, pyref, curve_id, ultra, log_n, gates):
+    """A circuit with a non-zero public input, copy constraints over all wires and (Ultra) key/range lookups; gates="all": every
+    selector column non-zero, so the verifier's linearisation commitment takes all thirteen gate terms from the proof's evaluations."""
     import pyref_verifier as V
     c, pc = mj.params.CURVES[curve_id], pyref.CURVES[curve_id]
     n, r = 1 << log_n, c.r
-    rng = random.Random(4100 + curve_id + 2 * ultra)
+    rng = random.Random(GC.verifier_seed(curve_id, ultra, log_n))
     W = 6 if ultra else 5
     plookup = None
     if ultra:
-        sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, rng)
+        sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, rng, gates=gates)
         plookup = tabs
     else:
-        sel, sig, k, w, pi = build_circuit(pc, log_n, rng)
+        sel, sig, k, w, pi = build_circuit(pc, log_n, rng, gates=gates)
+    assert all(GC.nonzero_selectors(sel)) == (gates == "all")
     dom = mj.Radix2EvaluationDomain(c, log_n)
     srs_beta = rng.randrange(1, r)
     ck = mj.UnivariateProverParam.gen_srs_for_testing(c, srs_beta, n + 2)

@@ -166,14 +166,15 @@ def main():
         c, pc = mj.params.CURVES[cid], P.CURVES[cid]
         n, W = 1 << log_n, 6 if ultra else 5
         crng = random.Random(rng.randrange(1 << 60))
-        desc = {"kind": "proof", "curve": cid, "ultra": ultra, "log_n": log_n}
+        gates = crng.choice(("hot", "all"))                  # "all": q_lc[2..3], q_hash[1..2] and q_ecc live as well
+        desc = {"kind": "proof", "curve": cid, "ultra": ultra, "log_n": log_n, "gates": gates}
         dom = mj.Radix2EvaluationDomain(c, log_n)
         kw = {}
         if ultra:
-            sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, crng)
+            sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, crng, gates=gates)
             kw = {"plookup": {name: dom.ifft(fr_mont_limbs(c, tabs[key])) for name, key in zip(mj.plonk.PLOOKUP_TABLE_POLYS, TABLES)}}
         else:
-            sel, sig, k, w, pi = build_circuit(pc, log_n, crng)
+            sel, sig, k, w, pi = build_circuit(pc, log_n, crng, gates=gates)
         sel_p, sig_p = [dom.ifft(fr_mont_limbs(c, s)) for s in sel], [dom.ifft(fr_mont_limbs(c, s)) for s in sig]
         wires = np.stack([fr_mont_limbs(c, col) for col in w])
         srs_beta = crng.randrange(1, c.r)
