@@ -21,13 +21,13 @@ namespace mzk {
 
 void set_error(const std::string& s);
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess) {                                                               \
-            ::mzk::set_error(std::string(#expr) + ": " + hipGetErrorString(_e));              \
-            return _e == hipErrorOutOfMemory ? MZK_ERR_OOM : MZK_ERR_HIP;                     \
-        }                                                                                     \
+// hipSuccess -> MZK_OK; anything else sets "<what>: <HIP's message>" and maps to MZK_ERR_OOM / MZK_ERR_HIP
+int32_t hip_status(hipError_t e, const char* what);
+
+#define HIP_TRY(expr)                                      \
+    do {                                                   \
+        int32_t _r = ::mzk::hip_status((expr), #expr);     \
+        if (_r != MZK_OK) return _r;                       \
     } while (0)
 
 #define MZK_TRY(expr)                \
@@ -51,6 +51,8 @@ struct Workspace {
     size_t h_collect_cap = 0;
     double heavy_frac = 0.125;          // msm.hip: share of the worst case the heavy buckets' level-1 sums are sized for (grows on overflow, with a re-run)
     hipEvent_t last_use = nullptr;
+    struct Named { const char* name; DevBuf Workspace::* buf; };
+    static const Named bufs[];          // every DevBuf above with its name (mzk.hip): what release(), bytes() and the MZK_WS_DEBUG print walk
     void release();
     size_t bytes();
 };
@@ -77,16 +79,20 @@ struct ProfScope {
 extern std::atomic<bool> g_msm_precompute;
 
 struct Srs {
-    int curve;
-    uint64_t n;
-    uint32_t* d_xy;   // n * 2 * fq words, boundary form (what mzk_srs_download returns)
-    uint32_t* d_int;  // internal reduced-radix table used by the MSM (29-bit limbs, R'-Montgomery form: ecx.cuh)
+    int curve = 0;
+    uint64_t n = 0;
+    uint32_t* d_xy = nullptr;   // n * 2 * fq words, boundary form (what mzk_srs_download returns)
+    uint32_t* d_int = nullptr;  // internal reduced-radix table used by the MSM (29-bit limbs, R'-Montgomery form: ecx.cuh)
     uint32_t* d_pre = nullptr;  // [W][n] precomputed multiples 2^(c*w) P_i (msm_pre.cuh), built on first large MSM
     int pre_c = 0;              // window bits of d_pre; -1 = do not build
     int pre_levels = 0;         // W: levels of d_pre
     double pre_build_ms = 0;    // wall time of the build (pre_next_level launches, synchronised)
+    void free();                // releases the three tables (errors ignored) and nulls them; called explicitly, never from a destructor
 };
+inline bool valid_curve(int curve) { return curve == MZK_CURVE_BLS12_381 || curve == MZK_CURVE_BN254; }
 inline int fq_words(int curve) { return curve == MZK_CURVE_BLS12_381 ? 12 : 8; }
+inline size_t srs_point_bytes(int curve) { return (size_t)2 * fq_words(curve) * 4; }                            // boundary form (d_xy)
+constexpr size_t srs_int_point_bytes(int curve) { return curve == MZK_CURVE_BLS12_381 ? 2 * 14 * 4 : 2 * 9 * 4; }  // internal form (d_int, d_pre): pinned to EcFx::AFF_WORDS in msm.hip
 
 // ---- device contexts ---------------------------------------------------------------------------------
 // One context per LOGICAL device: the HIP device it runs on, its lock, workspace, I/O slots, SRS registry; the NTT plan cache,

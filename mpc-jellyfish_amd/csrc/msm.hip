@@ -701,6 +701,8 @@ int32_t msm_batch_dispatch(const Srs& s, uint32_t n_polys, const uint32_t* const
     return msm_batch_dev<BnFr, EcFx<BnFqX>>(items.data(), (int)n_polys, is_mont, pre, table, aff_words, st);
 }
 
+static_assert(srs_int_point_bytes(MZK_CURVE_BLS12_381) == EcFx<BlsFqX>::AFF_WORDS * 4 && srs_int_point_bytes(MZK_CURVE_BN254) == EcFx<BnFqX>::AFF_WORDS * 4,
+              "srs_int_point_bytes (internal.hpp) is the size of an EcFx affine point");
 // builds the internal (reduced-radix) copy of a freshly registered SRS
 template <class X>
 static int32_t srs_build_internal_t(Srs& s, hipStream_t st) {

@@ -19,6 +19,11 @@ void set_error(const std::string& s) {
     std::lock_guard<std::mutex> g(g_last_error_lock);
     g_last_error_global = s;
 }
+int32_t hip_status(hipError_t e, const char* what) {
+    if (e == hipSuccess) return MZK_OK;
+    set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? MZK_ERR_OOM : MZK_ERR_HIP;
+}
 
 int32_t DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return MZK_OK;
@@ -34,8 +39,22 @@ void DevBuf::release() {
     p = nullptr;
     cap = 0;
 }
+#define WS_BUF(name) {#name, &Workspace::name}
+const Workspace::Named Workspace::bufs[] = {
+    WS_BUF(ntt_scratch), WS_BUF(scalars), WS_BUF(hist), WS_BUF(offs), WS_BUF(cursor), WS_BUF(sorted), WS_BUF(buckets), WS_BUF(collect),
+    WS_BUF(io), WS_BUF(misc), WS_BUF(digits), WS_BUF(long_desc), WS_BUF(long_parts), WS_BUF(plonk_polys), WS_BUF(plonk_out), WS_BUF(pre_cnt),
+    WS_BUF(pre_off), WS_BUF(pre_ce), WS_BUF(pre_cb), WS_BUF(poly_tmp), WS_BUF(split), WS_BUF(link_tmp), WS_BUF(occ)};
+#undef WS_BUF
+static_assert(sizeof(Workspace) == sizeof(Workspace::bufs) / sizeof(Workspace::bufs[0]) * sizeof(DevBuf) + sizeof(void*) + sizeof(size_t) + sizeof(double) + sizeof(hipEvent_t),
+              "a DevBuf of Workspace is missing from Workspace::bufs");
+void Srs::free() {
+    for (uint32_t** d : {&d_xy, &d_int, &d_pre}) {
+        if (*d) (void)hipFree(*d);
+        *d = nullptr;
+    }
+}
 void Workspace::release() {
-    for (DevBuf* b : {&ntt_scratch, &scalars, &hist, &offs, &cursor, &sorted, &buckets, &collect, &io, &misc, &digits, &long_desc, &long_parts, &plonk_polys, &plonk_out, &pre_cnt, &pre_off, &pre_ce, &pre_cb, &poly_tmp, &split, &link_tmp, &occ}) b->release();
+    for (const Named& b : bufs) (this->*b.buf).release();
     if (h_collect) (void)hipHostFree(h_collect);
     h_collect = nullptr;
     h_collect_cap = 0;
@@ -46,7 +65,7 @@ void Workspace::release() {
 
 size_t Workspace::bytes() {
     size_t b = 0;
-    for (DevBuf* d : {&ntt_scratch, &scalars, &hist, &offs, &cursor, &sorted, &buckets, &collect, &io, &misc, &digits, &long_desc, &long_parts, &plonk_polys, &plonk_out, &pre_cnt, &pre_off, &pre_ce, &pre_cb, &poly_tmp, &split, &link_tmp, &occ}) b += d->cap;
+    for (const Named& d : bufs) b += (this->*d.buf).cap;
     return b;
 }
 
@@ -124,6 +143,39 @@ struct CtxBind {
 #define ENTER_HANDLE(h) \
     BIND_HANDLE(h);     \
     std::lock_guard<std::mutex> lk(cx_->lock)
+
+Srs* srs_find(Ctx& cx, uint64_t handle) {
+    auto it = cx.srs.find(handle);
+    if (it == cx.srs.end()) { set_error("unknown SRS handle"); return nullptr; }
+    return &it->second;
+}
+// An SRS under construction.  Whatever it has allocated is freed on every return path until publish() hands it to the registry,
+// so a construction site is: validate, alloc(), fill s.d_xy (plain HIP_TRY / MZK_TRY in between), return publish().
+struct SrsBuilder {
+    Srs s{};
+    bool published = false;
+    ~SrsBuilder() { if (!published) s.free(); }
+    int32_t alloc(int curve, uint64_t n) {
+        s.curve = curve;
+        s.n = n;
+        const size_t bytes = (size_t)n * srs_point_bytes(curve);
+        HIP_TRY(hipMalloc((void**)&s.d_xy, bytes ? bytes : 4));
+        return MZK_OK;
+    }
+    size_t bytes() const { return (size_t)s.n * srs_point_bytes(s.curve); }
+    int32_t publish(Ctx& cx, uint64_t* out_handle, hipStream_t st) {
+        MZK_TRY(srs_build_internal(s, st));
+        *out_handle = handle_make(cx.logical, cx.next_handle++);
+        cx.srs[*out_handle] = s;
+        published = true;
+        return MZK_OK;
+    }
+};
+// a device buffer that lives for one call (freed directly: the context lock is held and is not recursive)
+struct DevScratch {
+    uint8_t* p = nullptr;
+    ~DevScratch() { if (p) (void)hipFree(p); }
+};
 
 // ---- host-pointer I/O slots ------------------------------------------------------------------------
 // The host-pointer entry points (mzk_ntt, mzk_ntt_batch, mzk_msm, mzk_msm_batch: what a shim that swaps only the two
@@ -262,7 +314,7 @@ int32_t mzk_shutdown(void) {
         CtxBind bind(&cx);
         std::lock_guard<std::mutex> lk2(cx.lock);
         (void)hipDeviceSynchronize();
-        for (auto& kv : cx.srs) { (void)hipFree(kv.second.d_xy); if (kv.second.d_int) (void)hipFree(kv.second.d_int); if (kv.second.d_pre) (void)hipFree(kv.second.d_pre); }
+        for (auto& kv : cx.srs) kv.second.free();
         cx.srs.clear();
         io_release_all(cx);
         ntt_release_plans();
@@ -307,93 +359,68 @@ const char* mzk_version(void) { return "libmi355zk 0.3 (gfx950)"; }
 // ---- SRS -----------------------------------------------------------------------------------------
 int32_t mzk_srs_register(int32_t curve_id, const uint64_t* xy_mont, uint64_t n_points, uint64_t* out_handle) {
     ENTER_CUR();
-    if ((curve_id != 0 && curve_id != 1) || !out_handle || (!xy_mont && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    Srs s{curve_id, n_points, nullptr, nullptr, nullptr, 0};
-    const size_t bytes = (size_t)n_points * 2 * fq_words(curve_id) * 4;
-    HIP_TRY(hipMalloc((void**)&s.d_xy, bytes ? bytes : 4));
-    if (bytes) HIP_TRY(hipMemcpy(s.d_xy, xy_mont, bytes, hipMemcpyHostToDevice));
-    MZK_TRY(srs_build_internal(s, nullptr));
-    *out_handle = handle_make(cx_->logical, cx_->next_handle++);
-    cx_->srs[*out_handle] = s;
-    return MZK_OK;
+    if (!valid_curve(curve_id) || !out_handle || (!xy_mont && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    SrsBuilder b;
+    MZK_TRY(b.alloc(curve_id, n_points));
+    if (n_points) HIP_TRY(hipMemcpy(b.s.d_xy, xy_mont, b.bytes(), hipMemcpyHostToDevice));
+    return b.publish(*cx_, out_handle, nullptr);
 }
 int32_t mzk_srs_register_dev(int32_t curve_id, const void* d_xy_mont, uint64_t n_points, uint64_t* out_handle, void* stream) {
     ENTER_CUR();
-    if ((curve_id != 0 && curve_id != 1) || !out_handle || (!d_xy_mont && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    Srs s{curve_id, n_points, nullptr, nullptr, nullptr, 0};
-    const size_t bytes = (size_t)n_points * 2 * fq_words(curve_id) * 4;
-    HIP_TRY(hipMalloc((void**)&s.d_xy, bytes ? bytes : 4));
-    if (bytes) {
-        HIP_TRY(hipMemcpyAsync(s.d_xy, d_xy_mont, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (!valid_curve(curve_id) || !out_handle || (!d_xy_mont && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    SrsBuilder b;
+    MZK_TRY(b.alloc(curve_id, n_points));
+    if (n_points) {
+        HIP_TRY(hipMemcpyAsync(b.s.d_xy, d_xy_mont, b.bytes(), hipMemcpyDeviceToDevice, (hipStream_t)stream));
         HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     }
-    MZK_TRY(srs_build_internal(s, (hipStream_t)stream));
-    *out_handle = handle_make(cx_->logical, cx_->next_handle++);
-    cx_->srs[*out_handle] = s;
-    return MZK_OK;
+    return b.publish(*cx_, out_handle, (hipStream_t)stream);
 }
 // ---- serialized SRS (srs_io.hip) ----
 namespace {
 // decode n records at d_bytes (device) into a new SRS of the current context; on any failure nothing stays allocated
 int32_t srs_register_decoded(int32_t curve_id, const uint8_t* d_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
                              uint64_t* out_bad_index, hipStream_t st) {
-    Srs s{curve_id, n_points, nullptr, nullptr, nullptr, 0};
-    HIP_TRY(hipMalloc((void**)&s.d_xy, n_points ? (size_t)n_points * 2 * fq_words(curve_id) * 4 : 4));
+    SrsBuilder b;
+    MZK_TRY(b.alloc(curve_id, n_points));
     uint64_t bad = ~0ull;
     int reason = -1;
     int32_t rc;
     {
         ProfScope ps("srs_load.decode", st);
-        rc = srs_decode_dispatch(curve_id, d_bytes, n_points, flags & MZK_SER_COMPRESSED, flags & MZK_SER_VALIDATE, s.d_xy, &bad, &reason, st);
+        rc = srs_decode_dispatch(curve_id, d_bytes, n_points, flags & MZK_SER_COMPRESSED, flags & MZK_SER_VALIDATE, b.s.d_xy, &bad, &reason, st);
     }
     if (out_bad_index) *out_bad_index = bad;
-    if (rc == MZK_OK && reason >= 0) {
+    MZK_TRY(rc);
+    if (reason >= 0) {
         set_error("point " + std::to_string(bad) + ": " + srs_bad_reason(reason));
-        rc = MZK_ERR_ENCODING;
+        return MZK_ERR_ENCODING;
     }
-    if (rc == MZK_OK) {
-        ProfScope ps("srs_load.table", st);
-        rc = srs_build_internal(s, st);
-    }
-    if (rc != MZK_OK) {
-        (void)hipFree(s.d_xy);
-        if (s.d_int) (void)hipFree(s.d_int);
-        return rc;
-    }
-    *out_handle = handle_make(cur().logical, cur().next_handle++);
-    cur().srs[*out_handle] = s;
-    return MZK_OK;
+    ProfScope ps("srs_load.table", st);
+    return b.publish(cur(), out_handle, st);
 }
 }  // namespace
 int32_t mzk_srs_register_serialized(int32_t curve_id, const uint8_t* point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
                                     uint64_t* out_bad_index) {
     ENTER_CUR();
-    if ((curve_id != 0 && curve_id != 1) || !out_handle || (!point_bytes && n_points) || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
+    if (!valid_curve(curve_id) || !out_handle || (!point_bytes && n_points) || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
     }
     // whole staging: one copy of the records, then one decode launch (the copy / decode split)
     const size_t bytes = (size_t)n_points * srs_record_bytes(curve_id, flags & MZK_SER_COMPRESSED);
-    uint8_t* d_bytes = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_bytes, bytes ? bytes : 4));
-    hipError_t e;
+    DevScratch d_bytes;
+    HIP_TRY(hipMalloc((void**)&d_bytes.p, bytes ? bytes : 4));
     {
         ProfScope ps("srs_load.copy", nullptr);
-        e = bytes ? hipMemcpy(d_bytes, point_bytes, bytes, hipMemcpyHostToDevice) : hipSuccess;
+        if (bytes) MZK_TRY(hip_status(hipMemcpy(d_bytes.p, point_bytes, bytes, hipMemcpyHostToDevice), "hipMemcpy of the SRS records"));
     }
-    if (e != hipSuccess) {
-        (void)hipFree(d_bytes);
-        set_error(std::string("hipMemcpy of the SRS records: ") + hipGetErrorString(e));
-        return MZK_ERR_HIP;
-    }
-    const int32_t rc = srs_register_decoded(curve_id, d_bytes, n_points, flags, out_handle, out_bad_index, nullptr);
-    (void)hipFree(d_bytes);
-    return rc;
+    return srs_register_decoded(curve_id, d_bytes.p, n_points, flags, out_handle, out_bad_index, nullptr);
 }
 int32_t mzk_srs_register_serialized_dev(int32_t curve_id, const void* d_point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
                                         uint64_t* out_bad_index, void* stream) {
     ENTER_CUR();
-    if ((curve_id != 0 && curve_id != 1) || !out_handle || (!d_point_bytes && n_points) || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
+    if (!valid_curve(curve_id) || !out_handle || (!d_point_bytes && n_points) || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
     }
@@ -401,150 +428,105 @@ int32_t mzk_srs_register_serialized_dev(int32_t curve_id, const void* d_point_by
 }
 int32_t mzk_srs_serialize(uint64_t handle, uint64_t first, uint64_t n_points, uint32_t flags, uint8_t* out_bytes) {
     ENTER_HANDLE(handle);
-    auto it = cx_->srs.find(handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    const Srs& s = it->second;
-    if (first > s.n || n_points > s.n - first || (flags & ~MZK_SER_COMPRESSED) || (!out_bytes && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    const Srs* s = srs_find(*cx_, handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    if (first > s->n || n_points > s->n - first || (flags & ~MZK_SER_COMPRESSED) || (!out_bytes && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     if (!n_points) return MZK_OK;
-    const size_t bytes = (size_t)n_points * srs_record_bytes(s.curve, flags & MZK_SER_COMPRESSED);
-    uint8_t* d_out = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_out, bytes));
+    const size_t bytes = (size_t)n_points * srs_record_bytes(s->curve, flags & MZK_SER_COMPRESSED);
+    DevScratch d_out;
+    HIP_TRY(hipMalloc((void**)&d_out.p, bytes));
     HIP_TRY(hipDeviceSynchronize());
-    int32_t rc;
     {
         ProfScope ps("srs_save.encode", nullptr);
-        rc = srs_encode_dispatch(s.curve, s.d_xy + first * 2 * fq_words(s.curve), n_points, flags & MZK_SER_COMPRESSED, d_out, nullptr);
+        MZK_TRY(srs_encode_dispatch(s->curve, s->d_xy + first * 2 * fq_words(s->curve), n_points, flags & MZK_SER_COMPRESSED, d_out.p, nullptr));
     }
-    hipError_t e = hipSuccess;
-    if (rc == MZK_OK) {
-        ProfScope ps("srs_save.copy", nullptr);
-        e = hipMemcpy(out_bytes, d_out, bytes, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_out);
-    if (rc == MZK_OK && e != hipSuccess) {
-        set_error(std::string("hipMemcpy of the SRS records: ") + hipGetErrorString(e));
-        rc = MZK_ERR_HIP;
-    }
-    return rc;
+    ProfScope ps("srs_save.copy", nullptr);
+    return hip_status(hipMemcpy(out_bytes, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy of the SRS records");
 }
 // a new SRS holding the points [first, first + n_points) of a registered one (on its device): a rank of a multi-GPU prover keeps only
 // the range it commits over -- 1 / G of the points and of the fixed-base table, whose window then follows the slice's size
 int32_t mzk_srs_slice(uint64_t handle, uint64_t first, uint64_t n_points, uint64_t* out_handle) {
     ENTER_HANDLE(handle);
-    auto it = cx_->srs.find(handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    if (!out_handle || first > it->second.n || n_points > it->second.n - first) { set_error("slice outside the SRS"); return MZK_ERR_INVALID_ARG; }   // (no u64 wrap)
-    const Srs& src = it->second;
-    Srs s{src.curve, n_points, nullptr, nullptr, nullptr, 0};
-    const size_t pt = (size_t)2 * fq_words(src.curve) * 4, bytes = (size_t)n_points * pt;
-    HIP_TRY(hipMalloc((void**)&s.d_xy, bytes ? bytes : 4));
-    int32_t rc = MZK_OK;
-    if (bytes && hipMemcpy(s.d_xy, reinterpret_cast<const uint8_t*>(src.d_xy) + first * pt, bytes, hipMemcpyDeviceToDevice) != hipSuccess) {
-        set_error("hipMemcpy of the SRS slice failed");
-        rc = MZK_ERR_HIP;
-    }
-    if (rc == MZK_OK) rc = srs_build_internal(s, nullptr);
-    if (rc != MZK_OK) {                                               // nothing of a failed slice stays allocated
-        (void)hipFree(s.d_xy);
-        if (s.d_int) (void)hipFree(s.d_int);
-        return rc;
-    }
-    *out_handle = handle_make(cx_->logical, cx_->next_handle++);
-    cx_->srs[*out_handle] = s;
-    return MZK_OK;
+    const Srs* src = srs_find(*cx_, handle);
+    if (!src) return MZK_ERR_BAD_HANDLE;
+    if (!out_handle || first > src->n || n_points > src->n - first) { set_error("slice outside the SRS"); return MZK_ERR_INVALID_ARG; }   // (no u64 wrap)
+    SrsBuilder b;
+    MZK_TRY(b.alloc(src->curve, n_points));
+    if (n_points)
+        MZK_TRY(hip_status(hipMemcpy(b.s.d_xy, reinterpret_cast<const uint8_t*>(src->d_xy) + first * srs_point_bytes(src->curve), b.bytes(), hipMemcpyDeviceToDevice),
+                           "hipMemcpy of the SRS slice"));
+    return b.publish(*cx_, out_handle, nullptr);
 }
 int32_t mzk_srs_release(uint64_t handle) {
     ENTER_HANDLE(handle);
-    auto it = cx_->srs.find(handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipFree(it->second.d_xy));
-    if (it->second.d_int) HIP_TRY(hipFree(it->second.d_int));
-    if (it->second.d_pre) HIP_TRY(hipFree(it->second.d_pre));
-    cx_->srs.erase(it);
-    return MZK_OK;
+    Srs* s = srs_find(*cx_, handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    const hipError_t e = hipDeviceSynchronize();                    // whatever it reports, the entry and its memory go: nothing is left half released
+    s->free();
+    cx_->srs.erase(handle);
+    return hip_status(e, "hipDeviceSynchronize()");
 }
 int32_t mzk_srs_generate_for_testing_g(int32_t curve_id, const uint64_t* beta_canonical, const uint64_t* g_xy_mont, uint64_t n_points, uint64_t* out_handle) {
     ENTER_CUR();
-    if ((curve_id != 0 && curve_id != 1) || !out_handle || !beta_canonical) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    Srs s{curve_id, n_points, nullptr, nullptr, nullptr, 0};
-    const size_t bytes = (size_t)n_points * 2 * fq_words(curve_id) * 4;
-    HIP_TRY(hipMalloc((void**)&s.d_xy, bytes ? bytes : 4));
-    int32_t rc = MZK_OK;
-    if (n_points) {
-        const uint32_t* beta = reinterpret_cast<const uint32_t*>(beta_canonical);
-        rc = srs_generate_dispatch(curve_id, beta, reinterpret_cast<const uint32_t*>(g_xy_mont), n_points, s.d_xy);
-    }
-    if (rc == MZK_OK) rc = srs_build_internal(s, nullptr);
-    if (rc != MZK_OK) { (void)hipFree(s.d_xy); return rc; }
-    *out_handle = handle_make(cx_->logical, cx_->next_handle++);
-    cx_->srs[*out_handle] = s;
-    return MZK_OK;
+    if (!valid_curve(curve_id) || !out_handle || !beta_canonical) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    SrsBuilder b;
+    MZK_TRY(b.alloc(curve_id, n_points));
+    if (n_points)
+        MZK_TRY(srs_generate_dispatch(curve_id, reinterpret_cast<const uint32_t*>(beta_canonical), reinterpret_cast<const uint32_t*>(g_xy_mont), n_points, b.s.d_xy));
+    return b.publish(*cx_, out_handle, nullptr);
 }
 int32_t mzk_srs_generate_lagrange_for_testing(int32_t curve_id, const uint64_t* beta_canonical, const uint64_t* g_xy_mont, uint32_t log_n, uint32_t n_extra,
                                               uint64_t* out_handle) {
     ENTER_CUR();
-    if ((curve_id != 0 && curve_id != 1) || !out_handle || !beta_canonical || log_n > 27 || n_extra > 16) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    const uint64_t n_points = (1ull << log_n) + n_extra;
-    Srs s{curve_id, n_points, nullptr, nullptr, nullptr, 0};
-    HIP_TRY(hipMalloc((void**)&s.d_xy, (size_t)n_points * 2 * fq_words(curve_id) * 4));
-    int32_t rc = srs_lagrange_generate_dispatch(curve_id, reinterpret_cast<const uint32_t*>(beta_canonical), reinterpret_cast<const uint32_t*>(g_xy_mont), (int)log_n,
-                                                n_extra, s.d_xy);
-    if (rc == MZK_OK) rc = srs_build_internal(s, nullptr);
-    if (rc != MZK_OK) { (void)hipFree(s.d_xy); return rc; }
-    *out_handle = handle_make(cx_->logical, cx_->next_handle++);
-    cx_->srs[*out_handle] = s;
-    return MZK_OK;
+    if (!valid_curve(curve_id) || !out_handle || !beta_canonical || log_n > 27 || n_extra > 16) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    SrsBuilder b;
+    MZK_TRY(b.alloc(curve_id, (1ull << log_n) + n_extra));
+    MZK_TRY(srs_lagrange_generate_dispatch(curve_id, reinterpret_cast<const uint32_t*>(beta_canonical), reinterpret_cast<const uint32_t*>(g_xy_mont), (int)log_n,
+                                           n_extra, b.s.d_xy));
+    return b.publish(*cx_, out_handle, nullptr);
 }
 int32_t mzk_srs_lagrange_from_srs(uint64_t srs_handle, uint32_t log_n, uint32_t n_extra, uint64_t* out_handle) {
     ENTER_HANDLE(srs_handle);
-    auto it = cx_->srs.find(srs_handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    const Srs src = it->second;
-    if (!out_handle || log_n > 27 || n_extra > 16 || (1ull << log_n) + n_extra > src.n) {
+    const Srs* src = srs_find(*cx_, srs_handle);
+    if (!src) return MZK_ERR_BAD_HANDLE;
+    if (!out_handle || log_n > 27 || n_extra > 16 || (1ull << log_n) + n_extra > src->n) {
         set_error("bad argument (the SRS must hold 2^log_n + n_extra points)");
         return MZK_ERR_INVALID_ARG;
     }
-    const uint64_t n_points = (1ull << log_n) + n_extra;
-    Srs s{src.curve, n_points, nullptr, nullptr, nullptr, 0};
-    HIP_TRY(hipMalloc((void**)&s.d_xy, (size_t)n_points * 2 * fq_words(src.curve) * 4));
-    int32_t rc = srs_lagrange_from_points_dispatch(src.curve, src.d_xy, (int)log_n, n_extra, s.d_xy);
-    if (rc == MZK_OK) rc = srs_build_internal(s, nullptr);
-    if (rc != MZK_OK) { (void)hipFree(s.d_xy); return rc; }
-    *out_handle = handle_make(cx_->logical, cx_->next_handle++);
-    cx_->srs[*out_handle] = s;
-    return MZK_OK;
+    SrsBuilder b;
+    MZK_TRY(b.alloc(src->curve, (1ull << log_n) + n_extra));
+    MZK_TRY(srs_lagrange_from_points_dispatch(src->curve, src->d_xy, (int)log_n, n_extra, b.s.d_xy));
+    return b.publish(*cx_, out_handle, nullptr);         // (inserting into the std::map leaves `src` valid)
 }
 int32_t mzk_srs_generate_for_testing(int32_t curve_id, const uint64_t* beta_canonical, uint64_t n_points, uint64_t* out_handle) {
     return mzk_srs_generate_for_testing_g(curve_id, beta_canonical, nullptr, n_points, out_handle);
 }
 int32_t mzk_srs_download(uint64_t handle, uint64_t first, uint64_t n_points, uint64_t* out_xy_mont) {
     ENTER_HANDLE(handle);
-    auto it = cx_->srs.find(handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    const Srs& s = it->second;
-    if (first > s.n || n_points > s.n - first) { set_error("range outside the SRS"); return MZK_ERR_INVALID_ARG; }
-    const size_t pw = (size_t)2 * fq_words(s.curve);
+    const Srs* s = srs_find(*cx_, handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    if (first > s->n || n_points > s->n - first) { set_error("range outside the SRS"); return MZK_ERR_INVALID_ARG; }
+    const size_t pt = srs_point_bytes(s->curve);
     HIP_TRY(hipDeviceSynchronize());
-    if (n_points) HIP_TRY(hipMemcpy(out_xy_mont, s.d_xy + first * pw, n_points * pw * 4, hipMemcpyDeviceToHost));
+    if (n_points) HIP_TRY(hipMemcpy(out_xy_mont, reinterpret_cast<const uint8_t*>(s->d_xy) + first * pt, n_points * pt, hipMemcpyDeviceToHost));
     return MZK_OK;
 }
 int32_t mzk_srs_len(uint64_t handle, uint64_t* out_n_points) {
     ENTER_HANDLE(handle);
-    auto it = cx_->srs.find(handle);
-    if (it == cx_->srs.end() || !out_n_points) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    *out_n_points = it->second.n;
+    if (!out_n_points) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    const Srs* s = srs_find(*cx_, handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    *out_n_points = s->n;
     return MZK_OK;
 }
 // HBM a registered SRS holds: its points (boundary form + the MSM's internal reduced-radix form) and its fixed-base table
 int32_t mzk_srs_hbm_bytes(uint64_t handle, uint64_t* out_points_bytes, uint64_t* out_table_bytes) {
     ENTER_HANDLE(handle);
-    auto it = cx_->srs.find(handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    const Srs& s = it->second;
-    const uint64_t aff_int = s.curve == MZK_CURVE_BLS12_381 ? 2 * 14 * 4 : 2 * 9 * 4;       // 29-bit limbs: ecx.cuh
-    if (out_points_bytes) *out_points_bytes = s.n * (uint64_t)(2 * fq_words(s.curve) * 4) + (s.d_int ? s.n * aff_int : 0);
-    if (out_table_bytes) *out_table_bytes = s.d_pre ? (uint64_t)s.pre_levels * s.n * aff_int : 0;
+    const Srs* s = srs_find(*cx_, handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    const uint64_t aff_int = srs_int_point_bytes(s->curve);
+    if (out_points_bytes) *out_points_bytes = s->n * srs_point_bytes(s->curve) + (s->d_int ? s->n * aff_int : 0);
+    if (out_table_bytes) *out_table_bytes = s->d_pre ? (uint64_t)s->pre_levels * s->n * aff_int : 0;
     return MZK_OK;
 }
 int32_t mzk_launch_count(uint64_t* out_launches) {
@@ -570,15 +552,8 @@ int32_t mzk_workspace_hbm_bytes(uint64_t* out_bytes) {
     for (auto& slot : cx_->io) b += slot.buf.cap;
     *out_bytes = b;
     if (std::getenv("MZK_WS_DEBUG")) {                                // one line per buffer of the grow-only scratch (tools/hbm_report.py)
-        Workspace& w = cx_->ws;
-        const char* names[] = {"ntt_scratch", "scalars", "hist", "offs", "cursor", "sorted", "buckets", "collect", "io", "misc", "digits", "long_desc", "long_parts",
-                               "plonk_polys", "plonk_out", "pre_cnt", "pre_off", "pre_ce", "pre_cb", "poly_tmp", "split", "link_tmp", "occ"};
-        int i = 0;
-        for (DevBuf* d : {&w.ntt_scratch, &w.scalars, &w.hist, &w.offs, &w.cursor, &w.sorted, &w.buckets, &w.collect, &w.io, &w.misc, &w.digits, &w.long_desc,
-                          &w.long_parts, &w.plonk_polys, &w.plonk_out, &w.pre_cnt, &w.pre_off, &w.pre_ce, &w.pre_cb, &w.poly_tmp, &w.split, &w.link_tmp, &w.occ}) {
-            if (d->cap) std::fprintf(stderr, "[mzk ws] %-12s %10.1f MB\n", names[i], d->cap / 1e6);
-            i++;
-        }
+        for (const Workspace::Named& d : Workspace::bufs)
+            if ((cx_->ws.*d.buf).cap) std::fprintf(stderr, "[mzk ws] %-12s %10.1f MB\n", d.name, (cx_->ws.*d.buf).cap / 1e6);
         for (auto& slot : cx_->io)
             if (slot.buf.cap) std::fprintf(stderr, "[mzk ws] io slot      %10.1f MB\n", slot.buf.cap / 1e6);
     }
@@ -589,10 +564,10 @@ int32_t mzk_workspace_hbm_bytes(uint64_t* out_bytes) {
 int32_t mzk_msm_dev(uint64_t srs_handle, uint64_t base_offset, const void* d_scalars, uint64_t n, int32_t scalars_are_mont,
                     uint64_t* out_xyz_mont, void* stream) {
     ENTER_HANDLE(srs_handle);
-    auto it = cx_->srs.find(srs_handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
+    const Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
     if (!out_xyz_mont || (!d_scalars && n)) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
-    return msm_dispatch(it->second, base_offset, reinterpret_cast<const uint32_t*>(d_scalars), n, scalars_are_mont != 0,
+    return msm_dispatch(*s, base_offset, reinterpret_cast<const uint32_t*>(d_scalars), n, scalars_are_mont != 0,
                         reinterpret_cast<uint32_t*>(out_xyz_mont), (hipStream_t)stream);
 }
 
@@ -602,9 +577,9 @@ static int32_t msm_host(uint64_t srs_handle, uint64_t base_offset, const uint64_
     if (!out || (!scalars && n)) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
     {   // nothing is read from `scalars` before the range has been checked against the SRS
         std::lock_guard<std::mutex> lk(cx_->lock);
-        auto it = cx_->srs.find(srs_handle);
-        if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-        if (base_offset > it->second.n || n > it->second.n - base_offset) {
+        const Srs* s = srs_find(*cx_, srs_handle);
+        if (!s) return MZK_ERR_BAD_HANDLE;
+        if (base_offset > s->n || n > s->n - base_offset) {
             set_error("MSM longer than the registered SRS (poly degree larger than allowed)");
             return MZK_ERR_INVALID_ARG;
         }
@@ -619,10 +594,10 @@ static int32_t msm_host(uint64_t srs_handle, uint64_t base_offset, const uint64_
         HIP_TRY(hipMemcpyAsync(io.buf.p, scalars, n * 32, hipMemcpyHostToDevice, io.st));
     }
     std::lock_guard<std::mutex> lk(cx_->lock);
-    auto it = cx_->srs.find(srs_handle);                                // released by another thread meanwhile?
-    if (it == cx_->srs.end()) { (void)hipStreamSynchronize(io.st); set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    if (out_curve) *out_curve = it->second.curve;
-    const int32_t rc = msm_dispatch(it->second, base_offset, io.buf.as<uint32_t>(), n, is_mont != 0, reinterpret_cast<uint32_t*>(out), io.st);
+    const Srs* s = srs_find(*cx_, srs_handle);                          // released by another thread meanwhile?
+    if (!s) { (void)hipStreamSynchronize(io.st); return MZK_ERR_BAD_HANDLE; }
+    if (out_curve) *out_curve = s->curve;
+    const int32_t rc = msm_dispatch(*s, base_offset, io.buf.as<uint32_t>(), n, is_mont != 0, reinterpret_cast<uint32_t*>(out), io.st);
     if (rc != MZK_OK) (void)hipStreamSynchronize(io.st);          // the slot's buffer must be idle before it is handed on
     return rc;
 }
@@ -634,10 +609,10 @@ int32_t mzk_msm(uint64_t srs_handle, uint64_t base_offset, const uint64_t* scala
 int32_t mzk_msm_batch_dev(uint64_t srs_handle, uint32_t n_polys, const void* const* d_scalars, const uint64_t* lens, const uint64_t* base_offsets,
                           int32_t scalars_are_mont, uint64_t* out_xyz_mont, void* stream) {
     ENTER_HANDLE(srs_handle);
-    auto it = cx_->srs.find(srs_handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
+    const Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
     if (n_polys && (!d_scalars || !lens || !out_xyz_mont)) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
-    return msm_batch_dispatch(it->second, n_polys, reinterpret_cast<const uint32_t* const*>(d_scalars), lens, base_offsets, scalars_are_mont != 0,
+    return msm_batch_dispatch(*s, n_polys, reinterpret_cast<const uint32_t* const*>(d_scalars), lens, base_offsets, scalars_are_mont != 0,
                               reinterpret_cast<uint32_t*>(out_xyz_mont), (hipStream_t)stream);
 }
 
@@ -653,11 +628,11 @@ int32_t mzk_msm_batch(uint64_t srs_handle, uint32_t n_polys, const uint64_t* con
     }
     {   // nothing is read from the scalar arrays before the ranges have been checked against the SRS
         std::lock_guard<std::mutex> lk(cx_->lock);
-        auto it = cx_->srs.find(srs_handle);
-        if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
+        const Srs* s = srs_find(*cx_, srs_handle);
+        if (!s) return MZK_ERR_BAD_HANDLE;
         for (uint32_t i = 0; i < n_polys; i++) {
             const uint64_t off = base_offsets ? base_offsets[i] : 0;
-            if (off > it->second.n || lens[i] > it->second.n - off) {
+            if (off > s->n || lens[i] > s->n - off) {
                 set_error("MSM longer than the registered SRS (poly degree larger than allowed)");
                 return MZK_ERR_INVALID_ARG;
             }
@@ -677,9 +652,9 @@ int32_t mzk_msm_batch(uint64_t srs_handle, uint32_t n_polys, const uint64_t* con
         off += lens[i];
     }
     std::lock_guard<std::mutex> lk(cx_->lock);
-    auto it = cx_->srs.find(srs_handle);
-    if (it == cx_->srs.end()) { (void)hipStreamSynchronize(io.st); set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    const int32_t rc = msm_batch_dispatch(it->second, n_polys, dptr.data(), lens, base_offsets, scalars_are_mont != 0, reinterpret_cast<uint32_t*>(out_xyz_mont), io.st);
+    const Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) { (void)hipStreamSynchronize(io.st); return MZK_ERR_BAD_HANDLE; }
+    const int32_t rc = msm_batch_dispatch(*s, n_polys, dptr.data(), lens, base_offsets, scalars_are_mont != 0, reinterpret_cast<uint32_t*>(out_xyz_mont), io.st);
     if (rc != MZK_OK) (void)hipStreamSynchronize(io.st);
     return rc;
 }
@@ -694,15 +669,13 @@ int32_t mzk_msm_affine(uint64_t srs_handle, uint64_t base_offset, const uint64_t
 }
 
 int32_t mzk_g1_sum_jacobian(int32_t curve_id, const uint64_t* xyz_mont, uint64_t n, uint64_t* out_xyz_mont) {
-    if ((curve_id != 0 && curve_id != 1) || !out_xyz_mont || (!xyz_mont && n)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (!valid_curve(curve_id) || !out_xyz_mont || (!xyz_mont && n)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     jac_sum_host_dispatch(curve_id, xyz_mont, n, out_xyz_mont);
     return MZK_OK;
 }
 
 int32_t mzk_g1_jacobian_to_affine(int32_t curve_id, const uint64_t* xyz_mont, uint64_t n, uint64_t* out_xy_mont) {
-    if ((curve_id != 0 && curve_id != 1) || ((!xyz_mont || !out_xy_mont) && n)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    const int L = fq_words(curve_id) / 2;
-    (void)L;
+    if (!valid_curve(curve_id) || ((!xyz_mont || !out_xy_mont) && n)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     jac_to_affine_host_dispatch(curve_id, xyz_mont, n, out_xy_mont);
     return MZK_OK;
 }
@@ -739,25 +712,20 @@ int32_t mzk_ntt_batch(int32_t curve_id, uint32_t n_polys, uint64_t* const* data_
     }
     if (n_polys == 0) return MZK_OK;
     // (a failed HIP call must not hand a slot on while its stream still owns the buffer: every exit path drains the slots first)
-    auto hip_ok = [](hipError_t e, const char* what) -> int32_t {
-        if (e == hipSuccess) return MZK_OK;
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? MZK_ERR_OOM : MZK_ERR_HIP;
-    };
     int32_t rc = MZK_OK;
     for (uint32_t i = 0; i < n_polys && rc == MZK_OK; i++) {
         IoSlot& io = cx_->io[slot[i % n_slots].idx];
-        if (i >= (uint32_t)n_slots) rc = hip_ok(hipStreamSynchronize(io.st), "hipStreamSynchronize");   // its previous polynomial has left the device
+        if (i >= (uint32_t)n_slots) rc = hip_status(hipStreamSynchronize(io.st), "hipStreamSynchronize");   // its previous polynomial has left the device
         const uint64_t len = in_lens[i] < N ? in_lens[i] : N;
-        if (rc == MZK_OK && len) rc = hip_ok(hipMemcpyAsync(io.buf.p, data_mont[i], len * 32, hipMemcpyHostToDevice, io.st), "hipMemcpyAsync");
+        if (rc == MZK_OK && len) rc = hip_status(hipMemcpyAsync(io.buf.p, data_mont[i], len * 32, hipMemcpyHostToDevice, io.st), "hipMemcpyAsync");
         if (rc == MZK_OK) {
             std::lock_guard<std::mutex> lk(cx_->lock);
             rc = ntt_dispatch(curve_id, io.buf.as<uint32_t>(), len, (int)log_n, inverse != 0, reinterpret_cast<const uint32_t*>(coset_offset_mont), 1, N, io.st);
         }
-        if (rc == MZK_OK) rc = hip_ok(hipMemcpyAsync(data_mont[i], io.buf.p, N * 32, hipMemcpyDeviceToHost, io.st), "hipMemcpyAsync");
+        if (rc == MZK_OK) rc = hip_status(hipMemcpyAsync(data_mont[i], io.buf.p, N * 32, hipMemcpyDeviceToHost, io.st), "hipMemcpyAsync");
     }
     for (int k = 0; k < n_slots; k++) {
-        const int32_t r2 = hip_ok(hipStreamSynchronize(cx_->io[slot[k].idx].st), "hipStreamSynchronize");
+        const int32_t r2 = hip_status(hipStreamSynchronize(cx_->io[slot[k].idx].st), "hipStreamSynchronize");
         if (rc == MZK_OK) rc = r2;
     }
     return rc;
@@ -1244,12 +1212,12 @@ int32_t mzk_msm_set_precompute(int32_t on) {
 }
 int32_t mzk_srs_precompute(uint64_t srs_handle, uint32_t* out_window_bits, uint32_t* out_levels, uint64_t* out_table_bytes, double* out_build_ms) {
     ENTER_HANDLE(srs_handle);
-    auto it = cx_->srs.find(srs_handle);
-    if (it == cx_->srs.end()) { set_error("unknown SRS handle"); return MZK_ERR_BAD_HANDLE; }
-    Srs& s = it->second;
+    Srs* sp = srs_find(*cx_, srs_handle);
+    if (!sp) return MZK_ERR_BAD_HANDLE;
+    Srs& s = *sp;
     MZK_TRY(srs_build_pre(s, nullptr));
     const bool have = s.d_pre != nullptr && s.pre_c > 0;
-    const uint64_t aff_bytes = (s.curve == MZK_CURVE_BLS12_381 ? 28u : 18u) * 4u;       // EcFx::AFF_WORDS: 2 x 14 / 2 x 9 limbs of 29 bits
+    const uint64_t aff_bytes = srs_int_point_bytes(s.curve);
     if (out_window_bits) *out_window_bits = have ? (uint32_t)s.pre_c : 0u;
     if (out_levels) *out_levels = have ? (uint32_t)s.pre_levels : 0u;
     if (out_table_bytes) *out_table_bytes = have ? (uint64_t)s.pre_levels * s.n * aff_bytes : 0u;

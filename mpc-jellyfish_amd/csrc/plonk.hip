@@ -663,6 +663,10 @@ int32_t quotient_combine_run(int log_n, const uint32_t* classes, int ncl, const 
     return MZK_OK;
 }
 
+// frees a key's device buffers (called explicitly: a registry-held key has no freeing destructor)
+void pk_free(PlonkPk& pk) {
+    for (auto* d : pk.bufs()) if (d) (void)hipFree(d);
+}
 const PlonkPk* find_pk(uint64_t handle) {
     auto it = g_pks.find(handle);
     if (it == g_pks.end()) { set_error("unknown proving-key handle"); return nullptr; }
@@ -679,7 +683,7 @@ int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, cons
         for (uint32_t i = 0; ok && i < n_classes; i++) ok = classes[i] < PLK_RATIO && (i == 0 || classes[i] > classes[i - 1]);
         if (!ok) { set_error("chunked proving key: 1..8 strictly increasing residue classes < 8, fixed polynomials of degree < n"); return MZK_ERR_INVALID_ARG; }
     }
-    if ((curve != 0 && curve != 1) || W != (ultra ? PLK_MAX_WIRES : PLK_WIRES) || log_n < 1 || log_n + 3 > (curve == 0 ? 32 : 28) || log_n + 3 > 30 ||
+    if (!valid_curve(curve) || W != (ultra ? PLK_MAX_WIRES : PLK_WIRES) || log_n < 1 || log_n + 3 > (curve == 0 ? 32 : 28) || log_n + 3 > 30 ||
         poly_len == 0 || poly_len > (8ull << log_n) || !sel || !sig || !k_mont || !out_handle) {
         set_error("bad argument (TurboPlonk: 5 wire types, 13 selectors; UltraPlonk: 6 wire types, 14 selectors, 4 table polynomials)");
         return MZK_ERR_INVALID_ARG;
@@ -705,7 +709,7 @@ int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, cons
         rc = curve == 0 ? pk_build<BlsFr>(*pk, sel, sig, tab, poly_len) : pk_build<BnFr>(*pk, sel, sig, tab, poly_len);
     }
     if (rc != MZK_OK) {
-        for (auto* d : pk->bufs()) if (d) (void)hipFree(d);
+        pk_free(*pk);
         return rc;
     }
     *out_handle = handle_make(cur().logical, g_next_pk++);
@@ -717,7 +721,7 @@ int32_t plonk_pk_release(uint64_t handle) {
     auto it = g_pks.find(handle);
     if (it == g_pks.end()) { set_error("unknown proving-key handle"); return MZK_ERR_BAD_HANDLE; }
     HIP_TRY(hipDeviceSynchronize());
-    for (auto* d : it->second->bufs()) if (d) (void)hipFree(d);
+    pk_free(*it->second);
     g_pks.erase(it);
     return MZK_OK;
 }
@@ -733,8 +737,7 @@ uint64_t plonk_pk_bytes(uint64_t handle) {
     return b;
 }
 void plonk_release_all() {
-    for (auto& kv : g_pks)
-        for (auto* d : kv.second->bufs()) if (d) (void)hipFree(d);
+    for (auto& kv : g_pks) pk_free(*kv.second);
     g_pks.clear();
 }
 
@@ -804,7 +807,7 @@ int32_t plonk_quotient_top_dev(uint64_t handle, const uint32_t* d_polys, uint64_
 }
 int32_t plonk_quotient_combine_dev(int curve, int log_n, const uint32_t* classes, uint32_t n_classes, const uint32_t* d_r, const uint32_t* d_top, uint32_t n_top,
                                    uint32_t* d_out, hipStream_t st) {
-    if (curve != 0 && curve != 1) { set_error("unknown curve_id"); return MZK_ERR_INVALID_ARG; }
+    if (!valid_curve(curve)) { set_error("unknown curve_id"); return MZK_ERR_INVALID_ARG; }
     if (d_top && (n_top == 0 || n_top > PLK_TOP_MAX || n_top > (1ull << log_n) || (classes ? n_classes : 8u) >= PLK_RATIO)) {
         set_error("combine: 1..9 top coefficients above at most 7 classes");
         return MZK_ERR_INVALID_ARG;
