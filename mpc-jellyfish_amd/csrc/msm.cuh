@@ -7,7 +7,7 @@
 //   1. msm_digits    signed base-2^c digits of every scalar (16-bit, window-major)
 //   2. msm_sort<COUNT> / msm_scan / msm_sort<SCATTER>   counting sort of point indices by (window,
 //                    bucket); one workgroup per (2048-bucket range, window), LDS atomics only
-//   3. msm_order     buckets of each window ranked by load (equal-length loops within a wave)
+//   3. msm_order     buckets ranked by load, per window or over all windows (equal-length loops within a wave)
 //   4. msm_accumulate  one thread per (window,bucket): XYZZ += +-P (mixed add, all in VGPRs)
 //   5. msm_fold x log2(M)  in-place recursive halving: after level l the main array keeps
 //                    sum_i B_i folded to M/2^l entries and T_j (at offset M/2^j) the partial sums
@@ -167,8 +167,11 @@ __global__ __launch_bounds__(1024) void msm_scan_kernel(const uint32_t* __restri
     }
 }
 
-// order[w*M + rank] = bucket, buckets of a window listed by descending point count (counting sort on the
-// count, clamped to 1023), so the 64 lanes of an accumulation wave run loops of equal length.
+// order[rank] = w*M + bucket (the GLOBAL bucket index: the consumers derive the window from it), buckets listed by descending point
+// count (counting sort on the count, clamped to 1023), so the 64 lanes of an accumulation wave run loops of equal length.
+// Ranks are either per set (`global` false: the ranks [w*M, (w+1)*M) hold the buckets of window w, heaviest first) or ONE ranking of the
+// buckets of all sets (`global` true: the launch walks from the heaviest bucket of any window to the lightest of any window --
+// longest-processing-time-first for the whole launch).  Which of the two is the producers' business alone.
 // Three small kernels; a workgroup owns MSM_ORDER_SLICE consecutive buckets of one window.
 constexpr uint32_t MSM_ORDER_SLICE = 8192;
 __device__ __forceinline__ uint32_t order_key(uint32_t count) { return 1023u - min(count, 1023u); }
@@ -184,11 +187,13 @@ __global__ __launch_bounds__(1024) void msm_order_hist_kernel(const uint32_t* __
     __syncthreads();
     if (cnt[t]) atomicAdd(&keycnt[(size_t)w * 1024 + t], cnt[t]);
 }
-// keycnt[w][key] -> exclusive start of that key in the window's order array (in place)
-__global__ __launch_bounds__(1024) void msm_order_scan_kernel(uint32_t* __restrict__ keycnt) {
+// keycnt[w][key] -> exclusive start of that key in the window's order array (in place).  global_sets > 0 (one workgroup): the starts of
+// the keys in ONE ranking of all `global_sets` sets -- the scan of the sets' summed counts -- into row 0
+__global__ __launch_bounds__(1024) void msm_order_scan_kernel(uint32_t* __restrict__ keycnt, uint32_t global_sets) {
     __shared__ uint32_t part[1024];
     const uint32_t w = blockIdx.x, t = threadIdx.x;
-    const uint32_t mine = keycnt[(size_t)w * 1024 + t];
+    uint32_t mine = keycnt[(size_t)w * 1024 + t];
+    for (uint32_t s = 1; s < global_sets; s++) mine += keycnt[(size_t)s * 1024 + t];
     part[t] = mine;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) {
@@ -199,11 +204,12 @@ __global__ __launch_bounds__(1024) void msm_order_scan_kernel(uint32_t* __restri
     }
     keycnt[(size_t)w * 1024 + t] = part[t] - mine;
 }
-// each slice reserves, per key, a range of the window's order array and fills it
+// each slice reserves, per key, a range of the window's order array (global: of the one order array, from the cursors of row 0) and fills it
 __global__ __launch_bounds__(1024) void msm_order_scatter_kernel(const uint32_t* __restrict__ hist, uint32_t M, uint32_t* __restrict__ keycur,
-                                                                 uint32_t* __restrict__ order) {
+                                                                 uint32_t* __restrict__ order, bool global) {
     __shared__ uint32_t cnt[1024];
     const uint32_t w = blockIdx.y, t = threadIdx.x;
+    const uint32_t row = global ? 0u : w;
     const uint32_t lo = blockIdx.x * MSM_ORDER_SLICE, hi = min(M, lo + MSM_ORDER_SLICE);
     cnt[t] = 0;
     __syncthreads();
@@ -211,11 +217,11 @@ __global__ __launch_bounds__(1024) void msm_order_scatter_kernel(const uint32_t*
     __syncthreads();
     const uint32_t mine = cnt[t];
     __syncthreads();
-    cnt[t] = mine ? atomicAdd(&keycur[(size_t)w * 1024 + t], mine) : 0u;      // start of this slice's range for key t
+    cnt[t] = mine ? atomicAdd(&keycur[(size_t)row * 1024 + t], mine) : 0u;      // start of this slice's range for key t
     __syncthreads();
     for (uint32_t b = lo + t; b < hi; b += 1024) {
         const uint32_t pos = atomicAdd(&cnt[order_key(hist[(size_t)w * M + b])], 1u);
-        order[(size_t)w * M + pos] = b;
+        order[(size_t)row * M + pos] = w * M + b;
     }
 }
 
@@ -223,6 +229,7 @@ __global__ __launch_bounds__(1024) void msm_order_scatter_kernel(const uint32_t*
 // the keys of their buckets into keycnt), every workgroup scans the 1024 key totals of its window for itself (what msm_order_scan did in a
 // launch of its own) and reserves its ranges from a zeroed cursor array -- and, visiting every bucket's count anyway, registers the
 // over-long and heavy ones (what msm_long_find_kernel did after the accumulation; NULL desc_count: not here).  Three launches fewer per MSM.
+// global: every workgroup sums the key totals of all sets (gridDim.y rows) before its scan and reserves from the ONE cursor row 0.
 struct LongDesc;
 struct HeavyRun;
 __device__ __forceinline__ void msm_long_register(uint32_t w, uint32_t b, uint32_t c, uint32_t offs_t, int n_win, uint32_t cap, uint32_t desc_cap,
@@ -231,12 +238,16 @@ __device__ __forceinline__ void msm_long_register(uint32_t w, uint32_t b, uint32
 __global__ __launch_bounds__(1024) void msm_order_place_kernel(const uint32_t* __restrict__ hist, const uint32_t* __restrict__ offs, uint32_t M,
                                                                const uint32_t* __restrict__ keycnt, uint32_t* __restrict__ keycur, uint32_t* __restrict__ order,
                                                                int n_win, uint32_t cap, uint32_t desc_cap, LongDesc* __restrict__ desc,
-                                                               uint32_t* __restrict__ desc_count, uint32_t run_cap, uint32_t h1_cap, HeavyRun* __restrict__ heavy_runs) {
+                                                               uint32_t* __restrict__ desc_count, uint32_t run_cap, uint32_t h1_cap, HeavyRun* __restrict__ heavy_runs,
+                                                               bool global) {
     __shared__ uint32_t cnt[1024];
     __shared__ uint32_t part[1024];
     const uint32_t w = blockIdx.y, t = threadIdx.x;
+    const uint32_t row = global ? 0u : w;
     const uint32_t lo = blockIdx.x * MSM_ORDER_SLICE, hi = min(M, lo + MSM_ORDER_SLICE);
-    const uint32_t total = keycnt[(size_t)w * 1024 + t];
+    uint32_t total = 0;
+    if (global) for (uint32_t s = 0; s < gridDim.y; s++) total += keycnt[(size_t)s * 1024 + t];
+    else total = keycnt[(size_t)w * 1024 + t];
     part[t] = total;
     cnt[t] = 0;
     __syncthreads();
@@ -246,17 +257,17 @@ __global__ __launch_bounds__(1024) void msm_order_place_kernel(const uint32_t* _
         part[t] += v;
         __syncthreads();
     }
-    const uint32_t key_start = part[t] - total;                        // exclusive start of key t in the window's order array
+    const uint32_t key_start = part[t] - total;                        // exclusive start of key t in the window's (global: the one) order array
     for (uint32_t b = lo + t; b < hi; b += 1024) atomicAdd(&cnt[order_key(hist[(size_t)w * M + b])], 1u);
     __syncthreads();
     const uint32_t mine = cnt[t];
     __syncthreads();
-    cnt[t] = mine ? key_start + atomicAdd(&keycur[(size_t)w * 1024 + t], mine) : 0u;      // start of this slice's range for key t
+    cnt[t] = mine ? key_start + atomicAdd(&keycur[(size_t)row * 1024 + t], mine) : 0u;      // start of this slice's range for key t
     __syncthreads();
     for (uint32_t b = lo + t; b < hi; b += 1024) {
         const uint32_t c = hist[(size_t)w * M + b];
         const uint32_t pos = atomicAdd(&cnt[order_key(c)], 1u);
-        order[(size_t)w * M + pos] = b;
+        order[(size_t)row * M + pos] = w * M + b;
         if (desc_count && c > cap) msm_long_register(w, b, c, offs[(size_t)w * M + b], n_win, cap, desc_cap, desc, desc_count, run_cap, h1_cap, heavy_runs);
     }
 }
@@ -404,8 +415,8 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_accumulate_kernel(const u
         for (unsigned i = threadIdx.x; i < (unsigned)n_win * (1 + MSM_HEAVY_COUNTERS); i += MSM_ACC_THREADS) long_count[i] = 0u;      // NULL: the sort has cleared and filled them already
     const unsigned long long t0 = (unsigned long long)blockIdx.x * MSM_ACC_THREADS + threadIdx.x;
     if (t0 >= (unsigned long long)n_win * M) return;
-    const unsigned long long w = t0 / M;
-    const unsigned long long t = w * M + order[t0];            // lanes of a wave take buckets of equal load
+    const uint32_t tb = order[t0];                             // lanes of a wave take buckets of equal load
+    const unsigned long long t = tb, w = tb / M;               // (global bucket index: the window comes from the bucket, not from the rank)
     const uint32_t start = offs[t];
     // the rest of an over-long bucket: msm_long_* kernels; ALL of a heavy one: msm_heavy_* (a lone chain of `cap` additions would
     // outlast the whole launch)
@@ -428,12 +439,13 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_accumulate_kernel(const u
 // alone).  There every bucket is split over S = 2^log_split threads -- thread s takes entries s, s + S, ... of the run -- and
 // msm_split_combine_kernel adds the S partial sums as a tree: chains S times shorter for (S - 1) M extra additions, log_split deep.
 //
-// LARGE plain-path MSMs, round 5 (last session): only the TAIL is split.  The buckets of rank < rank0 (ranks are window-major, by descending
-// load within a window: `order`) take one thread each and write their bucket directly; the buckets of rank >= rank0 -- what the launch
-// dispatches last -- are split.  With several bucket sets the last ranks are a whole window, light buckets AND heavy ones: a launch of
-// whole-bucket threads ends with the chip draining for the length of its chains (2.65-2.77 ms at 2^20 pairs), halving EVERY bucket costs an
-// addition per bucket (2.35 + 0.13 ms), splitting the last eighth of the ranks four ways 2.36 + 0.07.  (One bucket set -- the table path --
-// is ranked as a whole, so its launch ends on its lightest buckets and gains nothing: not used there.)  rank0 = 0: every bucket is split.
+// LARGE plain-path MSMs, round 5: only the TAIL is split.  The buckets of rank < rank0 (`order`, by descending load) take one thread each
+// and write their bucket directly; the buckets of rank >= rank0 -- what the launch dispatches last -- are split.  With several bucket sets
+// ranked PER SET the last ranks are a whole window, light buckets AND heavy ones: a launch of whole-bucket threads ends with the chip
+// draining for the length of its chains (2.65-2.77 ms at 2^20 pairs), halving EVERY bucket costs an addition per bucket (2.35 + 0.13 ms),
+// splitting the last eighth of the ranks four ways 2.36 + 0.07.  Ranked over ALL sets (round 6) the tail is the lightest buckets of every
+// window, as it always was for one bucket set (the table path: its launch gains nothing from the split, not used there).
+// rank0 = 0: every bucket is split.
 // `sub` is laid out by RANK: the partial sums of the bucket of rank rank0 + r are sub[r S .. r S + S).
 // ONE_SET: one bucket set (the table path); it also gives the two paths' launches different names for the profiler.
 template <class EC, bool ONE_SET>
@@ -451,8 +463,8 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_accumulate_split_kernel(c
     const unsigned long long t0 = whole ? t1 : rank0 + (u >> log_split);
     if (t0 >= (unsigned long long)n_win * M) return;
     const uint32_t S = whole ? 1u : 1u << log_split, part = whole ? 0u : (uint32_t)(u & (S - 1));
-    const unsigned long long w = ONE_SET ? 0ull : t0 / M;
-    const unsigned long long t = w * M + order[t0];
+    const uint32_t tb = order[t0];
+    const unsigned long long t = tb, w = ONE_SET ? 0ull : tb / M;
     const uint32_t start = offs[t];
     const uint32_t h = hist[t];
     const uint32_t cnt = msm_is_heavy(h, cap) ? 0u : min(h, cap);
@@ -497,10 +509,10 @@ __device__ __forceinline__ typename EC::Pt pt_lds_get(const uint32_t* lds, int s
     }
     return p;
 }
-// (the bucket of tail rank r is the one of rank rank0 + r: window-major `order`, as in the accumulation)
+// (the bucket of tail rank r is the one of rank rank0 + r: `order`, as in the accumulation)
 template <class EC, bool ONE_SET>
 __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_split_combine_kernel(const uint32_t* __restrict__ sub, unsigned long long n_buckets, int log_split,
-                                                                             const uint32_t* __restrict__ order, uint32_t M, unsigned long long rank0,
+                                                                             const uint32_t* __restrict__ order, unsigned long long rank0,
                                                                              uint32_t* __restrict__ buckets, uint8_t* __restrict__ occ) {
     __shared__ uint32_t lds[MSM_ACC_THREADS * EC::PT_WORDS];
     const int tid = threadIdx.x;
@@ -523,7 +535,7 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_split_combine_kernel(cons
         if (mine) {
             acc = EC::add(a, b);
             if (lvl == log_split - 1) {
-                const unsigned long long t0 = rank0 + (base >> log_split) + tid, w = ONE_SET ? 0ull : t0 / M, t = w * M + order[t0];
+                const unsigned long long t = order[rank0 + (base >> log_split) + tid];
                 const bool empty = acc.is_inf();
                 occ[t] = empty ? 0 : 1;
                 if (!empty) EC::store_pt(buckets, t, acc);

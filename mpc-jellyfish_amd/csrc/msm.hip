@@ -242,6 +242,11 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
     // pairs, bit-identical.  MZK_MSM_LEGACY_LAUNCHES=1: the round-4 sequence (A/B).
     static const bool legacy_launches = std::getenv("MZK_MSM_LEGACY_LAUNCHES") != nullptr;
     const bool diet = (pre.c || sort2) && !legacy_launches;
+    // Round 6: several bucket sets are ranked by load as ONE list (msm.cuh, `order`): the launch walks from the heaviest bucket of any set
+    // to the lightest of any set instead of through the sets one after the other, each from its heaviest bucket to its lightest.
+    // MZK_MSM_RANK_PER_SET=1: ranks within each set, as until round 5 (A/B).  One set is one list either way.
+    static const bool rank_per_set = std::getenv("MZK_MSM_RANK_PER_SET") != nullptr;
+    const bool rank_global = sets > 1 && !rank_per_set;
     const size_t cnt_words = 2048 + (size_t)sets * 1024 * (diet ? 2 : 1);  // bin totals, bin cursors, order keys (diet: and their cursors)
     // the over-long buckets are registered inside the sort only when the sort may write this MSM's descriptors while the stream `st` still
     // works on the previous MSM of the batch: every MSM has a slot of its own (defer_heavy), or there is no second stream
@@ -400,18 +405,18 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
                 }
             }
             {
-                // buckets ranked by load within each bucket set
+                // buckets ranked by load: over all bucket sets at once (rank_global, below) or within each
                 ProfScope ps("msm_sort", sst);
                 uint32_t* keycnt = g_ws.pre_cnt.as<uint32_t>() + b * cnt_words + 2048;       // [sets][1024]
                 const unsigned slices = (M + MSM_ORDER_SLICE - 1) / MSM_ORDER_SLICE;
                 if (!pre.c && !sort2) HIP_TRY(hipMemsetAsync(keycnt, 0, (size_t)sets * 1024 * 4, sst));    // (two-level sort: zeroed with the bin totals above)
                 if (diet) {
                     hipLaunchKernelGGL(msm_order_place_kernel, dim3(slices, sets), dim3(1024), 0, sst, hist, offs, M, keycnt, keycnt + (size_t)sets * 1024, order,
-                                       sets, cap, desc_cap, desc, find_in_sort ? desc_count : nullptr, run_cap, h1_cap, heavy_runs);
+                                       sets, cap, desc_cap, desc, find_in_sort ? desc_count : nullptr, run_cap, h1_cap, heavy_runs, rank_global);
                 } else {
                     hipLaunchKernelGGL(msm_order_hist_kernel, dim3(slices, sets), dim3(1024), 0, sst, hist, M, keycnt);
-                    hipLaunchKernelGGL(msm_order_scan_kernel, dim3(sets), dim3(1024), 0, sst, keycnt);
-                    hipLaunchKernelGGL(msm_order_scatter_kernel, dim3(slices, sets), dim3(1024), 0, sst, hist, M, keycnt, order);
+                    hipLaunchKernelGGL(msm_order_scan_kernel, dim3(rank_global ? 1 : sets), dim3(1024), 0, sst, keycnt, rank_global ? (uint32_t)sets : 0u);
+                    hipLaunchKernelGGL(msm_order_scatter_kernel, dim3(slices, sets), dim3(1024), 0, sst, hist, M, keycnt, order, rank_global);
                 }
             }
             if (overlap) {
@@ -446,12 +451,17 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
                 // threads for all but the last 1/8 of the ranks, four threads per bucket there (msm.cuh, msm_accumulate_split_kernel).  Headline
                 // step, same box, alternating: 3.30-3.31 against 3.33-3.37 ms (profiles/r05_d_tail_split.txt).  The table path's ONE bucket set is
                 // ranked as a whole and ends on its lightest buckets: no gain there (measured), not used.  MZK_MSM_NO_TAIL_SPLIT=1: the rule alone
-                // (A/B); MZK_MSM_TAIL_FRAC_LOG / MZK_MSM_TAIL_SPLIT: tuning switches.
+                // (A/B); MZK_MSM_TAIL_FRAC_LOG / MZK_MSM_TAIL_SPLIT: tuning switches.  Round 6: with the ranks taken over ALL sets (rank_global)
+                // the last eighth is the lightest buckets of every window and the launch no longer needs the tail; it stays because the re-swept
+                // settings (1/8 ... 1/64, two or four ways; one repetition each) are not faster, and whole-bucket threads everywhere (MZK_MSM_FORCE_SPLIT=0), which
+                // are as fast or faster, would drop the combine launch that tests/test_msm_tail_split_gpu.py asserts
+                // (profiles/r06_global_rank_ab.txt).
                 static const bool no_tail = std::getenv("MZK_MSM_NO_TAIL_SPLIT") != nullptr;
+                static const bool force_tail = std::getenv("MZK_MSM_FORCE_TAIL") != nullptr;     // (tuning switch: the tail branch at ANY size with several sets -- the tests' way to rank0 > 0 below 2^20 pairs)
                 static const int tail_frac_log = std::getenv("MZK_MSM_TAIL_FRAC_LOG") ? std::atoi(std::getenv("MZK_MSM_TAIL_FRAC_LOG")) : 3;
                 static const int tail_split = std::getenv("MZK_MSM_TAIL_SPLIT") ? std::atoi(std::getenv("MZK_MSM_TAIL_SPLIT")) : 2;
                 unsigned long long rank0 = 0;
-                if (!few_rounds && sets > 1 && !no_tail && force_split < 0 && log_split == 1 && mean >= 8 && tail_frac_log >= 1 && tail_frac_log <= 6 && tail_split >= 1 && tail_split <= 3) {
+                if (sets > 1 && !no_tail && force_split < 0 && (force_tail || (!few_rounds && log_split == 1 && mean >= 8)) && tail_frac_log >= 1 && tail_frac_log <= 6 && tail_split >= 1 && tail_split <= 3) {
                     rank0 = (wm - (wm >> tail_frac_log)) & ~(unsigned long long)(MSM_ACC_THREADS - 1);
                     log_split = tail_split;
                 }
@@ -475,9 +485,9 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
                     }
                     ProfScope pc("msm_split_combine", st);
                     if (sets == 1)
-                        hipLaunchKernelGGL((msm_split_combine_kernel<EC, true>), cmb_grid, dim3(MSM_ACC_THREADS), 0, st, sub, (unsigned long long)n_split, log_split, order, M, rank0, buckets, occ);
+                        hipLaunchKernelGGL((msm_split_combine_kernel<EC, true>), cmb_grid, dim3(MSM_ACC_THREADS), 0, st, sub, (unsigned long long)n_split, log_split, order, rank0, buckets, occ);
                     else
-                        hipLaunchKernelGGL((msm_split_combine_kernel<EC, false>), cmb_grid, dim3(MSM_ACC_THREADS), 0, st, sub, (unsigned long long)n_split, log_split, order, M, rank0, buckets, occ);
+                        hipLaunchKernelGGL((msm_split_combine_kernel<EC, false>), cmb_grid, dim3(MSM_ACC_THREADS), 0, st, sub, (unsigned long long)n_split, log_split, order, rank0, buckets, occ);
                 }
             }
             {
