@@ -462,6 +462,46 @@ MZK_API int32_t mzk_prover_set_wire_variables(uint64_t prover, const uint32_t* w
  * wire, in wire order).  out_comms_xy: W affine points. */
 MZK_API int32_t mzk_prover_round1(uint64_t prover, int32_t witness_kind, const void* witness, uint64_t witness_len, const uint64_t* pub_input_rows,
                                   const uint64_t* pub_input_mont, uint64_t n_pub, const uint64_t* blinders_mont, uint64_t* out_comms_xy);
+/* Where a witness is wrong (the other half of what the reference's degree guard was used for; cf. "Unsatisfied witness" above):
+ * Circuit::check_circuit_satisfiability (relation/src/constraint_system.rs:389-451) for a caller that holds arrays only, with the
+ * witness where mzk_prover_round1 takes it -- all four witness kinds, the public input placed as round 1 places it.  Returns MZK_OK
+ * whether or not the witness satisfies the circuit: the report carries the answer.  All values in Fr; W = 5 or 6, w_j[i] the value
+ * on wire j of row i, selector order as for mzk_prover_create.
+ *   gate    row i < n fails iff  pi[i] + q_c + sum_{j<4} q_lc[j] w_j + q_mul[0] w_0 w_1 + q_mul[1] w_2 w_3 + sum_{j<4} q_hash[j] w_j^5
+ *           + q_ecc w_0 w_1 w_2 w_3 w_4 - q_o w_4 != 0  (check_gate, :695-738); pi[i] is zero off the public-input rows, so a wrong or
+ *           missing public input is a gate failure on its row.  gate_residual is that left-hand side on gate_row.
+ *   lookup  (UltraPlonk) the tau-free form of what the Plookup argument enforces: row i < n - 1 passes iff some row j < n has
+ *           (range[j], q tds[j], q key[j], q w_3[j], q w_4[j]) = (w_5[i], q' qds[i], q' w_0[i], q' w_1[i], q' w_2[i]),  q = q_lookup[j],
+ *           q' = q_lookup[i], tds / qds the table_dom_sep / q_dom_sep tables -- the coefficients in tau of merged_table_value /
+ *           merged_lookup_wire_value (:1441-1480): exactly the rows whose merged value round 1.5 finds in the merged table for every
+ *           tau.  Row n - 1 is not looked up (:1390-1398) and never fails.  On circuits built by the reference's gadgets this coincides
+ *           with check_range_gate (:602-618) plus the key / value check of :405-449.
+ *   copy    *_VECTOR kinds: the copy constraints hold by construction (copy_checked = 1, no failures).  *_WIRES kinds with a table from
+ *           mzk_prover_set_wire_variables: the representative of a variable is its cell of smallest index wire * n + row; a cell fails
+ *           iff its value differs from its representative's; copy_cell is the failing cell of smallest index.  *_WIRES kinds without a
+ *           table: copy_checked = 0 and `kind` is decided by the other two families (sigma is not decoded back to cells).
+ * Counts and locations are exact and deterministic.  MZK_ERR_INVALID_ARG: null report, wrong witness_len, a *_VECTOR kind without
+ * mzk_prover_set_wire_variables, a public-input row >= n.  MZK_ERR_UNSUPPORTED: copy check with W n >= 2^32.
+ * The call synchronises, needs no SRS and makes no collective call (with an mzk_comm any rank may call it alone).  Like a new
+ * mzk_prover_round1 it abandons a proof in flight on the handle: the next round call must be round 1 (MZK_ERR_STATE otherwise).  For
+ * MZK_WITNESS_DEV_WIRES the pointer is not kept.  Scratch is the context's shared scratch (selector values on H from 13 forward NTTs of
+ * the resident coefficient forms, hash slots): mzk_prover_hbm_bytes reports the same figures before and after. */
+#define MZK_CHECK_SATISFIED 0
+#define MZK_CHECK_GATE 1
+#define MZK_CHECK_LOOKUP 2
+#define MZK_CHECK_COPY 3
+typedef struct mzk_witness_report {
+    uint32_t kind;          /* 0, or the first failing family in the order gate, lookup, copy */
+    uint32_t copy_checked;  /* 1: copy constraints were checked (or hold by construction); 0: they could not be */
+    uint64_t gate_failures, gate_row;                  /* rows failing the gate identity; the lowest one (UINT64_MAX if none) */
+    uint64_t lookup_failures, lookup_row;              /* UltraPlonk; 0 / UINT64_MAX on TurboPlonk */
+    uint64_t copy_failures, copy_cell, copy_rep_cell;  /* cells as wire * n + row; UINT64_MAX if none */
+    uint64_t row_wires[6 * 4];                         /* the W wire values (Montgomery) of the row that `kind` reports; rest zero */
+    uint64_t gate_residual[4];                         /* kind == GATE: expected_gate_output - q_o * w_4 on gate_row (Montgomery) */
+} mzk_witness_report;
+MZK_API int32_t mzk_prover_check_witness(uint64_t prover, int32_t witness_kind, const void* witness, uint64_t witness_len,
+                                         const uint64_t* pub_input_rows, const uint64_t* pub_input_mont, uint64_t n_pub,
+                                         mzk_witness_report* out_report);
 /* UltraPlonk only.  blinders: 2 x 3 (h_1 then h_2); out: 2 points.  MZK_ERR_LOOKUP when a looked-up value is not in the table. */
 MZK_API int32_t mzk_prover_round1_5(uint64_t prover, const uint64_t* tau_mont, const uint64_t* blinders_mont, uint64_t* out_comms_xy);
 /* blinders: 3; out: 1 point. */

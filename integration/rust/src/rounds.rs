@@ -20,6 +20,35 @@ use crate::{check, mzk_srs_release, Mi355Error, SrsHandle};
 
 pub const MZK_WITNESS_HOST_VECTOR: i32 = 2;
 pub const MZK_ERR_WRONG_QUOTIENT_DEGREE: i32 = -9;
+pub const MZK_CHECK_SATISFIED: u32 = 0;
+pub const MZK_CHECK_GATE: u32 = 1;
+pub const MZK_CHECK_LOOKUP: u32 = 2;
+pub const MZK_CHECK_COPY: u32 = 3;
+
+/// `mzk_witness_report` (include/mzk.h): where a witness fails -- the first failing family in the order gate, lookup, copy, the number
+/// of failing gate rows / lookup rows / copy cells and the lowest of each (`u64::MAX` = none; cells as `wire * n + row`), the W wire
+/// values of the reported row and, for the gate family, the residual of the gate identity on it (Montgomery limbs).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct WitnessReport {
+    pub kind: u32,
+    pub copy_checked: u32,
+    pub gate_failures: u64,
+    pub gate_row: u64,
+    pub lookup_failures: u64,
+    pub lookup_row: u64,
+    pub copy_failures: u64,
+    pub copy_cell: u64,
+    pub copy_rep_cell: u64,
+    pub row_wires: [u64; 24],
+    pub gate_residual: [u64; 4],
+}
+
+impl WitnessReport {
+    pub fn satisfied(&self) -> bool {
+        self.kind == MZK_CHECK_SATISFIED
+    }
+}
 
 #[cfg_attr(feature = "link", link(name = "mi355zk"))]
 extern "C" {
@@ -31,6 +60,8 @@ extern "C" {
     pub fn mzk_prover_set_wire_variables(prover: u64, wire_variables: *const u32, n_vars: u64) -> i32;
     pub fn mzk_prover_round1(prover: u64, witness_kind: i32, witness: *const c_void, witness_len: u64, pub_input_rows: *const u64,
                              pub_input_mont: *const u64, n_pub: u64, blinders_mont: *const u64, out_comms_xy: *mut u64) -> i32;
+    pub fn mzk_prover_check_witness(prover: u64, witness_kind: i32, witness: *const c_void, witness_len: u64, pub_input_rows: *const u64,
+                                    pub_input_mont: *const u64, n_pub: u64, out_report: *mut WitnessReport) -> i32;
     pub fn mzk_prover_round1_5(prover: u64, tau: *const u64, blinders: *const u64, out_comms_xy: *mut u64) -> i32;
     pub fn mzk_prover_round2(prover: u64, beta: *const u64, gamma: *const u64, blinders: *const u64, out_comm_xy: *mut u64) -> i32;
     pub fn mzk_prover_round2_5(prover: u64, blinders: *const u64, out_comm_xy: *mut u64) -> i32;
@@ -92,6 +123,19 @@ impl Mi355Prover {
         let me = Self { handle, num_wire_types, ultra: tables.is_some(), fq_limbs, lagrange_key: lagrange };
         unsafe { check(mzk_prover_set_wire_variables(handle, wire_variables.as_ptr(), n_vars as u64))? };
         Ok(me)
+    }
+
+    /// `Circuit::check_circuit_satisfiability` (relation/src/constraint_system.rs:389-451) on the device, for the witness vector
+    /// `prove_rounds` hands to round 1 (`cs.witness_and_wire_variables().0`) and the public input on rows 0 .. : which gate row or
+    /// lookup row fails first and how many do.  Copy constraints hold by construction for a witness vector.  A proof in flight on
+    /// this prover is abandoned.
+    pub fn check_witness<F: PrimeField>(&self, witness: &[F], pub_input: &[F]) -> Result<WitnessReport, Mi355Error> {
+        let mut report = WitnessReport::default();
+        unsafe {
+            check(mzk_prover_check_witness(self.handle, MZK_WITNESS_HOST_VECTOR, witness.as_ptr() as *const c_void, witness.len() as u64,
+                                           core::ptr::null(), flat(pub_input), pub_input.len() as u64, &mut report))?;
+        }
+        Ok(report)
     }
 
     fn points<P: ark_ec::short_weierstrass::SWCurveConfig>(&self, xy: &[u64]) -> Vec<Affine<P>>

@@ -16,6 +16,9 @@
 
 // library-internal entry point (not in include/mzk.h, not exported): the calling thread's context hands a prover handle its stream
 extern "C" int32_t mzk_ctx_prover_stream(uint32_t k, void** out_stream);
+// ... and runs the witness check of a prover handle on its proving key (plonk.hip plonk_check_witness_dev), under the context's lock
+namespace mzk { struct WitnessCheckIn; }
+extern "C" int32_t mzk_ctx_check_witness(uint64_t pk_handle, const mzk::WitnessCheckIn* in, mzk_witness_report* out_report, void* stream);
 
 namespace mzk {
 
@@ -199,6 +202,18 @@ int32_t plookup_sorted_vec_dev(uint64_t handle, const uint32_t* d_wires, const u
                                hipStream_t st);
 int32_t plookup_product_dev(uint64_t handle, const uint32_t* d_table, const uint32_t* d_lookup, const uint32_t* d_sorted, const uint32_t* beta,
                             const uint32_t* gamma, uint32_t* d_out, hipStream_t st);
+// the witness check (check.cuh): the 13 selectors' coefficient forms (device, rows of n), the witness and the public input as
+// mzk_prover_round1 takes them, the wire-variable table (device, nullable) -- validated by the caller (prover_check.inc)
+struct WitnessCheckIn {
+    const uint32_t* d_sel_coeffs;
+    int kind;
+    const void* witness;
+    const uint32_t* d_vars;
+    uint64_t n_vars;
+    const uint64_t *pi_rows, *pi;
+    uint64_t n_pi;
+};
+int32_t plonk_check_witness_dev(uint64_t handle, const WitnessCheckIn& in, mzk_witness_report* out, hipStream_t st);
 int plonk_pk_is_ultra(uint64_t handle);
 int32_t plonk_perm_product_dev(uint64_t handle, const uint32_t* d_wires, const uint32_t* beta, const uint32_t* gamma, uint32_t* d_out, hipStream_t st);
 int plonk_pk_log_n(uint64_t handle);

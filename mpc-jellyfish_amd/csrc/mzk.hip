@@ -1097,6 +1097,10 @@ int32_t mzk_ctx_prover_stream(uint32_t k, void** out_stream) {
     *out_stream = st;
     return MZK_OK;
 }
+int32_t mzk_ctx_check_witness(uint64_t pk_handle, const WitnessCheckIn* in, mzk_witness_report* out_report, void* stream) {
+    ENTER_HANDLE(pk_handle);
+    return plonk_check_witness_dev(pk_handle, *in, out_report, (hipStream_t)stream);
+}
 int32_t mzk_stream_destroy(void* stream) {
     BIND_CUR();
     if (stream) HIP_TRY(hipStreamDestroy((hipStream_t)stream));

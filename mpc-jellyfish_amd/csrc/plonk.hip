@@ -7,6 +7,7 @@
 #include "internal.hpp"
 #include "plonk.cuh"
 #include "plookup.cuh"
+#include "check.cuh"
 
 namespace mzk {
 namespace {
@@ -663,6 +664,113 @@ int32_t quotient_combine_run(int log_n, const uint32_t* classes, int ncl, const 
     return MZK_OK;
 }
 
+// The three constraint families over one witness (check.cuh; include/mzk.h mzk_prover_check_witness).  Scratch: the context's shared
+// buffers (plonk_polys: selector values on H, wire values, public-input row, witness vector; io: result block, hash slots, representatives).
+// Synchronises: the report is read back.
+template <class P>
+int32_t witness_check_run(const PlonkPk& pk, const WitnessCheckIn& in, mzk_witness_report* out, hipStream_t st) {
+    const uint64_t n = 1ull << pk.log_n, cells = (uint64_t)pk.W * n;
+    const bool vec = in.kind == MZK_WITNESS_HOST_VECTOR || in.kind == MZK_WITNESS_DEV_VECTOR;
+    const bool copy = !vec && in.d_vars != nullptr;
+    if (copy && cells >= (1ull << 32)) { set_error("copy check: num_wire_types * domain size must be below 2^32"); return MZK_ERR_UNSUPPORTED; }
+    const bool own_wires = in.kind != MZK_WITNESS_DEV_WIRES;
+    bool pi_any = false;
+    for (uint64_t i = 0; i < in.n_pi * 4 && !pi_any; i++) pi_any = in.pi[i] != 0;
+    uint64_t slots = 0;
+    if (pk.ultra) for (slots = 4; slots < 4 * n;) slots <<= 1;
+    // the public input as round 1 places it: rows 0 .. n_pi - 1, or the given rows with a later entry replacing an earlier one of the same
+    // row (resolved here, so that the scatter below writes every row once); staged in this call's own memory, two copies whatever n_pi
+    std::vector<uint32_t> pi_at;
+    std::vector<uint64_t> pi_val;
+    if (pi_any && in.pi_rows) {
+        std::map<uint64_t, uint64_t> last;
+        for (uint64_t i = 0; i < in.n_pi; i++) last[in.pi_rows[i]] = i;
+        for (auto& kv : last) {
+            pi_at.push_back((uint32_t)kv.first);
+            pi_val.insert(pi_val.end(), in.pi + 4 * kv.second, in.pi + 4 * kv.second + 4);
+        }
+    }
+    ProfScope total("witness_check", st);
+    MZK_TRY(ws_acquire(st));
+    struct Release { hipStream_t st; ~Release() { (void)ws_release(st); } } release{st};      // on every return path: what is queued on st stays covered
+    const uint64_t wit_elems = in.kind == MZK_WITNESS_HOST_VECTOR ? in.n_vars : 0;
+    const uint64_t pi_stage = pi_at.size() + (pi_at.size() + 7) / 8;                        // values, then the rows (u32), in elements
+    MZK_TRY(g_ws.plonk_polys.reserve(((uint64_t)PLK_SELECTORS * n + (own_wires ? cells : 0) + (pi_any ? n : 0) + wit_elems + pi_stage) * 32));
+    MZK_TRY(g_ws.io.reserve((CHK_WORDS + slots + (copy ? in.n_vars : 0)) * 4));
+    uint32_t* d_sel = g_ws.plonk_polys.as<uint32_t>();
+    uint32_t* d_own = d_sel + (size_t)PLK_SELECTORS * n * 8;
+    uint32_t* d_pi = d_own + (own_wires ? cells * 8 : 0);
+    uint32_t* d_wit = d_pi + (pi_any ? n * 8 : 0);
+    uint32_t* d_res = g_ws.io.as<uint32_t>();
+    uint32_t* d_slots = d_res + CHK_WORDS;
+    uint32_t* d_rep = d_slots + slots;
+    // selector values on H
+    MZK_TRY(ntt_dispatch(pk.curve, d_sel, n, pk.log_n, false, nullptr, PLK_SELECTORS, n, st, 0, in.d_sel_coeffs, n));   // out of place: the resident rows are read, not copied
+    // wire values, as round 1 gets them
+    const uint32_t* d_wires = reinterpret_cast<const uint32_t*>(in.witness);
+    if (in.kind == MZK_WITNESS_HOST_WIRES) {
+        HIP_TRY(hipMemcpyAsync(d_own, in.witness, cells * 32, hipMemcpyHostToDevice, st));
+        d_wires = d_own;
+    } else if (vec) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(in.witness);
+        if (in.kind == MZK_WITNESS_HOST_VECTOR) {
+            HIP_TRY(hipMemcpyAsync(d_wit, in.witness, in.n_vars * 32, hipMemcpyHostToDevice, st));
+            src = d_wit;
+        }
+        MZK_TRY(wire_gather_dispatch(src, in.n_vars, in.d_vars, cells, d_own, st));
+        d_wires = d_own;
+    }
+    if (pi_any) {
+        HIP_TRY(hipMemsetAsync(d_pi, 0, n * 32, st));
+        if (!in.pi_rows) {
+            HIP_TRY(hipMemcpyAsync(d_pi, in.pi, in.n_pi * 32, hipMemcpyHostToDevice, st));
+        } else {
+            uint32_t* d_val = d_wit + wit_elems * 8;
+            uint32_t* d_at = d_val + pi_at.size() * 8;
+            HIP_TRY(hipMemcpyAsync(d_val, pi_val.data(), pi_at.size() * 32, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_at, pi_at.data(), pi_at.size() * 4, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(witness_pi_scatter_kernel, dim3((unsigned)((pi_at.size() + PLK_THREADS - 1) / PLK_THREADS)), dim3(PLK_THREADS), 0, st,
+                               reinterpret_cast<const uint4*>(d_val), d_at, (unsigned long long)pi_at.size(), reinterpret_cast<uint4*>(d_pi));
+        }
+    }
+    HIP_TRY(hipMemsetAsync(d_res, 0, CHK_WORDS * 4, st));
+    HIP_TRY(hipMemsetAsync(d_res + CHK_GATE_MIN, 0xFF, 4 * 4, st));
+    GateCheckArgs ga{d_sel, d_wires, pi_any ? d_pi : nullptr, d_res, n};
+    const unsigned gn = (unsigned)((n + PLK_THREADS - 1) / PLK_THREADS);
+    hipLaunchKernelGGL((witness_gate_check_kernel<P>), dim3(gn), dim3(PLK_THREADS), 0, st, ga);
+    if (pk.ultra) {
+        HIP_TRY(hipMemsetAsync(d_slots, 0xFF, slots * 4, st));
+        LookupCheckArgs la{d_wires, pk.d_tab_n, d_slots, d_res, n, (uint32_t)(slots - 1)};
+        hipLaunchKernelGGL((witness_lookup_insert_kernel<P>), dim3(gn), dim3(PLK_THREADS), 0, st, la);
+        hipLaunchKernelGGL((witness_lookup_probe_kernel<P>), dim3(gn), dim3(PLK_THREADS), 0, st, la);
+    }
+    if (copy) {
+        const unsigned gc = (unsigned)((cells + PLK_THREADS - 1) / PLK_THREADS);
+        HIP_TRY(hipMemsetAsync(d_rep, 0xFF, in.n_vars * 4, st));
+        hipLaunchKernelGGL(witness_copy_rep_kernel, dim3(gc), dim3(PLK_THREADS), 0, st, in.d_vars, cells, d_rep);
+        hipLaunchKernelGGL(witness_copy_check_kernel, dim3(gc), dim3(PLK_THREADS), 0, st, reinterpret_cast<const uint4*>(d_wires), in.d_vars, cells, d_rep,
+                           d_res);
+    }
+    hipLaunchKernelGGL((witness_report_kernel<P>), dim3(1), dim3(64), 0, st, ga, pk.W, copy ? in.d_vars : nullptr, copy ? d_rep : nullptr);
+    HIP_TRY(hipGetLastError());
+    uint32_t res[CHK_WORDS];
+    HIP_TRY(hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memset(out, 0, sizeof *out);
+    out->kind = res[CHK_KIND];
+    out->copy_checked = vec || copy ? 1 : 0;
+    out->gate_failures = res[CHK_GATE_CNT];
+    out->gate_row = res[CHK_GATE_CNT] ? res[CHK_GATE_MIN] : UINT64_MAX;
+    out->lookup_failures = res[CHK_LOOKUP_CNT];
+    out->lookup_row = res[CHK_LOOKUP_CNT] ? res[CHK_LOOKUP_MIN] : UINT64_MAX;
+    out->copy_failures = res[CHK_COPY_CNT];
+    out->copy_cell = res[CHK_COPY_CNT] ? res[CHK_COPY_MIN] : UINT64_MAX;
+    out->copy_rep_cell = res[CHK_COPY_CNT] ? res[CHK_COPY_REP] : UINT64_MAX;
+    std::memcpy(out->row_wires, res + CHK_ROW_WIRES, (size_t)pk.W * 32);
+    std::memcpy(out->gate_residual, res + CHK_RESIDUAL, 32);
+    return MZK_OK;
+}
+
 // frees a key's device buffers (called explicitly: a registry-held key has no freeing destructor)
 void pk_free(PlonkPk& pk) {
     for (auto* d : pk.bufs()) if (d) (void)hipFree(d);
@@ -777,6 +885,12 @@ int32_t plookup_product_dev(uint64_t handle, const uint32_t* d_table, const uint
     }
     return pk->curve == 0 ? lookup_product_run<BlsFr>(*pk, d_table, d_lookup, d_sorted, beta, gamma, d_out, st)
                           : lookup_product_run<BnFr>(*pk, d_table, d_lookup, d_sorted, beta, gamma, d_out, st);
+}
+int32_t plonk_check_witness_dev(uint64_t handle, const WitnessCheckIn& in, mzk_witness_report* out, hipStream_t st) {
+    const PlonkPk* pk = find_pk(handle);
+    if (!pk) return MZK_ERR_BAD_HANDLE;
+    if (!out || !in.d_sel_coeffs || !in.witness || (in.n_pi && !in.pi)) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    return pk->curve == 0 ? witness_check_run<BlsFr>(*pk, in, out, st) : witness_check_run<BnFr>(*pk, in, out, st);
 }
 int32_t plonk_quotient_chunked_dev(uint64_t handle, const uint32_t* d_polys, uint64_t in_stride, uint64_t in_len, uint32_t flags, const uint32_t* tau,
                                    const uint32_t* alpha, const uint32_t* beta, const uint32_t* gamma, uint32_t* d_out, hipStream_t st) {

@@ -98,6 +98,8 @@ struct ProverBase {
     virtual void set_wire_variables(const uint32_t* vars, uint64_t n_vars) = 0;
     virtual void round1(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
                         const uint64_t* blinders, uint64_t* out) = 0;
+    virtual void check_witness(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
+                               mzk_witness_report* out) = 0;
     virtual void round1_5(const uint64_t* tau, const uint64_t* blinders, uint64_t* out) = 0;
     virtual void round2(const uint64_t* beta, const uint64_t* gamma, const uint64_t* blinders, uint64_t* out) = 0;
     virtual void round2_5(const uint64_t* blinders, uint64_t* out) = 0;
@@ -261,6 +263,9 @@ struct ProverT final : ProverBase {
     void public_input_row(const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi);   // prover_round1.inc
     void round1(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
         const uint64_t* blinders, uint64_t* out) override;   // prover_round1.inc
+    // ---- the witness check (constraint_system.rs:389-451) ------------------------------------------------------------------------
+    void check_witness(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
+        mzk_witness_report* out) override;   // prover_check.inc
     // ---- round 1.5 (prover.rs:89-118), UltraPlonk only --------------------------------------------------------------------------
     void round1_5(const uint64_t* tau, const uint64_t* blinders, uint64_t* out) override;   // prover_round1.inc
     // ---- round 2 (prover.rs:125-141) -------------------------------------------------------------------------------------------
@@ -297,6 +302,7 @@ struct ProverT final : ProverBase {
 
 #include "prover_setup.inc"
 #include "prover_round1.inc"
+#include "prover_check.inc"
 #include "prover_round2.inc"
 #include "prover_round3.inc"
 #include "prover_round4.inc"
@@ -433,6 +439,11 @@ int32_t mzk_prover_round1(uint64_t prover, int32_t witness_kind, const void* wit
                           const uint64_t* pub_input_mont, uint64_t n_pub, const uint64_t* blinders_mont, uint64_t* out_comms_xy) {
     PROVER(prover);
     return guarded(*p_, [&] { p_->round1(witness_kind, witness, witness_len, pub_input_rows, pub_input_mont, n_pub, blinders_mont, out_comms_xy); });
+}
+int32_t mzk_prover_check_witness(uint64_t prover, int32_t witness_kind, const void* witness, uint64_t witness_len, const uint64_t* pub_input_rows,
+                                 const uint64_t* pub_input_mont, uint64_t n_pub, mzk_witness_report* out_report) {
+    PROVER(prover);
+    return guarded(*p_, [&] { p_->check_witness(witness_kind, witness, witness_len, pub_input_rows, pub_input_mont, n_pub, out_report); });
 }
 int32_t mzk_prover_round1_5(uint64_t prover, const uint64_t* tau_mont, const uint64_t* blinders_mont, uint64_t* out_comms_xy) {
     PROVER(prover);

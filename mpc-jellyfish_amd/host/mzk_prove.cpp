@@ -2,6 +2,9 @@
 // include/mzk.h, no Python, no HIP in this translation unit (g++ builds it).
 //   mzk_prove <curve: 0 BLS12-381 | 1 BN254> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree]
 //   mzk_prove <curve> file <circuit file> [reps] [--gpus G] [--host-witness] ...
+// --check-witness (turbo, ultra, file): mzk_prover_check_witness before proving; prints one line -- `witness: satisfied`, or
+// `witness: gate row R residual 0x..`, `witness: lookup row R`, `witness: copy cell (wire,row) != (wire,row)` -- followed by the numbers of
+// failing gate rows, lookup rows and copy cells, and exits with status 3 without proving when the witness is not satisfied (--gpus G: rank 0 checks).
 // --srs FILE (turbo, ultra, file): commit over the powers of a setup file -- CanonicalSerialize of UnivariateUniversalParams, compressed --
 // decoded and validated on every device, instead of the testing SRS [beta^i] G.  The trapdoor is still drawn (and discarded) from the rng,
 // so the blinders are those of a run without --srs.  A file with fewer than n + 3 powers is an error.
@@ -32,6 +35,7 @@ struct Options {
     bool check_agree = false;     // --check-agree: every rank's proof bytes are compared (tests)
     const char* srs_path = nullptr;  // --srs FILE: the commit key from a serialized setup
     bool slice_srs = true;        // --no-slice: with --gpus G every rank keeps the whole commit key (and its table) instead of its point range
+    bool check_witness = false;   // --check-witness: say where the witness fails before proving; exit status 3 if it does
     int lagrange = -1;            // round 1 commits the wires from their VALUES over the Lagrange-basis key derived from the SRS (same proof
                                   // bytes): -1 = from 2^18 gates on (below, the heavy-bucket paths of small scalars cost more than they save: 2^15 gates 3.93 against 3.73 ms) when a sample of the witness
                                   // shows small values (a dense witness gains nothing from the key), --lagrange = always,
@@ -60,6 +64,24 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     const bool lagrange = opt.lagrange < 0 ? (host.log_n >= 18 && host.witness_is_small()) : opt.lagrange != 0;
     sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr);                           // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
     const double preprocess_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (opt.check_witness) {
+        const mzk_witness_report rep = sp.check_witness();
+        const unsigned long long n = 1ull << host.log_n;
+        if (rep.kind == MZK_CHECK_SATISFIED) std::printf("witness: satisfied");
+        else if (rep.kind == MZK_CHECK_GATE) {
+            Fr res;
+            std::memcpy(res.l, rep.gate_residual, 32);
+            const auto v = canonical(res);
+            std::printf("witness: gate row %llu residual 0x%016llx%016llx%016llx%016llx", (unsigned long long)rep.gate_row, (unsigned long long)v[3],
+                        (unsigned long long)v[2], (unsigned long long)v[1], (unsigned long long)v[0]);
+        } else if (rep.kind == MZK_CHECK_LOOKUP) std::printf("witness: lookup row %llu", (unsigned long long)rep.lookup_row);
+        else std::printf("witness: copy cell (%llu,%llu) != (%llu,%llu)", (unsigned long long)(rep.copy_cell / n), (unsigned long long)(rep.copy_cell % n),
+                         (unsigned long long)(rep.copy_rep_cell / n), (unsigned long long)(rep.copy_rep_cell % n));
+        std::printf("; failing gate rows %llu, lookup rows %llu, copy cells %llu%s\n", (unsigned long long)rep.gate_failures, (unsigned long long)rep.lookup_failures,
+                    (unsigned long long)rep.copy_failures, rep.copy_checked ? "" : " (copy constraints not checked: no wire-variable table)");
+        std::fflush(stdout);
+        if (rep.kind != MZK_CHECK_SATISFIED) return 3;
+    }
     Proof<C> proof = sp.prove(rng, false, opt.check_agree);             // the proof whose bytes are printed (and warm-up)
     const std::vector<uint8_t> bytes = proof.serialize_compressed();
     double ms = 0, median_ms = 0, min_ms = 0, max_ms = 0;
@@ -178,6 +200,7 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--host-witness") opt.host_witness = 1;
         else if (a == "--host-witness-vars") opt.host_witness = 2;
         else if (a == "--check-agree") opt.check_agree = true;
+        else if (a == "--check-witness") opt.check_witness = true;
         else if (a == "--lagrange") opt.lagrange = 1;
         else if (a == "--no-lagrange") opt.lagrange = 0;
         else if (a == "--no-slice") opt.slice_srs = false;
@@ -187,7 +210,7 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     if (opt.gpus < 1 || opt.gpus > 16) { std::fprintf(stderr, "mzk_prove: --gpus 1..16\n"); return 2; }
-    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
     const int curve = std::atoi(argv[1]);
     if (std::string(argv[2]) == "link") {
         if (argc < 8) { std::fprintf(stderr, "usage: %s <curve 0|1> link <num_gates_1> <num_gates_2> <alignment> <offset> <size> [reps]\n", argv[0]); return 2; }

@@ -397,6 +397,18 @@ struct Prover {
               "mzk_prover_round1");
         wires_comms = points(out);
     }
+    // where the witness fails, without proving (mzk_prover_check_witness; Circuit::check_circuit_satisfiability, constraint_system.rs:389-451):
+    // the witness and the public input exactly as round 1 hands them over
+    mzk_witness_report check_witness(const BenchCircuit<C>& cs) {
+        const void* wit = cs.host_witness == 0 ? cs.wire_values.p : (cs.host_witness == 1 ? cs.host_wires.p : cs.host_vars.p);
+        const int32_t kind = cs.host_witness == 0 ? MZK_WITNESS_DEV_WIRES : (cs.host_witness == 1 ? MZK_WITNESS_HOST_WIRES : MZK_WITNESS_HOST_VECTOR);
+        const uint64_t len = cs.host_witness == 2 ? cs.n_vars : (uint64_t)W * n;
+        std::vector<uint64_t> pi = flat(cs.pub_input);
+        mzk_witness_report rep;
+        check(mzk_prover_check_witness(handle, kind, wit, len, cs.pub_rows.empty() ? nullptr : cs.pub_rows.data(), pi.data(), cs.pub_input.size(), &rep),
+              "mzk_prover_check_witness");
+        return rep;
+    }
     void round1_5(const Fr& tau, const Blinds& b) {                          // prover.rs:89-118
         h_comms.clear();
         if (!ultra) return;
@@ -686,6 +698,12 @@ struct ShardedProver {
             for (int r = 1; r < G; r++)
                 if (proofs[r].serialize_compressed() != proofs[0].serialize_compressed()) throw std::runtime_error("the ranks disagree on the proof");
         return std::move(proofs[0]);
+    }
+    // the witness check needs no collective: rank 0 runs it alone on its device
+    mzk_witness_report check_witness() {
+        mzk_witness_report rep{};
+        each([&](int r) { if (r == 0) rep = prover[0]->check_witness(*circuit[0]); });
+        return rep;
     }
     void sync() { each([&](int) { check(mzk_dev_sync(), "sync"); }); }
 };

@@ -19,6 +19,13 @@ def lib_path() -> str:
     return os.environ.get("MZK_LIB_PATH") or os.path.join(_HERE, "libmi355zk.so")      # (MZK_LIB_PATH: A/B builds of the library, tools/ only)
 
 
+class WitnessReport(C.Structure):
+    """mzk_witness_report (include/mzk.h)"""
+    _fields_ = [("kind", C.c_uint32), ("copy_checked", C.c_uint32), ("gate_failures", C.c_uint64), ("gate_row", C.c_uint64),
+                ("lookup_failures", C.c_uint64), ("lookup_row", C.c_uint64), ("copy_failures", C.c_uint64), ("copy_cell", C.c_uint64),
+                ("copy_rep_cell", C.c_uint64), ("row_wires", C.c_uint64 * 24), ("gate_residual", C.c_uint64 * 4)]
+
+
 _SIGS = {
     "mzk_init": [C.c_int32],
     "mzk_set_device": [C.c_int32],
@@ -117,6 +124,7 @@ _SIGS = {
     "mzk_prover_vk_commitments": [C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_prover_set_wire_variables": [C.c_uint64, C.c_void_p, C.c_uint64],
     "mzk_prover_round1": [C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    "mzk_prover_check_witness": [C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(WitnessReport)],
     "mzk_prover_round1_5": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_prover_round2": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_prover_round2_5": [C.c_uint64, C.c_void_p, C.c_void_p],

@@ -165,6 +165,31 @@ class ProofCore:
 
 WITNESS_DEV_WIRES, WITNESS_HOST_WIRES, WITNESS_HOST_VECTOR, WITNESS_DEV_VECTOR = 0, 1, 2, 3
 ERR_WRONG_QUOTIENT_DEGREE = -9
+ERR_LOOKUP = -8
+CHECK_SATISFIED, CHECK_GATE, CHECK_LOOKUP, CHECK_COPY = 0, 1, 2, 3
+CHECK_KINDS = ("satisfied", "gate", "lookup", "copy")
+_NONE = (1 << 64) - 1
+
+
+@dataclass
+class WitnessReport:
+    """mzk_witness_report (include/mzk.h) with integer field values: `kind` is one of CHECK_KINDS -- the first failing family in the
+    order gate, lookup, copy; rows and cells are None where nothing failed; cells are (wire, row) pairs."""
+    kind: str
+    copy_checked: bool
+    gate_failures: int
+    gate_row: int | None
+    lookup_failures: int
+    lookup_row: int | None
+    copy_failures: int
+    copy_cell: tuple | None
+    copy_rep_cell: tuple | None
+    row_wires: list          # the W wire values of the row `kind` reports ([] when satisfied)
+    gate_residual: int | None
+
+    @property
+    def satisfied(self) -> bool:
+        return self.kind == "satisfied"
 
 
 def _ptr(a):
@@ -310,6 +335,24 @@ class TurboPlonkProver:
         del keep
         return self._comms(out)
 
+    def check_witness(self, wire_values, pub_input) -> WitnessReport:
+        """mzk_prover_check_witness: where the witness fails (gate rows, lookup rows, copy cells), without proving.  Arguments as for
+        round1.  Abandons a proof in flight on this handle."""
+        L = _lib.load()
+        kind, wptr, wlen, keep = self._witness_args(wire_values)
+        rows, vals, n_pub = self._pub_args(pub_input)
+        rep = _lib.WitnessReport()
+        _check(L.mzk_prover_check_witness(self.handle, kind, wptr, wlen, _ptr(rows) if rows is not None else None, _ptr(vals) if n_pub else None, n_pub,
+                                          C.byref(rep)), "mzk_prover_check_witness")
+        del keep
+        opt = lambda v: None if v == _NONE else int(v)
+        cell = lambda v: None if v == _NONE else (int(v) // self.n, int(v) % self.n)
+        sat = rep.kind == CHECK_SATISFIED
+        wires = [] if sat else fr_from_mont(self.curve, np.array(rep.row_wires, dtype=np.uint64).reshape(6, 4)[:self.W])
+        resid = fr_from_mont(self.curve, np.array(rep.gate_residual, dtype=np.uint64).reshape(1, 4))[0] if rep.kind == CHECK_GATE else None
+        return WitnessReport(CHECK_KINDS[rep.kind], bool(rep.copy_checked), int(rep.gate_failures), opt(rep.gate_row), int(rep.lookup_failures),
+                             opt(rep.lookup_row), int(rep.copy_failures), cell(rep.copy_cell), cell(rep.copy_rep_cell), wires, resid)
+
     def round1_5(self, tau, blind_h):
         bl, t = self._mont([b for row in blind_h for b in row]), self._mont([tau])      # (named: the arrays must outlive the call)
         out = self._points(2)
@@ -352,10 +395,29 @@ class TurboPlonkProver:
         torch.cuda.synchronize()
         return t
 
-    def prove(self, wire_values, pub_input, ch, blind: Blinders, profile: bool = False, pi_zero: bool = False) -> ProofCore:
+    def prove(self, wire_values, pub_input, ch, blind: Blinders, profile: bool = False, pi_zero: bool = False, check: bool = False) -> ProofCore:
         """One instance: the calls of batch_prove_internal (snark.rs:263-431) with a challenge source (TranscriptChallenges /
         FixedChallenges).  pub_input: values for rows 0.., a (rows, values) pair, or the n-vector of evaluations; pi_zero is accepted for
-        the callers of the former Python sequencing and ignored (the library decides from the data)."""
+        the callers of the former Python sequencing and ignored (the library decides from the data).  check=True: when the proof fails
+        with WrongQuotientPolyDegree or a lookup error, check_witness runs on the same witness and its report travels on the raised
+        PlonkError as `e.report`.  NOTE the exception type of a lookup refusal: without `check` round 1.5's MZK_ERR_LOOKUP surfaces as
+        lib.MzkError (code -8), as it always has; with check=True it is re-raised as PlonkError(kind="CircuitError") -- the reference's
+        PlonkError::CircuitError(ParameterError), errors.rs:30 -- carrying `report` and `code`, chained to the MzkError (`__cause__`).
+        A caller that catches MzkError for this case must catch PlonkError as well when it passes check=True."""
+        if check:
+            try:
+                return self.prove(wire_values, pub_input, ch, blind, profile, pi_zero)
+            except (PlonkError, _lib.MzkError) as e:
+                lookup = isinstance(e, _lib.MzkError) and e.code == ERR_LOOKUP
+                if not lookup and getattr(e, "kind", None) != "WrongQuotientPolyDegree":
+                    raise
+                report = self.check_witness(wire_values, pub_input)
+                if lookup:
+                    err = PlonkError(str(e), kind="CircuitError")             # PlonkError::CircuitError(ParameterError), errors.rs:30
+                    err.report, err.code = report, e.code
+                    raise err from e
+                e.report = report
+                raise
         src = FixedChallenges(ch) if isinstance(ch, ProverChallenges) else ch
         L = _lib.load()
         _check(L.mzk_prover_profile(self.handle, 1 if profile else 0), "mzk_prover_profile")

@@ -14,6 +14,10 @@ lists.  What a case can be:
           against the test-side mirror's bytes, and the restated verifier must accept
   poly    evaluate / divide by X - z / linear combination of device-resident polynomials (rounds 4-5: mzk_poly_{eval,div_linear,lincomb}_dev),
           1 .. 2^17 coefficients, shorter logical lengths, points 0 / 1 / -1 / GENERATOR -- against the oracle's Horner, synthetic division, axpy
+  check   a random general circuit at 2^3 .. 2^11 gates with k = 0 .. 6 random cells overwritten (any wire, any row), the wire-variable
+          table derived from sigma now and then, host or device wires: the report of mzk_prover_check_witness -- first failing family,
+          the three counts, lowest rows / cells, the reported row's wires, the gate residual -- against the integer restatement of its
+          definitions (tests/check_witness_ref.py)
 The tests under tests/ pin the same paths on fixed seeds; this is the long-running version of them (profiles/r05_soak.json)."""
 import argparse
 import json
@@ -195,6 +199,48 @@ def main():
         ck.release()
         return desc, ok
 
+    def case_check(case):
+        import check_witness_ref as REF
+        cid = rng.randrange(2)
+        ultra = rng.random() < 0.5
+        log_n = rng.randrange(4 if ultra else 3, 12)
+        c, pc = mj.params.CURVES[cid], P.CURVES[cid]
+        n, W = 1 << log_n, 6 if ultra else 5
+        crng = random.Random(rng.randrange(1 << 60))
+        gates = crng.choice(("hot", "all"))
+        n_bad, with_vars, dev = crng.randrange(0, 7), crng.random() < 0.5, crng.random() < 0.5
+        desc = {"kind": "check", "curve": cid, "ultra": ultra, "log_n": log_n, "gates": gates, "corrupted": n_bad, "vars": with_vars, "dev": dev}
+        dom = mj.Radix2EvaluationDomain(c, log_n)
+        kw, tabs = {}, None
+        if ultra:
+            sel, sig, k, w, pi, tabs = build_ultra_circuit(pc, log_n, crng, gates=gates)
+            kw = {"plookup": {name: dom.ifft(fr_mont_limbs(c, tabs[key])) for name, key in zip(mj.plonk.PLOOKUP_TABLE_POLYS, TABLES)}}
+        else:
+            sel, sig, k, w, pi = build_circuit(pc, log_n, crng, gates=gates)
+        for _ in range(n_bad):
+            w[crng.randrange(W)][crng.choice([0, n - 1, crng.randrange(n)])] = crng.choice([0, 1, crng.randrange(c.r)])
+        ck = mj.UnivariateProverParam.gen_srs_for_testing(c, 77, n + 2)
+        native = mj.prover.TurboPlonkProver(c, n, [dom.ifft(fr_mont_limbs(c, s)) for s in sel], [dom.ifft(fr_mont_limbs(c, s)) for s in sig], k, ck, **kw)
+        wv = None
+        if with_vars:
+            wv, n_vars = REF.wire_variables_from_sigma(pc, sig, k, log_n)
+            native.set_wire_variables(np.array(wv, dtype=np.uint32), n_vars)
+        wires = np.stack([fr_mont_limbs(c, col) for col in w])
+        rep = native.check_witness(torch.from_numpy(wires.view(np.int64)).cuda() if dev else wires, pi[:4])
+        exp = REF.expected_report(pc, sel, w, pi, tabs, wv)
+        cell = lambda v: (v // n, v % n)
+        row = {"gate": exp["gate"][0][0] if exp["gate"] else None, "lookup": exp["lookup"][0] if exp["lookup"] else None,
+               "copy": exp["copy"][0][0] % n if exp["copy"] else None, "satisfied": None}[exp["kind"]]
+        want = (exp["kind"], wv is not None, len(exp["gate"]), exp["gate"][0][0] if exp["gate"] else None, len(exp["lookup"]),
+                exp["lookup"][0] if exp["lookup"] else None, len(exp["copy"] or []), cell(exp["copy"][0][0]) if exp["copy"] else None,
+                cell(exp["copy"][0][1]) if exp["copy"] else None, [w[j][row] for j in range(W)] if row is not None else [],
+                exp["gate"][0][1] if exp["gate"] else None)
+        got = (rep.kind, rep.copy_checked, rep.gate_failures, rep.gate_row, rep.lookup_failures, rep.lookup_row, rep.copy_failures, rep.copy_cell,
+               rep.copy_rep_cell, rep.row_wires, rep.gate_residual)
+        native.release()
+        ck.release()
+        return desc, got == want
+
     def case_poly(case):
         cid = rng.randrange(2)
         c = mj.params.CURVES[cid]
@@ -227,7 +273,7 @@ def main():
         got = mj.poly.lincomb(c, list(zip(sc, [dev(pl) for pl in polys])), out_len=out_len).cpu().numpy().view(np.uint64)
         return desc, bool(np.array_equal(got, cref.poly_lincomb(cid, polys, mj.params.fr_to_mont(c, sc), out_len)))
 
-    kinds = [("msm", case_msm, 5), ("batch", case_batch, 2), ("ntt", case_ntt, 4), ("proof", case_proof, 1), ("poly", case_poly, 3)]
+    kinds = [("msm", case_msm, 5), ("batch", case_batch, 2), ("ntt", case_ntt, 4), ("proof", case_proof, 1), ("poly", case_poly, 3), ("check", case_check, 2)]
     weights = [k[2] for k in kinds]
     counts = {k[0]: 0 for k in kinds}
     seconds = {k[0]: 0.0 for k in kinds}
