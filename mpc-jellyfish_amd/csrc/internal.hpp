@@ -127,10 +127,28 @@ struct Ctx {
     std::condition_variable io_cv;
 };
 Ctx& cur();                                       // the context the running entry point is bound to (thread-local)
-#define g_ws (::mzk::cur().ws)
-// a call on `st` must not start before the previous user of the context's shared workspace is done
-int32_t ws_acquire(hipStream_t st);
-int32_t ws_release(hipStream_t st);
+// The shared workspace exists only inside a WsHold: acquire() makes `st` wait for the previous user's work, and the destructor
+// records the event on `st` on EVERY return path, so what a failed call left queued stays covered.  Holds nest freely on one
+// stream (a dispatch inside a hold takes its own).  ws_acquire / ws_release (mzk.hip) are the hold's two HIP calls: nothing else calls them.
+int32_t ws_acquire(Workspace& ws, hipStream_t st);
+void ws_release(Workspace& ws, hipStream_t st);
+class WsHold {
+    Workspace* ws_ = nullptr;                     // set once acquired: the workspace of the context that was current then
+    hipStream_t st_ = nullptr;
+   public:
+    WsHold() = default;
+    WsHold(const WsHold&) = delete;               // (no move either: one hold, one scope, one record)
+    WsHold& operator=(const WsHold&) = delete;
+    ~WsHold() { if (ws_) ws_release(*ws_, st_); }
+    int32_t acquire(hipStream_t st) {
+        Ctx& cx = cur();
+        MZK_TRY(ws_acquire(cx.ws, st));
+        ws_ = &cx.ws, st_ = st;
+        return MZK_OK;
+    }
+    Workspace* operator->() const { return ws_; }
+    Workspace& operator*() const { return *ws_; }
+};
 inline uint64_t handle_make(int logical, uint64_t counter) { return ((uint64_t)(logical + 1) << 48) | counter; }
 inline int handle_ctx(uint64_t h) { return (int)(h >> 48) - 1; }
 

@@ -137,14 +137,14 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
     static const bool no_sort2 = std::getenv("MZK_MSM_PLAIN_SORT1") != nullptr;                   // (A/B switch)
     const bool sort2 = !pre.c && !no_sort2 && n_min >= (1ull << 16) && wm >= (1u << 14) && (wm >> PRE_FINE_LOG) <= 1024;
     const uint64_t sorted_max = pre.c ? n_max * n_dig : n_max;           // entries per bucket set
-    MZK_TRY(ws_acquire(st));
+    WsHold ws; MZK_TRY(ws.acquire(st));
     // (Tried in round 4 and dropped: batches of SMALL MSMs in "lanes", one stream per MSM with all of its kernels on it -- cross-stream
     // event waits and queue switches cost more than the latency chains they overlap: profiles/r04_small_msm_lanes_experiment.txt.)
     const bool overlap = passes > 1 && std::getenv("MZK_MSM_NO_OVERLAP") == nullptr;
     const size_t nb = overlap ? (size_t)std::min(passes, SORT_SETS) : 1;  // sets of sort buffers
-    MZK_TRY(g_ws.hist.reserve(nb * wm * 4));
-    MZK_TRY(g_ws.offs.reserve(nb * wm * 4));
-    MZK_TRY(g_ws.cursor.reserve(nb * wm * 4));                           // bucket order by load
+    MZK_TRY(ws->hist.reserve(nb * wm * 4));
+    MZK_TRY(ws->offs.reserve(nb * wm * 4));
+    MZK_TRY(ws->cursor.reserve(nb * wm * 4));                           // bucket order by load
     const uint32_t desc_cap_worst = (uint32_t)(sorted_max / MSM_MIN_CAP + 1);        // cap >= MSM_MIN_CAP below
     uint32_t desc_cap_max = desc_cap_worst;                                          // (optimistic with a slot per MSM, like h1_cap below)
     // heavy buckets (msm.cuh): per window <= entries / MSM_HEAVY_RUN full level-1 runs plus one partial run per heavy bucket
@@ -164,7 +164,7 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
     // kernels are deferred and run as ONE launch per level over all of them (msm.cuh, HeavyJobs): each MSM then needs its own
     // descriptors, counters and partial sums ("slot").
     bool defer_heavy = passes > 1 && (size_t)passes <= nb && passes <= MSM_HEAVY_JOBS;
-    const double heavy_frac = defer_heavy ? g_ws.heavy_frac : 1.0;        // (one shared slot: its counters are overwritten MSM after MSM -- worst case there)
+    const double heavy_frac = defer_heavy ? ws->heavy_frac : 1.0;        // (one shared slot: its counters are overwritten MSM after MSM -- worst case there)
     auto desc_cap_of = [](uint64_t entries, uint64_t cap_, double frac) {
         const uint64_t worst = entries / cap_ + 1;
         return (uint32_t)std::min<uint64_t>(worst, (uint64_t)((double)worst * frac) + 1024);
@@ -175,7 +175,7 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
     // ... while the slots fit: the scratch is sized for the worst case (every entry in heavy buckets: ~3.5 x the sorted list per slot,
     // 2.3 GB for five 2^20-pair MSMs) and scales with n.  A batch whose slots would need more than what is reserved already AND more than
     // a quarter of the free HBM (batches of 2^24 pairs and up) runs its heavy kernels per MSM out of one slot instead.
-    if (defer_heavy && (size_t)passes * parts_slot_words * 4 > g_ws.long_parts.cap) {
+    if (defer_heavy && (size_t)passes * parts_slot_words * 4 > ws->long_parts.cap) {
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         if ((size_t)passes * parts_slot_words * 4 > free_b / 4) {
@@ -188,13 +188,13 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
     }
     const double h1_frac = defer_heavy ? heavy_frac : 1.0;
     const size_t slots = defer_heavy ? (size_t)passes : 1;
-    MZK_TRY(g_ws.long_desc.reserve(slots * desc_slot_bytes));
-    MZK_TRY(g_ws.long_parts.reserve(slots * parts_slot_words * 4));
+    MZK_TRY(ws->long_desc.reserve(slots * desc_slot_bytes));
+    MZK_TRY(ws->long_parts.reserve(slots * parts_slot_words * 4));
     const unsigned long long dstride_max = (n_max + 7) & ~7ull;
     const size_t fused_k = fuse ? (size_t)count : 1;                      // MSMs per pass
     const size_t digits_bytes = fused_k * n_dig * dstride_max * ((pre.c || sort2) ? 4 : 2), sorted_words = (fused_k * n_dig * n_max + 3) & ~(size_t)3;
-    MZK_TRY(g_ws.digits.reserve(nb * digits_bytes));
-    MZK_TRY(g_ws.sorted.reserve(nb * sorted_words * 4));
+    MZK_TRY(ws->digits.reserve(nb * digits_bytes));
+    MZK_TRY(ws->sorted.reserve(nb * sorted_words * 4));
     // coarse bins of the table path: the low 2^top_bits buckets also receive the short top digit of every scalar, so they
     // are binned finer by the density ratio 1 + M / (2^top_bits (n_dig - 1)) (msm_pre.cuh PreBins)
     PreBins pb{0, PRE_FINE_LOG, 0, PRE_FINE_LOG};
@@ -251,27 +251,27 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
     // the over-long buckets are registered inside the sort only when the sort may write this MSM's descriptors while the stream `st` still
     // works on the previous MSM of the batch: every MSM has a slot of its own (defer_heavy), or there is no second stream
     const bool find_in_sort = diet && (!overlap || defer_heavy);
-    MZK_TRY(g_ws.pre_cnt.reserve(nb * cnt_words * 4));
+    MZK_TRY(ws->pre_cnt.reserve(nb * cnt_words * 4));
     if (pre.c || sort2) {
-        MZK_TRY(g_ws.pre_off.reserve(nb * 8192 * 4));                      // bin_start [n_bins + 1 <= 1025], then the huge-bin words (msm_pre.cuh)
-        MZK_TRY(g_ws.pre_ce.reserve(nb * sorted_words * 8));
+        MZK_TRY(ws->pre_off.reserve(nb * 8192 * 4));                      // bin_start [n_bins + 1 <= 1025], then the huge-bin words (msm_pre.cuh)
+        MZK_TRY(ws->pre_ce.reserve(nb * sorted_words * 8));
     }
-    MZK_TRY(g_ws.buckets.reserve((size_t)passes * wm * EC::PT_WORDS * 4));
-    MZK_TRY(g_ws.occ.reserve((size_t)passes * wm));                       // one byte per bucket slot: does it hold a point?
+    MZK_TRY(ws->buckets.reserve((size_t)passes * wm * EC::PT_WORDS * 4));
+    MZK_TRY(ws->occ.reserve((size_t)passes * wm));                       // one byte per bucket slot: does it hold a point?
     const int n_out_one = n_win * (log_m + 1);
     const int n_out = n_out_one * count;
     const size_t out_bytes = (size_t)n_out * 4 * FQ::N * 4;
     const size_t counts_words = (size_t)sets * (1 + MSM_HEAVY_COUNTERS), host_bytes = out_bytes + (size_t)passes * counts_words * 4;   // results, then every MSM's counters
-    MZK_TRY(g_ws.collect.reserve(out_bytes));
-    if (g_ws.h_collect_cap < host_bytes) {
-        if (g_ws.h_collect) HIP_TRY(hipHostFree(g_ws.h_collect));
-        g_ws.h_collect = nullptr;
-        HIP_TRY(hipHostMalloc(&g_ws.h_collect, host_bytes, hipHostMallocDefault));
-        g_ws.h_collect_cap = host_bytes;
+    MZK_TRY(ws->collect.reserve(out_bytes));
+    if (ws->h_collect_cap < host_bytes) {
+        if (ws->h_collect) HIP_TRY(hipHostFree(ws->h_collect));
+        ws->h_collect = nullptr;
+        HIP_TRY(hipHostMalloc(&ws->h_collect, host_bytes, hipHostMallocDefault));
+        ws->h_collect_cap = host_bytes;
     }
     std::vector<uint32_t> h1_caps(passes, 0), desc_caps(passes, 0);
     std::vector<const uint32_t*> count_ptrs(passes, nullptr);
-    uint32_t* collect = g_ws.collect.as<uint32_t>();
+    uint32_t* collect = ws->collect.as<uint32_t>();
     HeavyJobs jobs;
     std::memset(&jobs, 0, sizeof jobs);
     uint32_t heavy_run_cap_max = 0, long_desc_cap_max = 0;
@@ -289,15 +289,15 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
         for (int p = 0; p < passes; p++) {
             const size_t b = overlap ? (size_t)p % nb : 0;               // this MSM's set of sort buffers
             const hipStream_t sst = overlap ? ss.streams[p % n_sort_streams()] : st;      // the stream this MSM's sort runs on
-            uint32_t* hist = g_ws.hist.as<uint32_t>() + b * wm;
-            uint32_t* offs = g_ws.offs.as<uint32_t>() + b * wm;
-            uint32_t* order = g_ws.cursor.as<uint32_t>() + b * wm;
-            uint32_t* sorted = g_ws.sorted.as<uint32_t>() + b * sorted_words;
+            uint32_t* hist = ws->hist.as<uint32_t>() + b * wm;
+            uint32_t* offs = ws->offs.as<uint32_t>() + b * wm;
+            uint32_t* order = ws->cursor.as<uint32_t>() + b * wm;
+            uint32_t* sorted = ws->sorted.as<uint32_t>() + b * sorted_words;
             const uint64_t n = fuse ? n_max : items[p].n;                // fused: the longest MSM of the batch sizes grids and caps
             const uint32_t* d_scalars = items[p].d_scalars;
             const uint32_t* d_bases = items[p].d_bases;
-            uint32_t* buckets = g_ws.buckets.as<uint32_t>() + (size_t)p * wm * EC::PT_WORDS;
-            uint8_t* occ = g_ws.occ.as<uint8_t>() + (size_t)p * wm;
+            uint32_t* buckets = ws->buckets.as<uint32_t>() + (size_t)p * wm * EC::PT_WORDS;
+            uint8_t* occ = ws->occ.as<uint8_t>() + (size_t)p * wm;
             const uint64_t n_sorted = pre.c ? n * (uint64_t)n_dig : n;
             // per-thread cap on a bucket's run (a chain of dependent mixed adds, ~5 us each when a wave runs alone): the
             // expected peak load plus six standard deviations.  On the table path the short top digit (scalar bits above
@@ -324,8 +324,8 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
             const uint32_t desc_cap = std::min(desc_cap_max, desc_cap_of(n_sorted, cap, h1_frac));
             desc_caps[p] = desc_cap;
             const size_t slot = defer_heavy ? (size_t)p : 0;
-            LongDesc* desc = reinterpret_cast<LongDesc*>(g_ws.long_desc.as<char>() + slot * desc_slot_bytes);
-            uint32_t* parts = g_ws.long_parts.as<uint32_t>() + slot * parts_slot_words;
+            LongDesc* desc = reinterpret_cast<LongDesc*>(ws->long_desc.as<char>() + slot * desc_slot_bytes);
+            uint32_t* parts = ws->long_parts.as<uint32_t>() + slot * parts_slot_words;
             uint32_t* desc_count = reinterpret_cast<uint32_t*>(desc + (size_t)sets * desc_cap);        // `sets` words, then the heavy counters
             const uint32_t* heavy_count = desc_count + sets;
             const uint32_t run_cap = (uint32_t)(2 * (n_sorted / MSM_HEAVY_RUN) + 2);
@@ -342,17 +342,17 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
             const unsigned long long list_stride = (pre.c || sort2) ? 0ull : n;     // window w's entries start at sorted + w * list_stride (+ offs)
             if (!pre.c && !sort2) {
                 ProfScope ps("msm_sort", sst);
-                uint16_t* digits = reinterpret_cast<uint16_t*>(g_ws.digits.as<char>() + b * digits_bytes);
+                uint16_t* digits = reinterpret_cast<uint16_t*>(ws->digits.as<char>() + b * digits_bytes);
                 hipLaunchKernelGGL((msm_digits_kernel<FR>), dim3(gs), dim3(MSM_THREADS), 0, sst, d_scalars, n, is_mont, c, sets, digits, dstride);
                 hipLaunchKernelGGL((msm_sort_kernel<false>), dim3(n_ranges, sets), dim3(MSM_SORT_THREADS), 0, sst, digits, n, dstride, M, hist, offs, sorted);
                 hipLaunchKernelGGL(msm_scan_kernel, dim3(sets), dim3(1024), 0, sst, hist, offs, M);
                 hipLaunchKernelGGL((msm_sort_kernel<true>), dim3(n_ranges, sets), dim3(MSM_SORT_THREADS), 0, sst, digits, n, dstride, M, hist, offs, sorted);
             } else {
                 ProfScope ps("msm_sort", sst);
-                uint32_t* dig32 = reinterpret_cast<uint32_t*>(g_ws.digits.as<char>() + b * digits_bytes);
-                uint32_t* cnt = g_ws.pre_cnt.as<uint32_t>() + b * cnt_words;
-                uint32_t* coff = g_ws.pre_off.as<uint32_t>() + b * 8192;
-                unsigned long long* coarse = g_ws.pre_ce.as<unsigned long long>() + b * sorted_words;
+                uint32_t* dig32 = reinterpret_cast<uint32_t*>(ws->digits.as<char>() + b * digits_bytes);
+                uint32_t* cnt = ws->pre_cnt.as<uint32_t>() + b * cnt_words;
+                uint32_t* coff = ws->pre_off.as<uint32_t>() + b * 8192;
+                unsigned long long* coarse = ws->pre_ce.as<unsigned long long>() + b * sorted_words;
                 const uint32_t chunk = pre_chunk_of(n);
                 const uint32_t n_chunks = (uint32_t)((n + chunk - 1) / chunk);
                 uint32_t* bin_total = cnt;                       // [n_bins]
@@ -407,7 +407,7 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
             {
                 // buckets ranked by load: over all bucket sets at once (rank_global, below) or within each
                 ProfScope ps("msm_sort", sst);
-                uint32_t* keycnt = g_ws.pre_cnt.as<uint32_t>() + b * cnt_words + 2048;       // [sets][1024]
+                uint32_t* keycnt = ws->pre_cnt.as<uint32_t>() + b * cnt_words + 2048;       // [sets][1024]
                 const unsigned slices = (M + MSM_ORDER_SLICE - 1) / MSM_ORDER_SLICE;
                 if (!pre.c && !sort2) HIP_TRY(hipMemsetAsync(keycnt, 0, (size_t)sets * 1024 * 4, sst));    // (two-level sort: zeroed with the bin totals above)
                 if (diet) {
@@ -471,8 +471,8 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
                                        d_bases, list_stride, offs, hist, sorted, order, M, sets, cap, find_in_sort ? nullptr : desc_count, buckets, occ);
                 } else {
                     const size_t n_split = (size_t)(wm - rank0), split_threads = n_split << log_split, threads = (size_t)rank0 + split_threads;
-                    MZK_TRY(g_ws.split.reserve(split_threads * EC::PT_WORDS * 4));
-                    uint32_t* sub = g_ws.split.as<uint32_t>();
+                    MZK_TRY(ws->split.reserve(split_threads * EC::PT_WORDS * 4));
+                    uint32_t* sub = ws->split.as<uint32_t>();
                     const dim3 acc_grid((unsigned)((threads + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS)), cmb_grid((unsigned)((split_threads + 2 * MSM_ACC_THREADS - 1) / (2 * MSM_ACC_THREADS)));
                     {
                         ProfScope ps("msm_accumulate", st);               // the dominant launch alone: what rocprofv3 --stats averages
@@ -515,8 +515,8 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
         }
         {
             ProfScope ps("msm_reduce", st);
-            uint32_t* buckets = g_ws.buckets.as<uint32_t>();
-            uint8_t* occ = g_ws.occ.as<uint8_t>();
+            uint32_t* buckets = ws->buckets.as<uint32_t>();
+            uint8_t* occ = ws->occ.as<uint8_t>();
             const int nw_all = sets * passes;                   // every bucket set folds independently (= n_win * count)
             // wide levels: one launch each over all bucket sets; narrow levels (<= 256 adds per set): one launch in all
             int first_tail = 1;
@@ -557,16 +557,15 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
                 hipLaunchKernelGGL((msm_collect_kernel<EC>), dim3((n_out + 63) / 64), dim3(64), 0, st, buckets, occ, M, log_m, nw_all, collect);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(g_ws.h_collect, collect, out_bytes, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ws->h_collect, collect, out_bytes, hipMemcpyDeviceToHost, st));
         if (defer_heavy)                                             // what the heavy buckets of every MSM really needed (their slots keep the counters)
             for (int p = 0; p < passes; p++)
-                HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(g_ws.h_collect) + out_bytes + (size_t)p * counts_words * 4, count_ptrs[p], counts_words * 4,
+                HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(ws->h_collect) + out_bytes + (size_t)p * counts_words * 4, count_ptrs[p], counts_words * 4,
                                        hipMemcpyDeviceToHost, st));
     }
-    MZK_TRY(ws_release(st));
     HIP_TRY(hipStreamSynchronize(st));
     if (defer_heavy) {
-        const uint32_t* cw = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(g_ws.h_collect) + out_bytes);
+        const uint32_t* cw = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(ws->h_collect) + out_bytes);
         double grow = 0;
         for (int p = 0; p < passes; p++)
             for (int w = 0; w < sets; w++) {
@@ -576,11 +575,11 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
                 if (need_desc > desc_caps[p]) grow = std::max(grow, (double)need_desc / (double)desc_cap_worst);
             }
         if (grow > 0) {                                              // some heavy bucket found no room: its MSM's result is incomplete -- larger arrays, same group again
-            g_ws.heavy_frac = std::min(1.0, std::max(g_ws.heavy_frac * 2, grow * 1.25));
+            ws->heavy_frac = std::min(1.0, std::max(ws->heavy_frac * 2, grow * 1.25));
             return MSM_RETRY;
         }
     }
-    const uint32_t* h = reinterpret_cast<const uint32_t*>(g_ws.h_collect);
+    const uint32_t* h = reinterpret_cast<const uint32_t*>(ws->h_collect);
     const size_t per = (size_t)n_out_one * 4 * FQ::N;
     // a Horner tail is c doublings + c additions on one core, ~17 us on the table path (one bucket set): starting a thread costs more
     // than running it (measured: 5 tails on 5 fresh threads 130-250 us, in sequence 70 us) -- the tails of a group, and the bucket
@@ -737,10 +736,10 @@ namespace {
 template <class FR, class FQ>
 int32_t srs_generate(const uint32_t* beta_canon, const uint32_t* g_xy_mont, uint64_t n, uint32_t* d_out) {
     hipStream_t st = nullptr;
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.scalars.reserve((n ? n : 1) * 32));
-    MZK_TRY(g_ws.misc.reserve(32 + 256 * 4 * FQ::N * 4 + 256 * 2 * FQ::N * 4 + 2 * FQ::N * 4));
-    uint32_t* d_beta = g_ws.misc.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->scalars.reserve((n ? n : 1) * 32));
+    MZK_TRY(ws->misc.reserve(32 + 256 * 4 * FQ::N * 4 + 256 * 2 * FQ::N * 4 + 2 * FQ::N * 4));
+    uint32_t* d_beta = ws->misc.as<uint32_t>();
     uint32_t* d_tab_xyzz = d_beta + 8;
     uint32_t* d_tab = d_tab_xyzz + 256 * 4 * FQ::N;
     uint32_t* d_g = d_tab + 256 * 2 * FQ::N;
@@ -748,13 +747,12 @@ int32_t srs_generate(const uint32_t* beta_canon, const uint32_t* g_xy_mont, uint
     if (g_xy_mont) HIP_TRY(hipMemcpyAsync(d_g, g_xy_mont, 2 * FQ::N * 4, hipMemcpyHostToDevice, st));
     const unsigned long long chunks = (n + 63) / 64;
     hipLaunchKernelGGL((fr_powers_kernel<FR>), dim3((unsigned)((chunks + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st,
-                       d_beta, n, g_ws.scalars.as<uint32_t>());
+                       d_beta, n, ws->scalars.as<uint32_t>());
     hipLaunchKernelGGL((g1_pow2_table_kernel<FQ>), dim3(1), dim3(64), 0, st, d_tab_xyzz, g_xy_mont ? d_g : nullptr);
     hipLaunchKernelGGL((g1_table_to_affine_kernel<FQ>), dim3(4), dim3(64), 0, st, d_tab_xyzz, d_tab, 256);
     hipLaunchKernelGGL((g1_fixed_base_kernel<FQ>), dim3((unsigned)((n + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS)), dim3(MSM_ACC_THREADS), 0, st,
-                       d_tab, g_ws.scalars.as<uint32_t>(), n, d_out);
+                       d_tab, ws->scalars.as<uint32_t>(), n, d_out);
     HIP_TRY(hipGetLastError());
-    MZK_TRY(ws_release(st));
     HIP_TRY(hipStreamSynchronize(st));
     return MZK_OK;
 }
@@ -764,10 +762,10 @@ template <class FR, class FQ>
 int32_t srs_lagrange_generate(const uint32_t* beta_canon, const uint32_t* g_xy_mont, int log_n, uint32_t n_extra, uint32_t* d_out) {
     hipStream_t st = nullptr;
     const uint64_t n = 1ull << log_n, total = n + n_extra;
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.scalars.reserve(total * 32));
-    MZK_TRY(g_ws.misc.reserve(32 + 256 * 4 * FQ::N * 4 + 256 * 2 * FQ::N * 4 + 2 * FQ::N * 4));
-    uint32_t* d_beta = g_ws.misc.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->scalars.reserve(total * 32));
+    MZK_TRY(ws->misc.reserve(32 + 256 * 4 * FQ::N * 4 + 256 * 2 * FQ::N * 4 + 2 * FQ::N * 4));
+    uint32_t* d_beta = ws->misc.as<uint32_t>();
     uint32_t* d_tab_xyzz = d_beta + 8;
     uint32_t* d_tab = d_tab_xyzz + 256 * 4 * FQ::N;
     uint32_t* d_g = d_tab + 256 * 2 * FQ::N;
@@ -775,13 +773,12 @@ int32_t srs_lagrange_generate(const uint32_t* beta_canon, const uint32_t* g_xy_m
     if (g_xy_mont) HIP_TRY(hipMemcpyAsync(d_g, g_xy_mont, 2 * FQ::N * 4, hipMemcpyHostToDevice, st));
     const unsigned long long chunks = (n + 63) / 64;
     hipLaunchKernelGGL((fr_lagrange_kernel<FR>), dim3((unsigned)((chunks + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st,
-                       d_beta, log_n, n_extra, g_ws.scalars.as<uint32_t>());
+                       d_beta, log_n, n_extra, ws->scalars.as<uint32_t>());
     hipLaunchKernelGGL((g1_pow2_table_kernel<FQ>), dim3(1), dim3(64), 0, st, d_tab_xyzz, g_xy_mont ? d_g : nullptr);
     hipLaunchKernelGGL((g1_table_to_affine_kernel<FQ>), dim3(4), dim3(64), 0, st, d_tab_xyzz, d_tab, 256);
     hipLaunchKernelGGL((g1_fixed_base_kernel<FQ>), dim3((unsigned)((total + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS)), dim3(MSM_ACC_THREADS), 0, st,
-                       d_tab, g_ws.scalars.as<uint32_t>(), total, d_out);
+                       d_tab, ws->scalars.as<uint32_t>(), total, d_out);
     HIP_TRY(hipGetLastError());
-    MZK_TRY(ws_release(st));
     HIP_TRY(hipStreamSynchronize(st));
     return MZK_OK;
 }
@@ -793,16 +790,16 @@ int32_t srs_lagrange_from_points(const uint32_t* d_xy, int log_n, uint32_t n_ext
     using EC = EcFx<X>;
     hipStream_t st = nullptr;
     const uint64_t n = 1ull << log_n;
-    MZK_TRY(ws_acquire(st));
+    WsHold ws; MZK_TRY(ws.acquire(st));
     // the array (n points) and the window tables of the scalar multiplications (8 points for each of the n / 2 threads of a stage):
     // (5n + 8) XYZZ points -- 1.17 GB at 2^20 on BLS12-381, 18.8 GB at 2^24 -- a one-off set-up peak that is handed back below
     // instead of staying in the grow-only workspace (an MSM's over-long-bucket scratch needs a small fraction of it)
-    const size_t parts_before = g_ws.long_parts.cap, parts_need = (n * 5 + 8) * EC::PT_WORDS * 4;
-    MZK_TRY(g_ws.long_parts.reserve(parts_need));
-    MZK_TRY(g_ws.misc.reserve(64));
-    uint32_t* a = g_ws.long_parts.as<uint32_t>();
+    const size_t parts_before = ws->long_parts.cap, parts_need = (n * 5 + 8) * EC::PT_WORDS * 4;
+    MZK_TRY(ws->long_parts.reserve(parts_need));
+    MZK_TRY(ws->misc.reserve(64));
+    uint32_t* a = ws->long_parts.as<uint32_t>();
     uint32_t* tab = a + n * EC::PT_WORDS;
-    uint32_t* d_c = g_ws.misc.as<uint32_t>();
+    uint32_t* d_c = ws->misc.as<uint32_t>();
     F w = F::from_const(FR::ROOT);
     for (int i = log_n; i < FR::TWO_ADICITY; i++) w = sqr(w);
     const F winv = from_mont(inv(w)), ninv = from_mont(inv(from_u64<FR>(n)));
@@ -815,9 +812,8 @@ int32_t srs_lagrange_from_points(const uint32_t* d_xy, int log_n, uint32_t n_ext
     hipLaunchKernelGGL((ecx_ntt_finish_kernel<X>), dim3(gn), dim3(MSM_ACC_THREADS), 0, st, a, n, log_n, d_c + 8, tab, d_out);
     if (n_extra) hipLaunchKernelGGL((ec_ntt_extra_kernel<FQ>), dim3(1), dim3(64), 0, st, d_xy, n, n_extra, d_out + n * 2 * FQ::N);
     HIP_TRY(hipGetLastError());
-    MZK_TRY(ws_release(st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (parts_before < parts_need) g_ws.long_parts.release();          // the set-up peak does not stay resident
+    if (parts_before < parts_need) ws->long_parts.release();          // the set-up peak does not stay resident
     return MZK_OK;
 }
 

@@ -69,15 +69,12 @@ size_t Workspace::bytes() {
     return b;
 }
 
-int32_t ws_acquire(hipStream_t st) {
-    if (!g_ws.last_use) HIP_TRY(hipEventCreateWithFlags(&g_ws.last_use, hipEventDisableTiming));
-    else HIP_TRY(hipStreamWaitEvent(st, g_ws.last_use, 0));
+int32_t ws_acquire(Workspace& ws, hipStream_t st) {
+    if (!ws.last_use) HIP_TRY(hipEventCreateWithFlags(&ws.last_use, hipEventDisableTiming));
+    else HIP_TRY(hipStreamWaitEvent(st, ws.last_use, 0));
     return MZK_OK;
 }
-int32_t ws_release(hipStream_t st) {
-    HIP_TRY(hipEventRecord(g_ws.last_use, st));
-    return MZK_OK;
-}
+void ws_release(Workspace& ws, hipStream_t st) { (void)hipEventRecord(ws.last_use, st); }      // (a failure here must not replace the call's own error text)
 
 std::atomic<bool> g_prof{false};
 std::atomic<uint64_t> g_launches{0};
@@ -182,7 +179,7 @@ struct DevScratch {
 // third-party call sites uses) move their operands over PCIe.  Each call -- or each polynomial of a
 // batch -- takes one of the context's IO_SLOTS slots: a non-blocking stream plus a device buffer.  Upload, kernels and download of
 // one polynomial are enqueued on its slot's stream; the context's lock is held only while the kernels are ENQUEUED (plan cache and
-// shared workspace; ws_acquire / ws_release order the kernels of different streams on the shared scratch), never across a
+// shared workspace; a WsHold, internal.hpp, orders the kernels of different streams on the shared scratch), never across a
 // transfer or a wait.  So the upload of polynomial k+1 and the download of k-1 overlap the transform of k -- inside one batch
 // call and between concurrent callers (the reference commits and transforms from a Rayon par_iter, prover.rs:552-562,
 // univariate_kzg/mod.rs:125-127).  Transfers are asynchronous when the host memory is page-locked (mzk_host_alloc /
@@ -899,7 +896,8 @@ int32_t mzk_plonk_quotient(uint64_t pk_handle, const uint64_t* polys, uint64_t i
     if (!polys || !out || in_len == 0 || in_len > (8ull << log_n)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     const uint64_t n = 1ull << log_n, m = 8 * n;
     hipStream_t st = nullptr;
-    MZK_TRY(g_ws.plonk_out.reserve(m * 32));
+    WsHold ws; MZK_TRY(ws.acquire(st));       // the staging below is scratch of the shared workspace too
+    MZK_TRY(ws->plonk_out.reserve(m * 32));
     uint32_t classes[8];
     const int ncl = plonk_pk_classes(pk_handle, classes);
     if (ncl > 0) {
@@ -910,22 +908,22 @@ int32_t mzk_plonk_quotient(uint64_t pk_handle, const uint64_t* polys, uint64_t i
             set_error("chunked proving key: its classes do not determine the quotient (or a polynomial of degree >= 2n)");
             return MZK_ERR_INVALID_ARG;
         }
-        MZK_TRY(g_ws.io.reserve((size_t)(W + 2) * in_len * 32));
-        MZK_TRY(g_ws.link_tmp.reserve((size_t)ncl * n * 32));
-        HIP_TRY(hipMemcpyAsync(g_ws.io.p, polys, (size_t)(W + 2) * in_len * 32, hipMemcpyHostToDevice, st));
-        MZK_TRY(plonk_quotient_chunked_dev(pk_handle, g_ws.io.as<uint32_t>(), in_len, in_len, 0, nullptr, reinterpret_cast<const uint32_t*>(alpha_mont),
+        MZK_TRY(ws->io.reserve((size_t)(W + 2) * in_len * 32));
+        MZK_TRY(ws->link_tmp.reserve((size_t)ncl * n * 32));
+        HIP_TRY(hipMemcpyAsync(ws->io.p, polys, (size_t)(W + 2) * in_len * 32, hipMemcpyHostToDevice, st));
+        MZK_TRY(plonk_quotient_chunked_dev(pk_handle, ws->io.as<uint32_t>(), in_len, in_len, 0, nullptr, reinterpret_cast<const uint32_t*>(alpha_mont),
                                            reinterpret_cast<const uint32_t*>(beta_mont), reinterpret_cast<const uint32_t*>(gamma_mont),
-                                           g_ws.link_tmp.as<uint32_t>(), st));
-        MZK_TRY(plonk_quotient_combine_dev(plonk_pk_curve(pk_handle), log_n, classes, (uint32_t)ncl, g_ws.link_tmp.as<uint32_t>(), nullptr, 0,
-                                           g_ws.plonk_out.as<uint32_t>(), st));
+                                           ws->link_tmp.as<uint32_t>(), st));
+        MZK_TRY(plonk_quotient_combine_dev(plonk_pk_curve(pk_handle), log_n, classes, (uint32_t)ncl, ws->link_tmp.as<uint32_t>(), nullptr, 0,
+                                           ws->plonk_out.as<uint32_t>(), st));
     } else {
-        MZK_TRY(g_ws.plonk_polys.reserve((size_t)(W + 2) * m * 32));
-        HIP_TRY(hipMemcpy2DAsync(g_ws.plonk_polys.p, m * 32, polys, in_len * 32, in_len * 32, W + 2, hipMemcpyHostToDevice, st));
-        MZK_TRY(plonk_quotient_dev(pk_handle, g_ws.plonk_polys.as<uint32_t>(), in_len, nullptr, reinterpret_cast<const uint32_t*>(alpha_mont),
+        MZK_TRY(ws->plonk_polys.reserve((size_t)(W + 2) * m * 32));
+        HIP_TRY(hipMemcpy2DAsync(ws->plonk_polys.p, m * 32, polys, in_len * 32, in_len * 32, W + 2, hipMemcpyHostToDevice, st));
+        MZK_TRY(plonk_quotient_dev(pk_handle, ws->plonk_polys.as<uint32_t>(), in_len, nullptr, reinterpret_cast<const uint32_t*>(alpha_mont),
                                    reinterpret_cast<const uint32_t*>(beta_mont), reinterpret_cast<const uint32_t*>(gamma_mont),
-                                   g_ws.plonk_out.as<uint32_t>(), st));
+                                   ws->plonk_out.as<uint32_t>(), st));
     }
-    HIP_TRY(hipMemcpyAsync(out, g_ws.plonk_out.p, m * 32, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(out, ws->plonk_out.p, m * 32, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return MZK_OK;
 }
@@ -943,12 +941,13 @@ int32_t mzk_plonk_perm_product(uint64_t pk_handle, const uint64_t* wire_values, 
     if (!wire_values || !out) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
     const uint64_t n = 1ull << log_n;
     hipStream_t st = nullptr;
-    MZK_TRY(g_ws.plonk_polys.reserve((size_t)W * n * 32));
-    MZK_TRY(g_ws.plonk_out.reserve(n * 32));
-    HIP_TRY(hipMemcpyAsync(g_ws.plonk_polys.p, wire_values, (size_t)W * n * 32, hipMemcpyHostToDevice, st));
-    MZK_TRY(plonk_perm_product_dev(pk_handle, g_ws.plonk_polys.as<uint32_t>(), reinterpret_cast<const uint32_t*>(beta_mont),
-                                   reinterpret_cast<const uint32_t*>(gamma_mont), g_ws.plonk_out.as<uint32_t>(), st));
-    HIP_TRY(hipMemcpyAsync(out, g_ws.plonk_out.p, n * 32, hipMemcpyDeviceToHost, st));
+    WsHold ws; MZK_TRY(ws.acquire(st));       // the staging below is scratch of the shared workspace too
+    MZK_TRY(ws->plonk_polys.reserve((size_t)W * n * 32));
+    MZK_TRY(ws->plonk_out.reserve(n * 32));
+    HIP_TRY(hipMemcpyAsync(ws->plonk_polys.p, wire_values, (size_t)W * n * 32, hipMemcpyHostToDevice, st));
+    MZK_TRY(plonk_perm_product_dev(pk_handle, ws->plonk_polys.as<uint32_t>(), reinterpret_cast<const uint32_t*>(beta_mont),
+                                   reinterpret_cast<const uint32_t*>(gamma_mont), ws->plonk_out.as<uint32_t>(), st));
+    HIP_TRY(hipMemcpyAsync(out, ws->plonk_out.p, n * 32, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return MZK_OK;
 }

@@ -166,9 +166,9 @@ int32_t ntt_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n, bool in
     if (log_n == 0) { set_error("scaled size-1 transform"); return MZK_ERR_UNSUPPORTED; }
     NttPlanDev* pl;
     MZK_TRY(get_plan<X>(curve, log_n, inverse, coset, scale, &pl));
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.ntt_scratch.reserve((size_t)batch * N * 36));          // 9-limb planes between passes
-    uint32_t* scratch = g_ws.ntt_scratch.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->ntt_scratch.reserve((size_t)batch * N * 36));          // 9-limb planes between passes
+    uint32_t* scratch = ws->ntt_scratch.as<uint32_t>();
     ProfScope total("ntt_total", st);
     const int K = pl->h.n_pass;
     // transforms of at least 2^21 points take 2048-element tiles and stage pairs in registers (ntt_fx.cuh, R4): -4 % at 2^22, -7 % at 2^24;
@@ -188,7 +188,6 @@ int32_t ntt_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n, bool in
     }
     if (K == 1)
         HIP_TRY(hipMemcpy2DAsync(d_data, stride * 32, scratch, N * 32, N * 32, batch, hipMemcpyDeviceToDevice, st));
-    MZK_TRY(ws_release(st));
     return MZK_OK;
 }
 
@@ -213,9 +212,9 @@ int32_t ntt_classes_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n,
             return MZK_ERR_UNSUPPORTED;
         }
     if (K < 2) { set_error("ntt_classes: single-pass transform"); return MZK_ERR_UNSUPPORTED; }
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.ntt_scratch.reserve((size_t)batch * N * 36));
-    uint32_t* scratch = g_ws.ntt_scratch.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->ntt_scratch.reserve((size_t)batch * N * 36));
+    uint32_t* scratch = ws->ntt_scratch.as<uint32_t>();
     ProfScope total("ntt_total", st);
     for (int k = 0; k < K; k++) {
         const NttxPassArgs a = pass_args(pl[0]->h, k, NTT_TILE_LOG, d_data, stride, scratch, in_len, d_src, src_stride, d_patch, skip_batch);
@@ -235,7 +234,6 @@ int32_t ntt_classes_dev(int curve, uint32_t* d_data, uint64_t in_len, int log_n,
         hipLaunchKernelGGL((nttx_pass_classes_kernel<X>), dim3(n_tiles, (unsigned)batch), dim3(NTTX_THREADS), pass_lds_bytes(a), st, a, mc);
         HIP_TRY(hipGetLastError());
     }
-    MZK_TRY(ws_release(st));
     return MZK_OK;
 }
 

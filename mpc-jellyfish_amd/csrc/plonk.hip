@@ -113,9 +113,9 @@ int32_t pk_build(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_co
     for (int i = pk.log_n; i < P::TWO_ADICITY; i++) wn = sqr(wn);
     const F wn_inv = inv(wn);
     for (int q = 0; q < 8; q++) pk.w_inv[q] = wn_inv.l[q];
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.misc.reserve(128));
-    uint32_t* d_c = g_ws.misc.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->misc.reserve(128));
+    uint32_t* d_c = ws->misc.as<uint32_t>();
     HIP_TRY(hipMemcpyAsync(d_c, w.l, 32, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_c + 8, nf.l, 32, hipMemcpyHostToDevice, st));
     const uint64_t threads = (m + 15) / 16;
@@ -149,7 +149,6 @@ int32_t pk_build(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_co
     HIP_TRY(hipMemcpy2DAsync(pk.d_sigma_n, n * 32, sig_coeffs, poly_len * 32, sl * 32, pk.W, hipMemcpyHostToDevice, st));
     launch_powers<P>(st, &wn, 1, n, &pk.d_omega_n);
     HIP_TRY(hipGetLastError());
-    MZK_TRY(ws_release(st));
     MZK_TRY(ntt_dispatch(pk.curve, pk.d_sigma_n, sl, pk.log_n, false, nullptr, pk.W, n, st));
     if (pk.ultra) {
         HIP_TRY(hipMalloc((void**)&pk.d_tab_n, (size_t)5 * n * 32));
@@ -183,10 +182,10 @@ template <class P>
 int32_t perm_product_run(const PlonkPk& pk, const uint32_t* d_wires, const uint32_t* beta, const uint32_t* gamma, uint32_t* d_out, hipStream_t st) {
     const uint64_t n = 1ull << pk.log_n;
     ProfScope total("plonk_perm_product", st);
-    MZK_TRY(ws_acquire(st));
+    WsHold ws; MZK_TRY(ws.acquire(st));
     const unsigned n_blocks = (unsigned)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-    MZK_TRY(g_ws.io.reserve(3 * n * 32 + (size_t)n_blocks * 32));
-    uint32_t* ratio = g_ws.io.as<uint32_t>();
+    MZK_TRY(ws->io.reserve(3 * n * 32 + (size_t)n_blocks * 32));
+    uint32_t* ratio = ws->io.as<uint32_t>();
     uint32_t* den = ratio + n * 8;
     uint32_t* pref = den + n * 8;
     uint32_t* totals = pref + n * 8;
@@ -200,7 +199,6 @@ int32_t perm_product_run(const PlonkPk& pk, const uint32_t* d_wires, const uint3
     hipLaunchKernelGGL((fr_batch_div_kernel<P, typename FxOf<P>::type>), dim3((unsigned)((T + PLK_THREADS - 1) / PLK_THREADS)), dim3(PLK_THREADS), 0, st,
                        ratio, den, n, T, pref);
     MZK_TRY(scan_and_interpolate<P>(pk, ratio, totals, n_blocks, false, d_out, st));
-    MZK_TRY(ws_release(st));
     return ntt_dispatch(pk.curve, d_out, n, pk.log_n, true, nullptr, 1, n, st);
 }
 
@@ -221,9 +219,9 @@ int32_t sorted_vec_run(const PlonkPk& pk, const uint32_t* d_wires, const uint32_
     uint64_t slots = 4;
     while (slots < 4 * n) slots <<= 1;
     const unsigned n_blocks = (unsigned)((n + PLK_SCAN_BLOCK - 1) / PLK_SCAN_BLOCK);
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.io.reserve(slots * 4 + n * 4 + n * 4 + (size_t)n_blocks * 4 + 64));
-    uint32_t* d_slots = g_ws.io.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->io.reserve(slots * 4 + n * 4 + n * 4 + (size_t)n_blocks * 4 + 64));
+    uint32_t* d_slots = ws->io.as<uint32_t>();
     uint32_t* d_count = d_slots + slots;
     uint32_t* d_pos = d_count + n;
     uint32_t* d_totals = d_pos + n;
@@ -246,7 +244,6 @@ int32_t sorted_vec_run(const PlonkPk& pk, const uint32_t* d_wires, const uint32_
     uint32_t missing = 0;
     HIP_TRY(hipMemcpyAsync(&missing, d_missing, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    MZK_TRY(ws_release(st));
     if (missing) {
         set_error("The sorted vector has wrong length, some lookup variables might be outside the table");      // constraint_system.rs:1410-1412
         return MZK_ERR_LOOKUP;
@@ -260,10 +257,10 @@ int32_t lookup_product_run(const PlonkPk& pk, const uint32_t* d_table, const uin
                            const uint32_t* gamma, uint32_t* d_out, hipStream_t st) {
     const uint64_t n = 1ull << pk.log_n;
     ProfScope total("plookup_product", st);
-    MZK_TRY(ws_acquire(st));
+    WsHold ws; MZK_TRY(ws.acquire(st));
     const unsigned n_blocks = (unsigned)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
-    MZK_TRY(g_ws.io.reserve(3 * n * 32 + (size_t)n_blocks * 32));
-    uint32_t* ratio = g_ws.io.as<uint32_t>();
+    MZK_TRY(ws->io.reserve(3 * n * 32 + (size_t)n_blocks * 32));
+    uint32_t* ratio = ws->io.as<uint32_t>();
     uint32_t* den = ratio + n * 8;
     uint32_t* pref = den + n * 8;
     uint32_t* totals = pref + n * 8;
@@ -276,7 +273,6 @@ int32_t lookup_product_run(const PlonkPk& pk, const uint32_t* d_table, const uin
     hipLaunchKernelGGL((fr_batch_div_kernel<P, typename FxOf<P>::type>), dim3((unsigned)((T + PLK_THREADS - 1) / PLK_THREADS)), dim3(PLK_THREADS), 0, st,
                        ratio, den, n, T, pref);
     MZK_TRY(scan_and_interpolate<P>(pk, ratio, totals, n_blocks, true, d_out, st));
-    MZK_TRY(ws_release(st));
     return ntt_dispatch(pk.curve, d_out, n, pk.log_n, true, nullptr, 1, n, st);
 }
 
@@ -390,9 +386,9 @@ int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t
     if (pk.ultra) HIP_TRY(hipMalloc((void**)&pk.d_inv_den_n, ncl * n * 32));
     HIP_TRY(hipMemsetAsync(pk.d_fixed, 0, (size_t)nfix * ncl * n * 32, st));
     const uint64_t sl = poly_len < n ? poly_len : n;               // fixed polynomials have degree < n
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.misc.reserve(512));
-    uint32_t* d_c = g_ws.misc.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->misc.reserve(512));
+    uint32_t* d_c = ws->misc.as<uint32_t>();
     const F one = F::one(), scale_n = nf * wn;
     HIP_TRY(hipMemcpyAsync(d_c, wn.l, 32, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_c + 8, nf.l, 32, hipMemcpyHostToDevice, st));
@@ -434,7 +430,6 @@ int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t
     HIP_TRY(hipMemcpy2DAsync(pk.d_sigma_n, n * 32, sig_coeffs, poly_len * 32, sl * 32, pk.W, hipMemcpyHostToDevice, st));
     launch_powers<P>(st, &wn, 1, n, &pk.d_omega_n);
     HIP_TRY(hipGetLastError());
-    MZK_TRY(ws_release(st));
     // class evaluations of the fixed polynomials: size-n coset NTTs with offset h_k, all polynomials of a class in one batch
     for (size_t lc = 0; lc < ncl; lc++)
         MZK_TRY(ntt_dispatch(pk.curve, pk.d_fixed + lc * n * 8, sl, pk.log_n, false, pk.h_cls[pk.cls[lc]], nfix, ncl * n, st, 1));     // internal form
@@ -507,9 +502,9 @@ int32_t quotient_chunked_run(const PlonkPk& pk, const uint32_t* d_polys, uint64_
     const int rows = pk.W + 2 + (pk.ultra ? 3 : 0);
     const size_t ncl = pk.cls.size();
     ProfScope total("plonk_quotient_chunked_total", st);
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.plonk_polys.reserve((size_t)rows * n * 32 + 64 + (size_t)rows * 4 * 32));
-    uint32_t* work = g_ws.plonk_polys.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->plonk_polys.reserve((size_t)rows * n * 32 + 64 + (size_t)rows * 4 * 32));
+    uint32_t* work = ws->plonk_polys.as<uint32_t>();
     uint32_t* patch = work + ((size_t)rows * n + 2) * 8;
     const bool pi_zero = (flags & MZK_QUOTIENT_PI_ZERO) != 0;              // the caller knows its public-input polynomial is zero: row W + 1 is neither
                                                                            // transformed nor read
@@ -526,8 +521,8 @@ int32_t quotient_chunked_run(const PlonkPk& pk, const uint32_t* d_polys, uint64_
     static const bool no_class_batch = std::getenv("MZK_QUOTIENT_NO_CLASS_BATCH") != nullptr;
     static const int class_batch_max_log = std::getenv("MZK_QUOTIENT_CLASS_BATCH_MAX_LOG") ? std::atoi(std::getenv("MZK_QUOTIENT_CLASS_BATCH_MAX_LOG")) : 18;      // (tuning switch; measured: 2^18 gates 1.97 -> 1.60 ms, 2^19 3.47 -> 3.28, 2^20 no gain for 1.1 GB more workspace)
     if (patched && ncl > 1 && ncl <= (size_t)PLK_RATIO && pk.log_n >= 10 && pk.log_n <= class_batch_max_log && !no_class_batch) {
-        MZK_TRY(g_ws.plonk_polys.reserve(ncl * (size_t)rows * n * 32 + 64 + ncl * (size_t)rows * 4 * 32));
-        work = g_ws.plonk_polys.as<uint32_t>();
+        MZK_TRY(ws->plonk_polys.reserve(ncl * (size_t)rows * n * 32 + 64 + ncl * (size_t)rows * 4 * 32));
+        work = ws->plonk_polys.as<uint32_t>();
         patch = work + (ncl * (size_t)rows * n + 2) * 8;
         FoldClasses fc;
         const uint32_t* cosets[PLK_RATIO];                          // (= NTTX_MAX_CLASSES of ntt_fx.cuh)
@@ -568,7 +563,6 @@ int32_t quotient_chunked_run(const PlonkPk& pk, const uint32_t* d_polys, uint64_
         }
         HIP_TRY(hipGetLastError());
         MZK_TRY(ntt_classes_dispatch(pk.curve, d_out, n, pk.log_n, true, cosets, (int)ncl, 1, n, st, 2, nullptr, 0, nullptr, -1));     // back to the boundary form
-        MZK_TRY(ws_release(st));
         return MZK_OK;
     }
     for (size_t lc = 0; lc < ncl; lc++) {
@@ -615,7 +609,6 @@ int32_t quotient_chunked_run(const PlonkPk& pk, const uint32_t* d_polys, uint64_
         HIP_TRY(hipGetLastError());
         MZK_TRY(ntt_dispatch(pk.curve, d_out + lc * n * 8, n, pk.log_n, true, pk.h_cls[k], 1, n, st, 2));  // back to the boundary form
     }
-    MZK_TRY(ws_release(st));
     return MZK_OK;
 }
 
@@ -691,17 +684,16 @@ int32_t witness_check_run(const PlonkPk& pk, const WitnessCheckIn& in, mzk_witne
         }
     }
     ProfScope total("witness_check", st);
-    MZK_TRY(ws_acquire(st));
-    struct Release { hipStream_t st; ~Release() { (void)ws_release(st); } } release{st};      // on every return path: what is queued on st stays covered
+    WsHold ws; MZK_TRY(ws.acquire(st));
     const uint64_t wit_elems = in.kind == MZK_WITNESS_HOST_VECTOR ? in.n_vars : 0;
     const uint64_t pi_stage = pi_at.size() + (pi_at.size() + 7) / 8;                        // values, then the rows (u32), in elements
-    MZK_TRY(g_ws.plonk_polys.reserve(((uint64_t)PLK_SELECTORS * n + (own_wires ? cells : 0) + (pi_any ? n : 0) + wit_elems + pi_stage) * 32));
-    MZK_TRY(g_ws.io.reserve((CHK_WORDS + slots + (copy ? in.n_vars : 0)) * 4));
-    uint32_t* d_sel = g_ws.plonk_polys.as<uint32_t>();
+    MZK_TRY(ws->plonk_polys.reserve(((uint64_t)PLK_SELECTORS * n + (own_wires ? cells : 0) + (pi_any ? n : 0) + wit_elems + pi_stage) * 32));
+    MZK_TRY(ws->io.reserve((CHK_WORDS + slots + (copy ? in.n_vars : 0)) * 4));
+    uint32_t* d_sel = ws->plonk_polys.as<uint32_t>();
     uint32_t* d_own = d_sel + (size_t)PLK_SELECTORS * n * 8;
     uint32_t* d_pi = d_own + (own_wires ? cells * 8 : 0);
     uint32_t* d_wit = d_pi + (pi_any ? n * 8 : 0);
-    uint32_t* d_res = g_ws.io.as<uint32_t>();
+    uint32_t* d_res = ws->io.as<uint32_t>();
     uint32_t* d_slots = d_res + CHK_WORDS;
     uint32_t* d_rep = d_slots + slots;
     // selector values on H

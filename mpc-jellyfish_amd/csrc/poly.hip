@@ -17,9 +17,9 @@ int32_t eval_run(const uint32_t* d_coeffs, uint64_t stride, uint64_t len, uint32
     while (T * 32 < len && T < (uint64_t)POLY_EVAL_T_MAX) T <<= 1;
     const F y = pow_u64(x, T);
     const int blocks = (int)(T / POLY_THREADS);
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.poly_tmp.reserve((size_t)T * 32 + (size_t)batch * blocks * 32 + (size_t)batch * 32));
-    uint32_t* xpow = g_ws.poly_tmp.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->poly_tmp.reserve((size_t)T * 32 + (size_t)batch * blocks * 32 + (size_t)batch * 32));
+    uint32_t* xpow = ws->poly_tmp.as<uint32_t>();
     uint32_t* partial = xpow + (size_t)T * 8;
     uint32_t* d_out = partial + (size_t)batch * blocks * 8;
     const uint64_t tlen = len < T ? len : T;
@@ -29,7 +29,6 @@ int32_t eval_run(const uint32_t* d_coeffs, uint64_t stride, uint64_t len, uint32
     hipLaunchKernelGGL((poly_eval_final_kernel<P>), dim3(batch), dim3(POLY_THREADS), 0, st, partial, blocks, d_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, d_out, (size_t)batch * 32, hipMemcpyDeviceToHost, st));
-    MZK_TRY(ws_release(st));
     HIP_TRY(hipStreamSynchronize(st));
     return MZK_OK;
 }
@@ -48,9 +47,9 @@ int32_t eval_many_run(const EvalJob* jobs, uint32_t n_jobs, const uint32_t* x_mo
     const int blocks = (int)(T / POLY_THREADS);
     F x[2], y[2];
     for (int q = 0; q < 2; q++) { std::memcpy(x[q].l, x_mont + 8 * q, 32); y[q] = pow_u64(x[q], T); }
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.poly_tmp.reserve(2 * (size_t)T * 32 + (size_t)total * blocks * 32 + (size_t)total * 32));
-    uint32_t* xpow = g_ws.poly_tmp.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->poly_tmp.reserve(2 * (size_t)T * 32 + (size_t)total * blocks * 32 + (size_t)total * 32));
+    uint32_t* xpow = ws->poly_tmp.as<uint32_t>();
     uint32_t* partial = xpow + 2 * (size_t)T * 8;
     uint32_t* d_out = partial + (size_t)total * blocks * 8;
     const uint64_t tlen = max_len < T ? max_len : T;
@@ -76,7 +75,6 @@ int32_t eval_many_run(const EvalJob* jobs, uint32_t n_jobs, const uint32_t* x_mo
     hipLaunchKernelGGL((poly_eval_final_kernel<P>), dim3((unsigned)total), dim3(POLY_THREADS), 0, st, partial, blocks, d_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, d_out, (size_t)total * 32, hipMemcpyDeviceToHost, st));
-    MZK_TRY(ws_release(st));
     HIP_TRY(hipStreamSynchronize(st));
     return MZK_OK;
 }
@@ -96,9 +94,9 @@ int32_t div_run(const uint32_t* d_poly, uint64_t len, const uint32_t* z_mont, ui
     }
     const F zi = inv(z);
     const unsigned n_blocks = (unsigned)((len + DIV_BLOCK - 1) / DIV_BLOCK);
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.poly_tmp.reserve((size_t)len * 32 * 3 + (size_t)n_blocks * 32));
-    uint32_t* zpow = g_ws.poly_tmp.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->poly_tmp.reserve((size_t)len * 32 * 3 + (size_t)n_blocks * 32));
+    uint32_t* zpow = ws->poly_tmp.as<uint32_t>();
     uint32_t* zinvpow = zpow + len * 8;
     uint32_t* t = zinvpow + len * 8;
     uint32_t* totals = t + len * 8;
@@ -113,7 +111,6 @@ int32_t div_run(const uint32_t* d_poly, uint64_t len, const uint32_t* z_mont, ui
     hipLaunchKernelGGL((fr_suffix_add_totals_kernel<P>), dim3(1), dim3(1024), 0, st, totals, n_blocks);
     hipLaunchKernelGGL((poly_div_finish_kernel<P>), dim3(eg), dim3(POLY_THREADS), 0, st, t, totals, zinvpow, len, d_out, d_rem);
     HIP_TRY(hipGetLastError());
-    MZK_TRY(ws_release(st));
     return MZK_OK;
 }
 
@@ -144,9 +141,9 @@ int32_t div_roots_run(int curve, const uint32_t* d_poly, uint64_t len, uint32_t 
     const int log_e = log_q > (int)log_order ? log_q : (int)log_order;
     bool fast = len >= 64 && count <= (1ull << log_order) && log_e <= P::TWO_ADICITY && log_e <= 27;
     const uint64_t Ne = 1ull << log_e, Nq = 1ull << log_q;
-    MZK_TRY(ws_acquire(st));
-    MZK_TRY(g_ws.link_tmp.reserve(((fast && Ne > 2 * len) ? Ne : 2 * len) * 32 + 2 * count * 32));     // either path may follow the root check
-    uint32_t* T = g_ws.link_tmp.as<uint32_t>();
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->link_tmp.reserve(((fast && Ne > 2 * len) ? Ne : 2 * len) * 32 + 2 * count * 32));     // either path may follow the root check
+    uint32_t* T = ws->link_tmp.as<uint32_t>();
     uint32_t* d_at_roots = T + (((fast && Ne > 2 * len) ? Ne : 2 * len)) * 8;
     uint32_t* d_roots = d_at_roots + count * 8;
     DivRootsArgs a;
@@ -208,7 +205,6 @@ int32_t div_roots_run(int curve, const uint32_t* d_poly, uint64_t len, uint32_t 
             root = root * g;
         }
     }
-    MZK_TRY(ws_release(st));
     return MZK_OK;
 }
 

@@ -303,3 +303,68 @@ def test_quotient_kernel_limb_extremes(gpu, mj, cref, curve_id):
     want = cref.plonk_quotient(curve_id, log_n, polys, mj.params.fr_to_mont(c, k), *mj.params.fr_to_mont(c, [a, b, gm]), threads=2)
     assert np.array_equal(got, want)
     pk.release()
+
+
+@pytest.mark.parametrize("curve_id", [0, 1])
+def test_host_pointer_calls_share_the_workspace_with_a_side_stream(gpu, mj, curve_id):
+    """mzk_plonk_quotient and mzk_plonk_perm_product stage their operands in the context's shared scratch on the null stream: they hold
+    the workspace like every other user of it.  One thread issues them while another runs the chunked quotient and the combine on a
+    side stream, over one key; every result equals the value the same call gave alone, bit for bit.  2^10 gates: the smallest size at
+    which the chunked quotient runs all classes in one launch per step (plonk.hip quotient_chunked_run), i.e. with its real scratch layout."""
+    import threading
+    import torch
+    c = mj.params.CURVES[curve_id]
+    n, iters = 1 << 10, 24
+    rng = random.Random(77 + curve_id)
+    fixed = mj.params.random_fr_mont(c, 18 * n, seed=31 + curve_id).reshape(18, n, 4)
+    k = [rng.randrange(1, c.r) for _ in range(5)]
+    cl = mj.plonk.quotient_classes_needed(5, n, top=False)
+    assert cl == [0, 1, 2, 3, 4, 5]
+    pk = mj.plonk.ProvingKeyDevice.register(c, n, list(fixed[:13]), list(fixed[13:]), k, classes=cl)
+
+    def online(seed):                                            # wires with two blinding coefficients, z with three, the public input
+        rows = mj.params.random_fr_mont(c, 7 * (n + 3), seed=seed).reshape(7, n + 3, 4)
+        rows[:5, n + 2:] = 0
+        rows[6, n:] = 0
+        return rows
+    host_rows, dev_rows = online(41), online(43)
+    ch_host, ch_dev = (mj.plonk.Challenges(rng.randrange(c.r), rng.randrange(c.r), rng.randrange(c.r)) for _ in range(2))
+    wires = mj.params.random_fr_mont(c, 5 * n, seed=47).reshape(5, n, 4)
+    beta, gamma = rng.randrange(c.r), rng.randrange(c.r)
+    side = torch.cuda.Stream()
+    slab = torch.from_numpy(dev_rows.view(np.int64)).cuda()
+    torch.cuda.synchronize()
+
+    def host_calls():                                            # host pointers: the null stream
+        q = mj.plonk.compute_quotient_polynomial(pk, ch_host, [host_rows[j, :n + 2] for j in range(5)], host_rows[5], host_rows[6, :n])
+        return q, mj.plonk.compute_prod_permutation_polynomial(pk, beta, gamma, wires)
+
+    def dev_calls():                                             # device pointers: the side stream (the stream of this thread inside `with`)
+        with torch.cuda.stream(side):
+            rem = mj.plonk.compute_quotient_chunked_dev(pk, ch_dev, slab, n + 3)
+            return mj.plonk.combine_quotient_classes(c, n, rem, classes=cl).cpu().numpy().view(np.uint64)
+
+    want_q, want_z = host_calls()
+    want_dev = dev_calls()
+    assert want_q[5 * n:6 * n].any() and want_z.any() and want_dev[5 * n:6 * n].any() and not np.array_equal(want_q, want_dev)
+    got, errors = {"host": [], "dev": []}, []
+
+    def worker(name, fn):
+        try:
+            for _ in range(iters):
+                got[name].append(fn())
+        except Exception as e:                                   # (reported by the main thread)
+            errors.append((name, e))
+    threads = [threading.Thread(target=worker, args=a) for a in (("host", host_calls), ("dev", dev_calls))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    assert len(got["host"]) == iters and len(got["dev"]) == iters
+    for i, (q, z) in enumerate(got["host"]):
+        assert np.array_equal(q, want_q), "host-pointer quotient, iteration %d" % i
+        assert np.array_equal(z, want_z), "host-pointer permutation product, iteration %d" % i
+    for i, d in enumerate(got["dev"]):
+        assert np.array_equal(d, want_dev), "side-stream chunked quotient + combine, iteration %d" % i
+    pk.release()
