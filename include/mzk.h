@@ -299,6 +299,23 @@ MZK_API int32_t mzk_plonk_quotient_top_dev(uint64_t pk_handle, const void* d_pol
 MZK_API int32_t mzk_plonk_quotient_combine_top_dev(int32_t curve_id, uint32_t log_n, const uint32_t* classes, uint32_t n_classes,
                                                    const void* d_class_remainders, const void* d_top, uint32_t n_top, void* d_out, void* stream);
 
+/* ---- preprocess from circuit structure: the permutation half of PlonkKzgSnark::preprocess (plonk/src/proof_system/snark.rs:529-617) ----
+ * mzk_plonk_wire_permutation_dev replaces compute_wire_permutation (relation/src/constraint_system.rs:743-778).  d_wire_variables: `cells`
+ * u32 variable indices; in a circuit cell c = wire * n + row (cells = W n), but any count below 2^32 is taken (MZK_ERR_UNSUPPORTED at or
+ * above).  A variable on the cells c_0 < c_1 < .. < c_(m-1) yields d_out_next_u32[c_i] = c_((i+1) mod m): a variable with one cell maps to
+ * itself, variables without a cell are legal (1 <= n_vars).  Field-independent.  The result is a function of the table alone, identical
+ * from run to run (a stable radix sort on the variable index: csrc/perm.cuh; no order is left to atomics).  Every index is checked: one
+ * >= n_vars makes the call fail with MZK_ERR_INVALID_ARG and mzk_last_error() names the lowest such cell and its value (the reference
+ * panics on such an index).  Scratch (16 B per cell) is the context's shared scratch.  Synchronises (it returns the validation result). */
+MZK_API int32_t mzk_plonk_wire_permutation_dev(const void* d_wire_variables, uint64_t cells, uint64_t n_vars, void* d_out_next_u32, void* stream);
+/* Replaces compute_extended_id_permutation / compute_extended_permutation (relation/src/constraint_system.rs:913-960):
+ * d_out[c] = k[next[c] / n] * w^(next[c] mod n) for c < num_wire_types * n, n = 2^log_n, Montgomery, w the primitive n-th root of unity
+ * the NTT uses, k_mont the num_wire_types (5 or 6) coset representatives (host): the values of the sigma polynomials on the gate
+ * domain, wire-major -- what the inverse NTTs of constraint_system.rs:1162-1195 turn into `ProvingKey::sigmas`.  d_next_u32 from
+ * mzk_plonk_wire_permutation_dev over num_wire_types * n cells (< 2^32).  Asynchronous. */
+MZK_API int32_t mzk_plonk_sigma_values_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_next_u32, const uint64_t* k_mont, void* d_out,
+                                           void* stream);
+
 /* Round 2: replaces Arithmetization::compute_prod_permutation_polynomial
  * (relation/src/constraint_system.rs:1197-1223), whose loop performs one field division per gate.
  * wire_values: 5 x n (UltraPlonk key: 6 x n) wire evaluations witness[wire_variable(i, j)]; the sigma evaluations
@@ -443,6 +460,23 @@ typedef struct mzk_comm {
 MZK_API int32_t mzk_prover_create(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const uint64_t* selector_coeffs,
                                   const uint64_t* sigma_coeffs, const uint64_t* table_coeffs, uint64_t poly_len, const uint64_t* k_mont,
                                   uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, uint64_t* out_prover);
+/* The same prover from what a FINALISED CIRCUIT holds -- the whole of PlonkKzgSnark::preprocess (snark.rs:529-617) on the device:
+ * compute_wire_permutation, compute_extended_permutation and the 13 + W (+ 4) inverse FFTs of compute_selector_polynomials /
+ * compute_extended_permutation_polynomials (relation/src/constraint_system.rs:743-778, 913-960, 1162-1195) and of the Plookup table
+ * polynomials.  selector_values: nsel x n VALUES on the gate domain (selector order as above), wire_variables: W x n u32 variable indices
+ * (wire-major, every entry < n_vars, 1 <= n_vars < 2^32; checked, MZK_ERR_INVALID_ARG names the lowest offending cell), table_values:
+ * 4 x n values (range, key, table_dom_sep, q_dom_sep) or NULL for TurboPlonk.  Wire permutation -> sigma values -> one batched inverse
+ * NTT over all nsel + W (+ 4) rows -> everything mzk_prover_create does, from coefficient forms that never leave the device.  The
+ * variable table stays resident exactly as after mzk_prover_set_wire_variables: the *_VECTOR witness kinds work at once and
+ * mzk_prover_check_witness checks the copy constraints of every witness kind.  comm as for mzk_prover_create: every rank computes the
+ * same key, there is no collective call.  Set-up peak: (nsel + W (+ 4)) x n x 32 B besides the prover's own memory, handed back before
+ * the call returns.  The _dev form takes device arrays, complete on the null stream (or synchronised).  Both synchronise. */
+MZK_API int32_t mzk_prover_create_from_circuit(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const uint64_t* selector_values,
+                                               const uint32_t* wire_variables, uint64_t n_vars, const uint64_t* table_values, const uint64_t* k_mont,
+                                               uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, uint64_t* out_prover);
+MZK_API int32_t mzk_prover_create_from_circuit_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_selector_values,
+                                                   const void* d_wire_variables, uint64_t n_vars, const void* d_table_values, const uint64_t* k_mont,
+                                                   uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, uint64_t* out_prover);
 MZK_API int32_t mzk_prover_destroy(uint64_t prover);
 /* `VerifyingKey{selector_comms, sigma_comms}` (preprocess, snark.rs:562-594) from the resident coefficient forms: nsel + W affine points,
  * then -- UltraPlonk, out_plookup_xy non-NULL -- range_table_comm, key_table_comm, table_dom_sep_comm, q_dom_sep_comm (:575-590). */
@@ -479,7 +513,8 @@ MZK_API int32_t mzk_prover_round1(uint64_t prover, int32_t witness_kind, const v
  *   copy    *_VECTOR kinds: the copy constraints hold by construction (copy_checked = 1, no failures).  *_WIRES kinds with a table from
  *           mzk_prover_set_wire_variables: the representative of a variable is its cell of smallest index wire * n + row; a cell fails
  *           iff its value differs from its representative's; copy_cell is the failing cell of smallest index.  *_WIRES kinds without a
- *           table: copy_checked = 0 and `kind` is decided by the other two families (sigma is not decoded back to cells).
+ *           table: copy_checked = 0 and `kind` is decided by the other two families (sigma is not decoded back to cells).  A prover from
+ *           mzk_prover_create_from_circuit has the table.
  * Counts and locations are exact and deterministic.  MZK_ERR_INVALID_ARG: null report, wrong witness_len, a *_VECTOR kind without
  * mzk_prover_set_wire_variables, a public-input row >= n.  MZK_ERR_UNSUPPORTED: copy check with W n >= 2^32.
  * The call synchronises, needs no SRS and makes no collective call (with an mzk_comm any rank may call it alone).  Like a new

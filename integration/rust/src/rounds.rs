@@ -56,6 +56,9 @@ extern "C" {
     pub fn mzk_prover_create(curve_id: i32, log_n: u32, num_wire_types: u32, selector_coeffs: *const u64, sigma_coeffs: *const u64,
                              table_coeffs: *const u64, poly_len: u64, k_mont: *const u64, commit_key: u64, lagrange_key: u64,
                              comm: *const c_void, out_prover: *mut u64) -> i32;
+    pub fn mzk_prover_create_from_circuit(curve_id: i32, log_n: u32, num_wire_types: u32, selector_values: *const u64, wire_variables: *const u32,
+                                          n_vars: u64, table_values: *const u64, k_mont: *const u64, commit_key: u64, lagrange_key: u64,
+                                          comm: *const c_void, out_prover: *mut u64) -> i32;
     pub fn mzk_prover_destroy(prover: u64) -> i32;
     pub fn mzk_prover_set_wire_variables(prover: u64, wire_variables: *const u32, n_vars: u64) -> i32;
     pub fn mzk_prover_round1(prover: u64, witness_kind: i32, witness: *const c_void, witness_len: u64, pub_input_rows: *const u64,
@@ -123,6 +126,32 @@ impl Mi355Prover {
         let me = Self { handle, num_wire_types, ultra: tables.is_some(), fq_limbs, lagrange_key: lagrange };
         unsafe { check(mzk_prover_set_wire_variables(handle, wire_variables.as_ptr(), n_vars as u64))? };
         Ok(me)
+    }
+
+    /// The same prover from the FINALISED CIRCUIT instead of a `ProvingKey`: `PlonkKzgSnark::preprocess` (snark.rs:529-617) on the
+    /// device.  `selector_values` / `table_values`: the VALUES on the gate domain, each vector of length n = 2^log_n, concatenated
+    /// (`cs.all_selectors()` before `compute_selector_polynomials`' iFFTs, constraint_system.rs:1162-1177; range, key, table_dom_sep,
+    /// q_dom_sep); `wire_variables`: W x n variable indices, wire-major.  compute_wire_permutation, compute_extended_permutation and
+    /// the 13 + W (+ 4) iFFTs run inside the library; nothing but nsel x n x 32 B of selector values and W x n x 4 B of indices is
+    /// uploaded, and no CPU preprocess is needed.  The variable table stays with the prover: no `mzk_prover_set_wire_variables`.
+    #[allow(clippy::too_many_arguments)]
+    pub fn from_circuit<F: PrimeField>(curve_id: i32, log_n: u32, selector_values: &[F], table_values: Option<&[F]>, k: &[F], commit_key: &SrsHandle,
+                                       lagrange_round1: bool, wire_variables: &[u32], n_vars: usize, fq_limbs: usize) -> Result<Self, Mi355Error> {
+        let num_wire_types = k.len();
+        let (mut lagrange, mut handle) = (0u64, 0u64);
+        unsafe {
+            if lagrange_round1 {
+                check(mzk_srs_lagrange_from_srs(commit_key.raw(), log_n, 3, &mut lagrange))?;
+            }
+            let made = check(mzk_prover_create_from_circuit(curve_id, log_n, num_wire_types as u32, flat(selector_values), wire_variables.as_ptr(),
+                                                            n_vars as u64, table_values.map_or(core::ptr::null(), |t| flat(t)), flat(k),
+                                                            commit_key.raw(), lagrange, core::ptr::null(), &mut handle));
+            if made.is_err() && lagrange != 0 {
+                mzk_srs_release(lagrange);                         // nothing of a failed construction stays in HBM
+            }
+            made?;
+        }
+        Ok(Self { handle, num_wire_types, ultra: table_values.is_some(), fq_limbs, lagrange_key: lagrange })
     }
 
     /// `Circuit::check_circuit_satisfiability` (relation/src/constraint_system.rs:389-451) on the device, for the witness vector

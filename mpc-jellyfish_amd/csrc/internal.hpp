@@ -18,6 +18,10 @@
 extern "C" int32_t mzk_ctx_prover_stream(uint32_t k, void** out_stream);
 // ... and runs the witness check of a prover handle on its proving key (plonk.hip plonk_check_witness_dev), under the context's lock
 namespace mzk { struct WitnessCheckIn; }
+// ... and registers a chunked proving key whose coefficient forms are resident on the device already (mzk_prover_create_from_circuit)
+extern "C" int32_t mzk_ctx_pk_register_chunked(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* selector_coeffs, const void* sigma_coeffs,
+                                               const void* table_coeffs, uint64_t poly_len, const uint64_t* k_mont, const uint32_t* classes, uint32_t n_classes,
+                                               int32_t coeffs_on_device, uint64_t* out_handle);
 extern "C" int32_t mzk_ctx_check_witness(uint64_t pk_handle, const mzk::WitnessCheckIn* in, mzk_witness_report* out_report, void* stream);
 
 namespace mzk {
@@ -205,7 +209,10 @@ int32_t poly_mask_dispatch(int curve, uint32_t n_rows, uint32_t* const* d_rows, 
 // plonk.hip
 int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, const uint32_t* sig, const uint32_t* tab /* NULL: TurboPlonk */,
                           uint64_t poly_len, const uint32_t* k_mont, const uint32_t* classes /* NULL: whole domain */, uint32_t n_classes,
-                          uint64_t* out_handle);
+                          uint64_t* out_handle, bool coeffs_on_device = false /* sel, sig, tab are device pointers */);
+// the wire permutation of a variable table and its sigma values (perm.cuh)
+int32_t plonk_wire_permutation_dev(const uint32_t* d_vars, uint64_t cells, uint64_t n_vars, uint32_t* d_next, hipStream_t st);
+int32_t plonk_sigma_values_dev(int curve, int log_n, int W, const uint32_t* d_next, const uint32_t* k_mont, uint32_t* d_out, hipStream_t st);
 int32_t plonk_quotient_chunked_dev(uint64_t handle, const uint32_t* d_polys, uint64_t in_stride, uint64_t in_len, uint32_t flags, const uint32_t* tau,
                                    const uint32_t* alpha, const uint32_t* beta, const uint32_t* gamma, uint32_t* d_out, hipStream_t st);
 int32_t plonk_quotient_top_dev(uint64_t handle, const uint32_t* d_polys, uint64_t in_stride, uint64_t in_len, const uint32_t* alpha, const uint32_t* beta,

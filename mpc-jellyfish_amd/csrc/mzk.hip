@@ -811,6 +811,27 @@ int32_t mzk_plonk_pk_register_chunked(int32_t curve_id, uint32_t log_n, uint32_t
                              reinterpret_cast<const uint32_t*>(sigma_coeffs), reinterpret_cast<const uint32_t*>(table_coeffs), poly_len,
                              reinterpret_cast<const uint32_t*>(k_mont), classes, n_classes, out_handle);
 }
+int32_t mzk_ctx_pk_register_chunked(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* selector_coeffs, const void* sigma_coeffs,
+                                    const void* table_coeffs, uint64_t poly_len, const uint64_t* k_mont, const uint32_t* classes, uint32_t n_classes,
+                                    int32_t coeffs_on_device, uint64_t* out_handle) {
+    ENTER_CUR();
+    if (!classes || (num_wire_types == 6) != (table_coeffs != nullptr)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    return plonk_pk_register(curve_id, (int)log_n, (int)num_wire_types, reinterpret_cast<const uint32_t*>(selector_coeffs),
+                             reinterpret_cast<const uint32_t*>(sigma_coeffs), reinterpret_cast<const uint32_t*>(table_coeffs), poly_len,
+                             reinterpret_cast<const uint32_t*>(k_mont), classes, n_classes, out_handle, coeffs_on_device != 0);
+}
+int32_t mzk_plonk_wire_permutation_dev(const void* d_wire_variables, uint64_t cells, uint64_t n_vars, void* d_out_next_u32, void* stream) {
+    ENTER_CUR();
+    return plonk_wire_permutation_dev(reinterpret_cast<const uint32_t*>(d_wire_variables), cells, n_vars, reinterpret_cast<uint32_t*>(d_out_next_u32),
+                                      (hipStream_t)stream);
+}
+int32_t mzk_plonk_sigma_values_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_next_u32, const uint64_t* k_mont, void* d_out,
+                                   void* stream) {
+    ENTER_CUR();
+    if (log_n > 32) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    return plonk_sigma_values_dev(curve_id, (int)log_n, (int)num_wire_types, reinterpret_cast<const uint32_t*>(d_next_u32),
+                                  reinterpret_cast<const uint32_t*>(k_mont), reinterpret_cast<uint32_t*>(d_out), (hipStream_t)stream);
+}
 int32_t mzk_plonk_pk_hbm_bytes(uint64_t pk_handle, uint64_t* out_bytes) {
     ENTER_HANDLE(pk_handle);
     if (!out_bytes) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }

@@ -1,13 +1,16 @@
 // plonk.hip -- host side of the device-resident TurboPlonk quotient round (plonk.cuh).
+#include <algorithm>
 #include <array>
 #include <map>
 #include <vector>
 #include <memory>
+#include <string>
 
 #include "internal.hpp"
 #include "plonk.cuh"
 #include "plookup.cuh"
 #include "check.cuh"
+#include "perm.cuh"
 
 namespace mzk {
 namespace {
@@ -82,7 +85,7 @@ __global__ __launch_bounds__(PLK_THREADS) void plonk_shifted_inverse_kernel(cons
 }
 
 template <class P>
-int32_t pk_build(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_coeffs, const uint32_t* tab_coeffs, uint64_t poly_len) {
+int32_t pk_build(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_coeffs, const uint32_t* tab_coeffs, uint64_t poly_len, hipMemcpyKind from) {
     using F = Fp<P>;
     const int log_m = pk.log_n + 3;
     const uint64_t n = 1ull << pk.log_n, m = 1ull << log_m;
@@ -92,10 +95,10 @@ int32_t pk_build(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_co
     HIP_TRY(hipMalloc((void**)&pk.d_xs, m * 32));
     HIP_TRY(hipMalloc((void**)&pk.d_inv_den, m * 32));
     HIP_TRY(hipMemsetAsync(pk.d_fixed, 0, (size_t)nfix * m * 32, st));
-    HIP_TRY(hipMemcpy2DAsync(pk.d_fixed, m * 32, sel_coeffs, poly_len * 32, poly_len * 32, pk.nsel, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpy2DAsync(pk.d_fixed + (size_t)pk.nsel * m * 8, m * 32, sig_coeffs, poly_len * 32, poly_len * 32, pk.W, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(pk.d_fixed, m * 32, sel_coeffs, poly_len * 32, poly_len * 32, pk.nsel, from, st));
+    HIP_TRY(hipMemcpy2DAsync(pk.d_fixed + (size_t)pk.nsel * m * 8, m * 32, sig_coeffs, poly_len * 32, poly_len * 32, pk.W, from, st));
     if (pk.ultra)
-        HIP_TRY(hipMemcpy2DAsync(pk.d_fixed + (size_t)(pk.nsel + pk.W) * m * 8, m * 32, tab_coeffs, poly_len * 32, poly_len * 32, 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(pk.d_fixed + (size_t)(pk.nsel + pk.W) * m * 8, m * 32, tab_coeffs, poly_len * 32, poly_len * 32, 4, from, st));
     for (int i = 0; i < 8; i++) pk.gen[i] = P::GENERATOR[i];
     // coset evaluations of the fixed polynomials, once per proving key (prover.rs:552-558, 577-584 do it per proof)
     // ... and left in the internal form x * R' the quotient kernels compute in (plonk.cuh)
@@ -146,15 +149,15 @@ int32_t pk_build(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_co
     HIP_TRY(hipMalloc((void**)&pk.d_omega_n, n * 32));
     HIP_TRY(hipMemsetAsync(pk.d_sigma_n, 0, (size_t)pk.W * n * 32, st));
     const uint64_t sl = poly_len < n ? poly_len : n;
-    HIP_TRY(hipMemcpy2DAsync(pk.d_sigma_n, n * 32, sig_coeffs, poly_len * 32, sl * 32, pk.W, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(pk.d_sigma_n, n * 32, sig_coeffs, poly_len * 32, sl * 32, pk.W, from, st));
     launch_powers<P>(st, &wn, 1, n, &pk.d_omega_n);
     HIP_TRY(hipGetLastError());
     MZK_TRY(ntt_dispatch(pk.curve, pk.d_sigma_n, sl, pk.log_n, false, nullptr, pk.W, n, st));
     if (pk.ultra) {
         HIP_TRY(hipMalloc((void**)&pk.d_tab_n, (size_t)5 * n * 32));
         HIP_TRY(hipMemsetAsync(pk.d_tab_n, 0, (size_t)5 * n * 32, st));
-        HIP_TRY(hipMemcpy2DAsync(pk.d_tab_n, n * 32, tab_coeffs, poly_len * 32, sl * 32, 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(pk.d_tab_n + (size_t)4 * n * 8, sel_coeffs + (size_t)13 * poly_len * 8, sl * 32, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(pk.d_tab_n, n * 32, tab_coeffs, poly_len * 32, sl * 32, 4, from, st));
+        HIP_TRY(hipMemcpyAsync(pk.d_tab_n + (size_t)4 * n * 8, sel_coeffs + (size_t)13 * poly_len * 8, sl * 32, from, st));
         MZK_TRY(ntt_dispatch(pk.curve, pk.d_tab_n, sl, pk.log_n, false, nullptr, 5, n, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(PLK_THREADS) void plonk_class_points_kernel(const u
 
 // proving key holding only the residue classes `pk.cls` of the quotient domain (each class = the coset h_k * H_n)
 template <class P>
-int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_coeffs, const uint32_t* tab_coeffs, uint64_t poly_len) {
+int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t* sig_coeffs, const uint32_t* tab_coeffs, uint64_t poly_len, hipMemcpyKind from) {
     using F = Fp<P>;
     const int log_m = pk.log_n + 3;
     const uint64_t n = 1ull << pk.log_n;
@@ -400,10 +403,10 @@ int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t
         const int k = pk.cls[lc];
         uint32_t* base = pk.d_fixed + lc * n * 8;
         const size_t row = ncl * n * 32;                              // bytes between consecutive polynomials
-        HIP_TRY(hipMemcpy2DAsync(base, row, sel_coeffs, poly_len * 32, sl * 32, pk.nsel, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpy2DAsync(base + (size_t)pk.nsel * ncl * n * 8, row, sig_coeffs, poly_len * 32, sl * 32, pk.W, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(base, row, sel_coeffs, poly_len * 32, sl * 32, pk.nsel, from, st));
+        HIP_TRY(hipMemcpy2DAsync(base + (size_t)pk.nsel * ncl * n * 8, row, sig_coeffs, poly_len * 32, sl * 32, pk.W, from, st));
         if (pk.ultra)
-            HIP_TRY(hipMemcpy2DAsync(base + (size_t)(pk.nsel + pk.W) * ncl * n * 8, row, tab_coeffs, poly_len * 32, sl * 32, 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpy2DAsync(base + (size_t)(pk.nsel + pk.W) * ncl * n * 8, row, tab_coeffs, poly_len * 32, sl * 32, 4, from, st));
         HIP_TRY(hipMemcpyAsync(d_c + 40, pk.h_cls[k], 32, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL((plonk_class_points_kernel<P>), dim3(tg), dim3(PLK_THREADS), 0, st, d_c, d_c + 40, n, pk.d_xs + lc * n * 8);
         hipLaunchKernelGGL((plonk_shifted_inverse_kernel<P>), dim3(tg), dim3(PLK_THREADS), 0, st, pk.d_xs + lc * n * 8, n, d_c + 16, d_c + 8,
@@ -427,7 +430,7 @@ int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t
     HIP_TRY(hipMalloc((void**)&pk.d_sigma_n, (size_t)pk.W * n * 32));
     HIP_TRY(hipMalloc((void**)&pk.d_omega_n, n * 32));
     HIP_TRY(hipMemsetAsync(pk.d_sigma_n, 0, (size_t)pk.W * n * 32, st));
-    HIP_TRY(hipMemcpy2DAsync(pk.d_sigma_n, n * 32, sig_coeffs, poly_len * 32, sl * 32, pk.W, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpy2DAsync(pk.d_sigma_n, n * 32, sig_coeffs, poly_len * 32, sl * 32, pk.W, from, st));
     launch_powers<P>(st, &wn, 1, n, &pk.d_omega_n);
     HIP_TRY(hipGetLastError());
     // class evaluations of the fixed polynomials: size-n coset NTTs with offset h_k, all polynomials of a class in one batch
@@ -437,21 +440,24 @@ int32_t pk_build_chunked(PlonkPk& pk, const uint32_t* sel_coeffs, const uint32_t
     if (pk.ultra) {
         HIP_TRY(hipMalloc((void**)&pk.d_tab_n, (size_t)5 * n * 32));
         HIP_TRY(hipMemsetAsync(pk.d_tab_n, 0, (size_t)5 * n * 32, st));
-        HIP_TRY(hipMemcpy2DAsync(pk.d_tab_n, n * 32, tab_coeffs, poly_len * 32, sl * 32, 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(pk.d_tab_n + (size_t)4 * n * 8, sel_coeffs + (size_t)13 * poly_len * 8, sl * 32, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(pk.d_tab_n, n * 32, tab_coeffs, poly_len * 32, sl * 32, 4, from, st));
+        HIP_TRY(hipMemcpyAsync(pk.d_tab_n + (size_t)4 * n * 8, sel_coeffs + (size_t)13 * poly_len * 8, sl * 32, from, st));
         MZK_TRY(ntt_dispatch(pk.curve, pk.d_tab_n, sl, pk.log_n, false, nullptr, 5, n, st));
     }
     {   // top coefficients of the fixed polynomials that reach the top of the quotient's numerator (plonk_quotient_top_kernel)
         std::vector<uint32_t> top((size_t)(pk.W + 5) * 8 * 8, 0u);
-        auto fill = [&](int row, const uint32_t* coeffs) {
-            for (int t = 0; t < 8; t++) {
-                const long long idx = (long long)n - 8 + t;
-                if (idx >= 0 && (uint64_t)idx < sl) std::memcpy(&top[((size_t)row * 8 + t) * 8], coeffs + (size_t)idx * 8, 32);
-            }
+        auto fill = [&](int row, const uint32_t* coeffs) {                    // (device-resident coefficients: 8 elements a row come back)
+            const long long first = std::max<long long>((long long)n - 8, 0);
+            if ((uint64_t)first >= sl) return hipSuccess;
+            const size_t cnt = (size_t)(sl - (uint64_t)first);
+            uint32_t* dst = &top[((size_t)row * 8 + (size_t)(first - ((long long)n - 8))) * 8];
+            if (from == hipMemcpyDeviceToDevice) return hipMemcpy(dst, coeffs + (size_t)first * 8, cnt * 32, hipMemcpyDeviceToHost);
+            std::memcpy(dst, coeffs + (size_t)first * 8, cnt * 32);
+            return hipSuccess;
         };
-        for (int j = 0; j < pk.W; j++) fill(j, sig_coeffs + (size_t)j * poly_len * 8);
-        for (int j = 0; j < 4; j++) fill(pk.W + j, sel_coeffs + (size_t)(6 + j) * poly_len * 8);
-        fill(pk.W + 4, sel_coeffs + (size_t)12 * poly_len * 8);
+        for (int j = 0; j < pk.W; j++) HIP_TRY(fill(j, sig_coeffs + (size_t)j * poly_len * 8));
+        for (int j = 0; j < 4; j++) HIP_TRY(fill(pk.W + j, sel_coeffs + (size_t)(6 + j) * poly_len * 8));
+        HIP_TRY(fill(pk.W + 4, sel_coeffs + (size_t)12 * poly_len * 8));
         HIP_TRY(hipMalloc((void**)&pk.d_top_fixed, top.size() * 4));
         HIP_TRY(hipMemcpyAsync(pk.d_top_fixed, top.data(), top.size() * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));                                // `top` leaves scope
@@ -763,6 +769,73 @@ int32_t witness_check_run(const PlonkPk& pk, const WitnessCheckIn& in, mzk_witne
     return MZK_OK;
 }
 
+// The wire permutation of a variable table (perm.cuh; include/mzk.h mzk_plonk_wire_permutation_dev).  Scratch: the context's shared
+// buffers (sorted: two key / cell array pairs the passes alternate between; hist: [256][blocks] digit counts; misc: the validation's
+// two words).  Synchronises: the validation result is read back.
+int32_t wire_permutation_run(const uint32_t* d_vars, uint64_t cells, uint64_t n_vars, uint32_t* d_next, hipStream_t st) {
+    static_assert(PERM_THREADS == PERM_RADIX, "perm.cuh: thread t of a block owns digit t");
+    if (cells == 0) return MZK_OK;
+    int passes = 0;
+    for (uint64_t x = std::min<uint64_t>(n_vars - 1, 0xFFFFFFFFull); x; x >>= 8) passes++;
+    const uint64_t tiles = (cells + PERM_THREADS - 1) / PERM_THREADS;
+    const uint64_t want = std::min<uint64_t>(tiles, PERM_MAX_BLOCKS);
+    const uint64_t chunk = (tiles + want - 1) / want * PERM_THREADS;
+    const unsigned blocks = (unsigned)((cells + chunk - 1) / chunk);
+    ProfScope total("wire_permutation", st);
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->sorted.reserve(cells * 16));
+    MZK_TRY(ws->hist.reserve((size_t)PERM_RADIX * blocks * 4));
+    MZK_TRY(ws->misc.reserve(512));
+    uint32_t* buf[2][2];
+    for (int i = 0; i < 4; i++) buf[i >> 1][i & 1] = ws->sorted.as<uint32_t>() + (size_t)i * cells;
+    uint32_t* d_res = ws->misc.as<uint32_t>();
+    const unsigned grid = (unsigned)tiles;
+    HIP_TRY(hipMemsetAsync(d_res, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(d_res + 1, 0xFF, 4, st));
+    hipLaunchKernelGGL(perm_validate_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, d_vars, (unsigned long long)cells, (unsigned long long)n_vars, d_res);
+    const uint32_t *keys = d_vars, *cell_of = nullptr;
+    for (int i = 0; i < passes; i++) {
+        PermPass a{keys, cell_of, buf[i & 1][0], buf[i & 1][1], ws->hist.as<uint32_t>(), cells, chunk, blocks, (unsigned)(8 * i)};
+        hipLaunchKernelGGL(perm_hist_kernel, dim3(blocks), dim3(PERM_THREADS), 0, st, a);
+        hipLaunchKernelGGL(perm_scan_kernel, dim3(1), dim3(1024), 0, st, a.hist, (unsigned)(PERM_RADIX * blocks));
+        hipLaunchKernelGGL(perm_scatter_kernel, dim3(blocks), dim3(PERM_THREADS), 0, st, a);
+        keys = a.keys_out; cell_of = a.cells_out;
+    }
+    hipLaunchKernelGGL(perm_link_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, keys, cell_of, (unsigned long long)cells, d_next);
+    HIP_TRY(hipGetLastError());
+    uint32_t res[2];
+    HIP_TRY(hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (res[0]) {
+        uint32_t v = 0;
+        HIP_TRY(hipMemcpy(&v, d_vars + res[1], 4, hipMemcpyDeviceToHost));
+        set_error("wire_variables: cell " + std::to_string(res[1]) + " holds variable index " + std::to_string(v) + " >= number of variables " +
+                  std::to_string(n_vars) + " (" + std::to_string(res[0]) + " such cells)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return MZK_OK;
+}
+
+// sigma values from the permutation (perm.cuh perm_sigma_kernel); scratch: the n powers of w in poly_tmp.  Asynchronous.
+template <class P>
+int32_t sigma_values_run(int log_n, int W, const uint32_t* d_next, const uint32_t* k_mont, uint32_t* d_out, hipStream_t st) {
+    using F = Fp<P>;
+    const uint64_t n = 1ull << log_n, cells = (uint64_t)W * n;
+    F wn = F::from_const(P::ROOT);
+    for (int i = log_n; i < P::TWO_ADICITY; i++) wn = sqr(wn);
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->poly_tmp.reserve(n * 32));
+    uint32_t* d_omega = ws->poly_tmp.as<uint32_t>();
+    launch_powers<P>(st, &wn, 1, n, &d_omega);
+    SigmaArgs a;
+    a.next = d_next; a.omega = d_omega; a.out = d_out; a.cells = cells; a.log_n = (unsigned)log_n;
+    std::memset(a.k, 0, sizeof a.k);
+    std::memcpy(a.k, k_mont, (size_t)W * 32);
+    hipLaunchKernelGGL((perm_sigma_kernel<P>), dim3((unsigned)((cells + PERM_THREADS - 1) / PERM_THREADS)), dim3(PERM_THREADS), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return MZK_OK;
+}
+
 // frees a key's device buffers (called explicitly: a registry-held key has no freeing destructor)
 void pk_free(PlonkPk& pk) {
     for (auto* d : pk.bufs()) if (d) (void)hipFree(d);
@@ -776,7 +849,7 @@ const PlonkPk* find_pk(uint64_t handle) {
 }  // namespace
 
 int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, const uint32_t* sig, const uint32_t* tab, uint64_t poly_len,
-                          const uint32_t* k_mont, const uint32_t* classes, uint32_t n_classes, uint64_t* out_handle) {
+                          const uint32_t* k_mont, const uint32_t* classes, uint32_t n_classes, uint64_t* out_handle, bool coeffs_on_device) {
     const bool ultra = tab != nullptr;
     if (classes) {
         bool ok = n_classes >= 1 && n_classes <= PLK_RATIO && poly_len <= (1ull << log_n);
@@ -792,7 +865,16 @@ int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, cons
     pk->curve = curve; pk->log_n = log_n; pk->W = W; pk->ultra = ultra; pk->nsel = PLK_SELECTORS + (ultra ? 1 : 0);
     std::memset(pk->k, 0, sizeof pk->k);
     std::memcpy(pk->k, k_mont, (size_t)W * 32);
-    {   // selectors that are the zero polynomial: their gate terms are skipped (plonk.cuh)
+    const hipMemcpyKind from = coeffs_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (coeffs_on_device) {   // the same flags from the device: the length up to the highest non-zero coefficient of each selector, 13 words back
+        WsHold ws; MZK_TRY(ws.acquire(nullptr));
+        MZK_TRY(ws->misc.reserve(512));
+        unsigned long long* d_len = ws->misc.as<unsigned long long>();
+        unsigned long long len[PLK_SELECTORS];
+        for (int j = 0; j < PLK_SELECTORS; j++) MZK_TRY(poly_degree_dispatch(sel + (size_t)j * poly_len * 8, poly_len, d_len + j, nullptr));
+        HIP_TRY(hipMemcpy(len, d_len, sizeof len, hipMemcpyDeviceToHost));
+        for (int j = 0; j < PLK_SELECTORS; j++) if (len[j] == 0) pk->sel_zero |= 1u << j;
+    } else {   // selectors that are the zero polynomial: their gate terms are skipped (plonk.cuh)
         const uint64_t words = poly_len * 8;
         for (int j = 0; j < PLK_SELECTORS; j++) {
             const uint32_t* c = sel + (size_t)j * words;
@@ -804,9 +886,9 @@ int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, cons
     int32_t rc;
     if (classes) {
         pk->cls.assign(classes, classes + n_classes);
-        rc = curve == 0 ? pk_build_chunked<BlsFr>(*pk, sel, sig, tab, poly_len) : pk_build_chunked<BnFr>(*pk, sel, sig, tab, poly_len);
+        rc = curve == 0 ? pk_build_chunked<BlsFr>(*pk, sel, sig, tab, poly_len, from) : pk_build_chunked<BnFr>(*pk, sel, sig, tab, poly_len, from);
     } else {
-        rc = curve == 0 ? pk_build<BlsFr>(*pk, sel, sig, tab, poly_len) : pk_build<BnFr>(*pk, sel, sig, tab, poly_len);
+        rc = curve == 0 ? pk_build<BlsFr>(*pk, sel, sig, tab, poly_len, from) : pk_build<BnFr>(*pk, sel, sig, tab, poly_len, from);
     }
     if (rc != MZK_OK) {
         pk_free(*pk);
@@ -877,6 +959,19 @@ int32_t plookup_product_dev(uint64_t handle, const uint32_t* d_table, const uint
     }
     return pk->curve == 0 ? lookup_product_run<BlsFr>(*pk, d_table, d_lookup, d_sorted, beta, gamma, d_out, st)
                           : lookup_product_run<BnFr>(*pk, d_table, d_lookup, d_sorted, beta, gamma, d_out, st);
+}
+int32_t plonk_wire_permutation_dev(const uint32_t* d_vars, uint64_t cells, uint64_t n_vars, uint32_t* d_next, hipStream_t st) {
+    if (cells >= (1ull << 32)) { set_error("wire permutation: the number of cells must be below 2^32"); return MZK_ERR_UNSUPPORTED; }
+    if ((cells && (!d_vars || !d_next)) || n_vars == 0) { set_error("bad argument (null pointer, or no variables)"); return MZK_ERR_INVALID_ARG; }
+    return wire_permutation_run(d_vars, cells, n_vars, d_next, st);
+}
+int32_t plonk_sigma_values_dev(int curve, int log_n, int W, const uint32_t* d_next, const uint32_t* k_mont, uint32_t* d_out, hipStream_t st) {
+    if (!valid_curve(curve) || (W != PLK_WIRES && W != PLK_MAX_WIRES) || log_n < 0 || log_n > (curve == 0 ? 32 : 28) || ((uint64_t)W << log_n) >= (1ull << 32) ||
+        !d_next || !k_mont || !d_out) {
+        set_error("bad argument (5 or 6 wire types, num_wire_types * 2^log_n below 2^32)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return curve == 0 ? sigma_values_run<BlsFr>(log_n, W, d_next, k_mont, d_out, st) : sigma_values_run<BnFr>(log_n, W, d_next, k_mont, d_out, st);
 }
 int32_t plonk_check_witness_dev(uint64_t handle, const WitnessCheckIn& in, mzk_witness_report* out, hipStream_t st) {
     const PlonkPk* pk = find_pk(handle);

@@ -78,6 +78,8 @@ inline std::vector<uint32_t> class_range(int rank, int world, uint32_t n_classes
 enum PlookupEval { RANGE_TABLE, KEY_TABLE, TABLE_DOM_SEP, Q_DOM_SEP, H_1, Q_LOOKUP, PROD_NEXT, RANGE_TABLE_NEXT, KEY_TABLE_NEXT, TABLE_DOM_SEP_NEXT,
                    H_1_NEXT, H_2_NEXT, Q_LOOKUP_NEXT, W_3_NEXT, W_4_NEXT, N_PLOOKUP_EVALS };
 
+enum CoeffsAt { COEFFS_ON_HOST = 0, COEFFS_ON_DEVICE = 1 };            // where a constructor finds the key's coefficient forms
+
 enum Stage { CREATED = 0, R1 = 10, R1_5 = 15, R2 = 20, R2_5 = 25, R3 = 30, R4 = 40 };
 
 struct ProverBase {
@@ -96,6 +98,7 @@ struct ProverBase {
     virtual ~ProverBase() {}
     virtual void vk_commitments(uint64_t* out_xy, uint64_t* out_plookup_xy) = 0;
     virtual void set_wire_variables(const uint32_t* vars, uint64_t n_vars) = 0;
+    virtual void take_wire_variables(Buf& d_vars, uint64_t n_vars) = 0;
     virtual void round1(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
                         const uint64_t* blinders, uint64_t* out) = 0;
     virtual void check_witness(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
@@ -177,7 +180,7 @@ struct ProverT final : ProverBase {
     static Fr load(const uint64_t* p) { Fr v; std::memcpy(v.l, p, EL); return v; }
 
     ProverT(int log_n_, int W_, const uint64_t* sel, const uint64_t* sig, const uint64_t* tab, uint64_t poly_len, const uint64_t* k_mont,
-        uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* cm);   // prover_setup.inc
+        uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* cm, CoeffsAt at);   // prover_setup.inc
     ~ProverT() override;   // prover_setup.inc
     void hbm_bytes(uint64_t* fixed_b, uint64_t* pk_b, uint64_t* ws_b) override;   // prover_setup.inc
 
@@ -260,6 +263,7 @@ struct ProverT final : ProverBase {
 
     // ---- round 1 (prover.rs:72-87; constraint_system.rs:1225-1259) -------------------------------------------------------------
     void set_wire_variables(const uint32_t* v, uint64_t nv) override;   // prover_setup.inc
+    void take_wire_variables(Buf& d_vars, uint64_t nv) override;   // prover_setup.inc
     void public_input_row(const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi);   // prover_round1.inc
     void round1(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
         const uint64_t* blinders, uint64_t* out) override;   // prover_round1.inc
@@ -365,6 +369,74 @@ int32_t collect(const uint64_t* handles, uint32_t cnt, std::vector<std::shared_p
     return MZK_OK;
 }
 
+// argument checks shared by the ways a prover comes into being
+int32_t create_args_ok(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, bool pointers_ok, const void* tab) {
+    if ((curve_id != 0 && curve_id != 1) || (num_wire_types != 5 && num_wire_types != 6) || !pointers_ok || (num_wire_types == 6) != (tab != nullptr) || log_n < 1 ||
+        log_n > 27) {
+        set_error("bad argument (TurboPlonk: 5 wire types, 13 selectors; UltraPlonk: 6 wire types, 14 selectors, 4 table polynomials; coefficient vectors of at most 2^log_n)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    // the quotient lives on the 8n-point domain: its W (n + 1) + 3 coefficients (prover.rs:916-919) must fit below 8n.  The reference sizes
+    // that domain from the degree (n = 2 with five or six wire types and n = 4 with six would take 16n); such domains are refused here
+    if ((uint64_t)num_wire_types * ((1ull << log_n) + 1) + 2 >= (8ull << log_n)) {
+        set_error("domain too small for the 8n-point quotient domain: need num_wire_types * (n + 1) + 2 < 8 n (n >= 4 for TurboPlonk, n >= 8 for UltraPlonk)");
+        return MZK_ERR_UNSUPPORTED;
+    }
+    return MZK_OK;
+}
+// (throws Fail / std::bad_alloc)
+std::shared_ptr<ProverBase> make_prover(int32_t curve_id, uint32_t log_n, uint32_t W, const uint64_t* sel, const uint64_t* sig, const uint64_t* tab, uint64_t poly_len,
+                                        const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, CoeffsAt at) {
+    if (curve_id == 0) return std::make_shared<ProverT<BlsFr, MZK_CURVE_BLS12_381>>((int)log_n, (int)W, sel, sig, tab, poly_len, k_mont, commit_key, lagrange_key, comm, at);
+    return std::make_shared<ProverT<BnFr, MZK_CURVE_BN254>>((int)log_n, (int)W, sel, sig, tab, poly_len, k_mont, commit_key, lagrange_key, comm, at);
+}
+uint64_t publish(std::shared_ptr<ProverBase> p, int32_t device) {
+    p->device = device;
+    const uint64_t h = handle_make(device, g_next_prover++);
+    std::lock_guard<std::mutex> lk(g_reg_lock);
+    g_provers[h] = std::move(p);
+    return h;
+}
+
+// PlonkKzgSnark::preprocess from the arrays a finalised circuit holds (snark.rs:529-617): selector (and table) VALUES on the gate domain
+// and the variable table, host or device.  Wire permutation -> sigma values -> ONE batched inverse NTT over all nsel + W (+ 4) rows ->
+// the constructor every prover goes through, reading the coefficient forms where they are: in device memory.
+int32_t create_from_circuit(bool on_device, int32_t curve_id, uint32_t log_n, uint32_t W, const void* sel_values, const void* wire_variables, uint64_t n_vars,
+                            const void* table_values, const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, uint64_t* out_prover) {
+    MZK_TRY(create_args_ok(curve_id, log_n, W, sel_values && wire_variables && k_mont && out_prover, table_values));
+    if (n_vars == 0 || n_vars >= (1ull << 32)) { set_error("bad argument (1 <= n_vars < 2^32)"); return MZK_ERR_INVALID_ARG; }
+    int32_t device = -1;
+    MZK_TRY(mzk_get_device(&device));
+    if (device < 0) { set_error("mzk_init has not been called"); return MZK_ERR_NOT_INIT; }
+    const uint64_t n = 1ull << log_n, cells = (uint64_t)W * n;
+    const int nsel = W == 6 ? 14 : 13, nfix = nsel + (int)W + (W == 6 ? 4 : 0);
+    try {
+        Buf coeffs, vars, next;
+        coeffs.alloc((size_t)nfix * n);
+        vars.alloc((cells * 4 + EL - 1) / EL);                         // (sized as set_wire_variables sizes it)
+        next.alloc((cells * 4 + EL - 1) / EL);
+        auto bring = [&](void* dst, const void* src, uint64_t bytes) { ck(on_device ? mzk_dev_copy(dst, src, bytes, nullptr) : mzk_dev_upload(dst, src, bytes)); };
+        bring(coeffs.p, sel_values, (uint64_t)nsel * n * EL);
+        if (W == 6) bring(coeffs.at((size_t)(nsel + W) * n), table_values, 4 * n * EL);
+        bring(vars.p, wire_variables, cells * 4);
+        ck(mzk_plonk_wire_permutation_dev(vars.p, cells, n_vars, next.p, nullptr));         // validates the table
+        ck(mzk_plonk_sigma_values_dev(curve_id, log_n, W, next.p, k_mont, coeffs.at((size_t)nsel * n), nullptr));
+        ck(mzk_ntt_dev(curve_id, coeffs.p, n, log_n, 1, nullptr, (uint32_t)nfix, n, nullptr));
+        ck(mzk_dev_sync());
+        const uint64_t* c = static_cast<const uint64_t*>(coeffs.p);
+        auto p = make_prover(curve_id, log_n, W, c, c + (size_t)nsel * n * 4, W == 6 ? c + (size_t)(nsel + W) * n * 4 : nullptr, n, k_mont, commit_key, lagrange_key,
+                             comm, COEFFS_ON_DEVICE);
+        p->take_wire_variables(vars, n_vars);
+        *out_prover = publish(std::move(p), device);
+    } catch (const Fail& e) {
+        return e.rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return MZK_ERR_OOM;
+    }
+    return MZK_OK;
+}
+
 }  // namespace
 }  // namespace mzk
 
@@ -375,36 +447,33 @@ extern "C" {
 int32_t mzk_prover_create(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const uint64_t* selector_coeffs, const uint64_t* sigma_coeffs,
                           const uint64_t* table_coeffs, uint64_t poly_len, const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key,
                           const mzk_comm* comm, uint64_t* out_prover) {
-    if ((curve_id != 0 && curve_id != 1) || (num_wire_types != 5 && num_wire_types != 6) || !selector_coeffs || !sigma_coeffs || !k_mont || !out_prover ||
-        (num_wire_types == 6) != (table_coeffs != nullptr) || log_n < 1 || log_n > 27 || poly_len == 0 || poly_len > (1ull << log_n)) {
-        set_error("bad argument (TurboPlonk: 5 wire types, 13 selectors; UltraPlonk: 6 wire types, 14 selectors, 4 table polynomials; coefficient vectors of at most 2^log_n)");
-        return MZK_ERR_INVALID_ARG;
-    }
-    // the quotient lives on the 8n-point domain: its W (n + 1) + 3 coefficients (prover.rs:916-919) must fit below 8n.  The reference sizes
-    // that domain from the degree (n = 2 with five or six wire types and n = 4 with six would take 16n); such domains are refused here
-    if ((uint64_t)num_wire_types * ((1ull << log_n) + 1) + 2 >= (8ull << log_n)) {
-        set_error("domain too small for the 8n-point quotient domain: need num_wire_types * (n + 1) + 2 < 8 n (n >= 4 for TurboPlonk, n >= 8 for UltraPlonk)");
-        return MZK_ERR_UNSUPPORTED;
-    }
+    const bool len_ok = poly_len != 0 && (log_n > 27 || poly_len <= (1ull << log_n));
+    MZK_TRY(create_args_ok(curve_id, log_n, num_wire_types, selector_coeffs && sigma_coeffs && k_mont && out_prover && len_ok, table_coeffs));
     int32_t device = -1;
     MZK_TRY(mzk_get_device(&device));
     if (device < 0) { set_error("mzk_init has not been called"); return MZK_ERR_NOT_INIT; }
-    std::shared_ptr<ProverBase> p;
     try {
-        if (curve_id == 0) p = std::make_shared<ProverT<BlsFr, MZK_CURVE_BLS12_381>>((int)log_n, (int)num_wire_types, selector_coeffs, sigma_coeffs, table_coeffs, poly_len, k_mont, commit_key, lagrange_key, comm);
-        else p = std::make_shared<ProverT<BnFr, MZK_CURVE_BN254>>((int)log_n, (int)num_wire_types, selector_coeffs, sigma_coeffs, table_coeffs, poly_len, k_mont, commit_key, lagrange_key, comm);
+        *out_prover = publish(make_prover(curve_id, log_n, num_wire_types, selector_coeffs, sigma_coeffs, table_coeffs, poly_len, k_mont, commit_key, lagrange_key,
+                                          comm, COEFFS_ON_HOST), device);
     } catch (const Fail& e) {
         return e.rc;
     } catch (const std::bad_alloc&) {
         set_error("out of host memory");
         return MZK_ERR_OOM;
     }
-    p->device = device;
-    const uint64_t h = handle_make(device, g_next_prover++);
-    std::lock_guard<std::mutex> lk(g_reg_lock);
-    g_provers[h] = std::move(p);
-    *out_prover = h;
     return MZK_OK;
+}
+int32_t mzk_prover_create_from_circuit(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const uint64_t* selector_values, const uint32_t* wire_variables,
+                                       uint64_t n_vars, const uint64_t* table_values, const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key,
+                                       const mzk_comm* comm, uint64_t* out_prover) {
+    return create_from_circuit(false, curve_id, log_n, num_wire_types, selector_values, wire_variables, n_vars, table_values, k_mont, commit_key, lagrange_key, comm,
+                               out_prover);
+}
+int32_t mzk_prover_create_from_circuit_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_selector_values, const void* d_wire_variables,
+                                           uint64_t n_vars, const void* d_table_values, const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key,
+                                           const mzk_comm* comm, uint64_t* out_prover) {
+    return create_from_circuit(true, curve_id, log_n, num_wire_types, d_selector_values, d_wire_variables, n_vars, d_table_values, k_mont, commit_key, lagrange_key, comm,
+                               out_prover);
 }
 
 int32_t mzk_prover_destroy(uint64_t prover) {

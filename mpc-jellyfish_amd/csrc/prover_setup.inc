@@ -6,7 +6,7 @@
 // PlonkKzgSnark::preprocess's device half (snark.rs:529-617): coefficient forms resident, evaluations on the needed classes
 template <class FrP, int CURVE>
 ProverT<FrP, CURVE>::ProverT(int log_n_, int W_, const uint64_t* sel, const uint64_t* sig, const uint64_t* tab, uint64_t poly_len,
-        const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* cm) {
+        const uint64_t* k_mont, uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* cm, CoeffsAt at) {
     curve = CURVE; log_n = log_n_; W = W_; ultra = W_ == 6; nsel = ultra ? 14 : 13;
     rows = W + 2 + (ultra ? 3 : 0);
     n = 1ull << log_n; m = 8 * n;
@@ -37,12 +37,14 @@ ProverT<FrP, CURVE>::ProverT(int log_n_, int W_, const uint64_t* sel, const uint
     ck(mzk_dev_memset(fixed.p, 0, (size_t)nfix * n * EL, S));
     sync_stream();                                                 // the uploads below are synchronous copies, not ordered after S
     auto up_rows = [&](int first, int cnt, const uint64_t* src) {
-        if (poly_len == n) ck(mzk_dev_upload(fix(first), src, (size_t)cnt * n * EL));
+        if (at == COEFFS_ON_DEVICE) ck(mzk_dev_copy2d(fix(first), n * EL, src, poly_len * EL, poly_len * EL, (uint64_t)cnt, S));   // (complete before the call: mzk_prover_create_from_circuit)
+        else if (poly_len == n) ck(mzk_dev_upload(fix(first), src, (size_t)cnt * n * EL));
         else for (int i = 0; i < cnt; i++) ck(mzk_dev_upload(fix(first + i), src + (size_t)i * poly_len * 4, poly_len * EL));
     };
     up_rows(0, nsel, sel);
     up_rows(nsel, W, sig);
     if (ultra) up_rows(nsel + W, 4, tab);
+    if (at == COEFFS_ON_DEVICE) sync_stream();
     // The quotient has degree W (n + 1) + 2 (prover.rs:916-919).  Its W + 3 coefficients from X^(Wn) on are the top coefficients of
     // its numerator (mzk_plonk_quotient_top_dev, n > W + 2), so W of the 8 residue classes of the quotient domain determine the
     // rest -- 5 for TurboPlonk, 6 for UltraPlonk -- and only those are resident and evaluated; the polynomial so recovered has the
@@ -60,7 +62,7 @@ ProverT<FrP, CURVE>::ProverT(int log_n_, int W_, const uint64_t* sel, const uint
     split.alloc((size_t)W * (n + 3)); lin.alloc(n + 4); batch.alloc(n + 4); opening.alloc(n + 3); shifted.alloc(n + 3); tmp.alloc(64); deg.alloc(1);
     if (ultra) { hh.alloc(2 * n); table.alloc(n); lookup.alloc(n); sorted.alloc(2 * n); }
     // (last: a constructor that throws runs no destructor, and the key is the one resource the members do not release themselves)
-    ck(mzk_plonk_pk_register_chunked(CURVE, log_n, W, sel, sig, tab, poly_len, k_mont, resident.data(), (uint32_t)resident.size(), &pk));
+    ck(mzk_ctx_pk_register_chunked(CURVE, log_n, W, sel, sig, tab, poly_len, k_mont, resident.data(), (uint32_t)resident.size(), at == COEFFS_ON_DEVICE, &pk));
     w_n = root_of_unity<FrP>(log_n);
     gen = Fr::from_words(FrP::GENERATOR);
 }
@@ -200,6 +202,14 @@ void ProverT<FrP, CURVE>::set_wire_variables(const uint32_t* v, uint64_t nv) {
         if (v[i] >= nv) fail(MZK_ERR_INVALID_ARG, "wire_variables: variable index " + std::to_string(v[i]) + " >= number of variables " + std::to_string(nv));
     vars.alloc((cnt * 4 + EL - 1) / EL);
     ck(mzk_dev_upload(vars.p, v, cnt * 4));
+    n_vars = nv;
+}
+
+// the same table, resident already and validated where it was sorted (mzk_prover_create_from_circuit): the buffer changes hands
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::take_wire_variables(Buf& d_vars, uint64_t nv) {
+    std::swap(vars.p, d_vars.p);
+    std::swap(vars.elems, d_vars.elems);
     n_vars = nv;
 }
 

@@ -35,6 +35,8 @@ struct Options {
     bool check_agree = false;     // --check-agree: every rank's proof bytes are compared (tests)
     const char* srs_path = nullptr;  // --srs FILE: the commit key from a serialized setup
     bool slice_srs = true;        // --no-slice: with --gpus G every rank keeps the whole commit key (and its table) instead of its point range
+    bool device_preprocess = false;  // --device-preprocess: the proving key from the circuit's selector values and variable table, permutation and
+                                  // sigma values on the device (mzk_prover_create_from_circuit_dev) -- same key, same bytes; bench circuits only
     bool check_witness = false;   // --check-witness: say where the witness fails before proving; exit status 3 if it does
     int lagrange = -1;            // round 1 commits the wires from their VALUES over the Lagrange-basis key derived from the SRS (same proof
                                   // bytes): -1 = from 2^18 gates on (below, the heavy-bucket paths of small scalars cost more than they save: 2^15 gates 3.93 against 3.73 ms) when a sample of the witness
@@ -47,7 +49,7 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     using Fr = Fp64<typename C::Fr>;
     if (opt.gpus == 1) check(mzk_init(-1), "mzk_init");                  // (with several devices each worker thread binds its own)
     auto t0 = std::chrono::steady_clock::now();
-    BenchCircuitHost<C> host = circuit_file ? BenchCircuitHost<C>::read(circuit_file) : BenchCircuitHost<C>::generate(num_gates, ultra, range_bits);
+    BenchCircuitHost<C> host = circuit_file ? BenchCircuitHost<C>::read(circuit_file) : BenchCircuitHost<C>::generate(num_gates, ultra, range_bits, !opt.device_preprocess);
     ultra = host.ultra;
     if (std::getenv("MZK_PROVE_CORRUPT_WITNESS"))                       // test hook: wire 0 of row 5 takes the value of row 6 -> gate 5 no longer holds
     {
@@ -62,7 +64,7 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     double circuit_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     t0 = std::chrono::steady_clock::now();
     const bool lagrange = opt.lagrange < 0 ? (host.log_n >= 18 && host.witness_is_small()) : opt.lagrange != 0;
-    sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr);                           // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
+    sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr, opt.device_preprocess);    // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
     const double preprocess_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (opt.check_witness) {
         const mzk_witness_report rep = sp.check_witness();
@@ -201,6 +203,7 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--host-witness-vars") opt.host_witness = 2;
         else if (a == "--check-agree") opt.check_agree = true;
         else if (a == "--check-witness") opt.check_witness = true;
+        else if (a == "--device-preprocess") opt.device_preprocess = true;
         else if (a == "--lagrange") opt.lagrange = 1;
         else if (a == "--no-lagrange") opt.lagrange = 0;
         else if (a == "--no-slice") opt.slice_srs = false;
@@ -210,8 +213,13 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     if (opt.gpus < 1 || opt.gpus > 16) { std::fprintf(stderr, "mzk_prove: --gpus 1..16\n"); return 2; }
-    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--device-preprocess] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
     const int curve = std::atoi(argv[1]);
+    if (opt.device_preprocess && (std::string(argv[2]) == "file" || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
+        std::fprintf(stderr, "mzk_prove: --device-preprocess needs the circuit's variable table: a circuit file holds sigma values, not variables "
+                             "(bench circuits only: <turbo|ultra> <num_gates>)\n");
+        return 2;
+    }
     if (std::string(argv[2]) == "link") {
         if (argc < 8) { std::fprintf(stderr, "usage: %s <curve 0|1> link <num_gates_1> <num_gates_2> <alignment> <offset> <size> [reps]\n", argv[0]); return 2; }
         const GroupLayout layout{(uint32_t)std::atoi(argv[5]), std::strtoull(argv[6], nullptr, 10), std::strtoull(argv[7], nullptr, 10)};

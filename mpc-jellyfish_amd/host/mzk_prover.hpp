@@ -158,7 +158,9 @@ struct BenchCircuitHost {                                              // the fi
     }
 
     // plonk/benches/bench.rs:29-46 through PlonkCircuit::new, Circuit::add and finalize_for_arithmetization
-    static BenchCircuitHost generate(uint64_t num_gates, bool ultra, int range_bit_len = 8) {
+    // with_sigma = false: the circuit as finalisation leaves it -- selector values and the variable table; the permutation and the sigma
+    // values are left to the device (mzk_prover_create_from_circuit_dev)
+    static BenchCircuitHost generate(uint64_t num_gates, bool ultra, int range_bit_len = 8, bool with_sigma = true) {
         BenchCircuitHost cs;
         cs.ultra = ultra;
         cs.W = ultra ? 6 : 5;
@@ -195,6 +197,13 @@ struct BenchCircuitHost {                                              // the fi
         for (uint64_t row = 2; row < 2 + n_add; row++) sel[0 * n + row] = sel[1 * n + row] = one;
         for (uint64_t row = 0; row < 2 + n_add; row++) sel[10 * n + row] = one;
         sel[11 * n + 1] = one;
+        cs.k = compute_coset_representatives<typename C::Fr>(W, n);
+        if (ultra) {
+            cs.tables.assign((size_t)4 * n, Fr::zero());
+            Fr v = Fr::zero();
+            for (uint64_t i = 0; i < (1ull << range_bit_len); i++) { cs.tables[i] = v; v = v + one; }   // compute_range_table (:1423-1438)
+        }
+        if (!with_sigma) return cs;
         // wire permutation (constraint_system.rs:743-778): the occurrences of a variable, in (wire, row) order, form a cycle
         std::vector<uint32_t> cnt(n_vars + 1, 0);
         for (uint32_t v : var) cnt[v + 1]++;
@@ -205,7 +214,6 @@ struct BenchCircuitHost {                                              // the fi
         for (size_t v = 0; v < n_vars; v++)
             for (uint32_t i = cnt[v]; i < cnt[v + 1]; i++) perm[cells[i]] = cells[i + 1 < cnt[v + 1] ? i + 1 : cnt[v]];
         // extended identity k_i * w^j (:913-931) and sigma = id o perm
-        cs.k = compute_coset_representatives<typename C::Fr>(W, n);
         const Fr w = root_of_unity<typename C::Fr>(cs.log_n);
         std::vector<Fr> ext((size_t)W * n);
         Fr cur = Fr::one();
@@ -214,11 +222,6 @@ struct BenchCircuitHost {                                              // the fi
             for (uint64_t j = 0; j < n; j++) ext[(size_t)i * n + j] = cs.k[i] * ext[j];
         cs.sigmas.resize((size_t)W * n);
         for (size_t i = 0; i < cs.sigmas.size(); i++) cs.sigmas[i] = ext[perm[i]];
-        if (ultra) {
-            cs.tables.assign((size_t)4 * n, Fr::zero());
-            Fr v = Fr::zero();
-            for (uint64_t i = 0; i < (1ull << range_bit_len); i++) { cs.tables[i] = v; v = v + one; }   // compute_range_table (:1423-1438)
-        }
         return cs;
     }
 };
@@ -238,10 +241,12 @@ struct BenchCircuit {                                                  // ... an
     std::vector<uint32_t> host_wire_variables;                         // W x n: handed to the prover once (mzk_prover_set_wire_variables)
     uint64_t n_vars = 0;
     int host_witness = 0;
+    DevBuf wire_variables;                                             // W x n u32, with device_preprocess: the key comes from it and the selector values
+    bool device_preprocess = false;
     std::vector<Fr> pub_input;
     std::vector<uint64_t> pub_rows;
 
-    static BenchCircuit upload(const BenchCircuitHost<C>& h, int host_witness = 0) {
+    static BenchCircuit upload(const BenchCircuitHost<C>& h, int host_witness = 0, bool device_preprocess = false) {
         BenchCircuit cs;
         cs.ultra = h.ultra; cs.log_n = h.log_n; cs.W = h.W; cs.nsel = h.nsel; cs.n = h.n; cs.k = h.k;
         cs.pub_input = h.pub_input; cs.pub_rows = h.pub_rows;
@@ -251,7 +256,15 @@ struct BenchCircuit {                                                  // ... an
         };
         up(cs.wire_values, h.wires, "upload wires");
         up(cs.selector_values, h.selectors, "upload selectors");
-        up(cs.sigma_values, h.sigmas, "upload sigma");
+        cs.device_preprocess = device_preprocess;
+        if (device_preprocess) {
+            if (h.wire_variables.empty()) throw std::runtime_error("this circuit carries no wire variables: the key cannot come from its structure");
+            cs.n_vars = h.witness.size();
+            cs.wire_variables.alloc((h.wire_variables.size() * 4 + EL - 1) / EL);
+            check(mzk_dev_upload(cs.wire_variables.p, h.wire_variables.data(), h.wire_variables.size() * 4), "upload wire variables");
+        } else {
+            up(cs.sigma_values, h.sigmas, "upload sigma");
+        }
         if (h.ultra) up(cs.table_values, h.tables, "upload tables");
         cs.host_witness = host_witness;
         if (host_witness == 1) {
@@ -338,6 +351,24 @@ struct Prover {
     // lagrange_key: a handle from mzk_srs_lagrange_from_srs (0: round 1 commits the masked coefficient forms, as the reference does).
     Prover(uint64_t srs_handle, const BenchCircuit<C>& cs, uint64_t lagrange_key = 0, const mzk_comm* comm = nullptr)
         : ultra(cs.ultra), log_n(cs.log_n), W(cs.W), nsel(cs.nsel), n(cs.n), k(cs.k), srs(srs_handle) {
+        std::vector<uint64_t> kk((size_t)W * 4);
+        for (int i = 0; i < W; i++) std::memcpy(&kk[4 * i], k[i].l, 32);
+        if (cs.device_preprocess) create_from_structure(cs, kk, lagrange_key, comm);
+        else create_from_values(cs, kk, lagrange_key, comm);
+        std::vector<uint64_t> xy((size_t)(nsel + W) * 2 * QL);
+        check(mzk_prover_vk_commitments(handle, xy.data(), nullptr), "mzk_prover_vk_commitments");
+        auto pt = [&](size_t i) { Affine a; std::memcpy(a.data(), &xy[i * 2 * QL], sizeof(Affine)); return a; };
+        for (int i = 0; i < nsel; i++) selector_comms.push_back(pt(i));
+        for (int i = 0; i < W; i++) sigma_comms.push_back(pt(nsel + i));
+        if (cs.host_witness == 2 && !cs.device_preprocess)
+            check(mzk_prover_set_wire_variables(handle, cs.host_wire_variables.data(), cs.n_vars), "mzk_prover_set_wire_variables");
+    }
+    // permutation, sigma values, the inverse NTTs and the key inside the library, from the resident selector values and variable table
+    void create_from_structure(const BenchCircuit<C>& cs, const std::vector<uint64_t>& kk, uint64_t lagrange_key, const mzk_comm* comm) {
+        check(mzk_prover_create_from_circuit_dev(C::ID, log_n, W, cs.selector_values.p, cs.wire_variables.p, cs.n_vars, ultra ? cs.table_values.p : nullptr, kk.data(),
+                                                 srs, lagrange_key, comm, &handle), "mzk_prover_create_from_circuit_dev");
+    }
+    void create_from_values(const BenchCircuit<C>& cs, const std::vector<uint64_t>& kk, uint64_t lagrange_key, const mzk_comm* comm) {
         const int nfix = nsel + W + (ultra ? 4 : 0);
         DevBuf fixed((size_t)nfix * n);
         check(mzk_dev_copy(fixed.p, cs.selector_values.p, (size_t)nsel * n * EL, nullptr), "copy");
@@ -346,17 +377,9 @@ struct Prover {
         check(mzk_ntt_dev(C::ID, fixed.p, n, log_n, 1, nullptr, nfix, n, nullptr), "mzk_ntt_dev");
         std::vector<uint64_t> host((size_t)nfix * n * 4);
         check(mzk_dev_download(host.data(), fixed.p, host.size() * 8), "download");
-        std::vector<uint64_t> kk((size_t)W * 4);
-        for (int i = 0; i < W; i++) std::memcpy(&kk[4 * i], k[i].l, 32);
         const uint64_t* sel = host.data();
         const uint64_t* sig = sel + (size_t)nsel * n * 4;
         check(mzk_prover_create(C::ID, log_n, W, sel, sig, ultra ? sig + (size_t)W * n * 4 : nullptr, n, kk.data(), srs, lagrange_key, comm, &handle), "mzk_prover_create");
-        std::vector<uint64_t> xy((size_t)(nsel + W) * 2 * QL);
-        check(mzk_prover_vk_commitments(handle, xy.data(), nullptr), "mzk_prover_vk_commitments");
-        auto pt = [&](size_t i) { Affine a; std::memcpy(a.data(), &xy[i * 2 * QL], sizeof(Affine)); return a; };
-        for (int i = 0; i < nsel; i++) selector_comms.push_back(pt(i));
-        for (int i = 0; i < W; i++) sigma_comms.push_back(pt(nsel + i));
-        if (cs.host_witness == 2) check(mzk_prover_set_wire_variables(handle, cs.host_wire_variables.data(), cs.n_vars), "mzk_prover_set_wire_variables");
     }
     Prover(const Prover&) = delete;
     Prover& operator=(const Prover&) = delete;
@@ -649,7 +672,7 @@ struct ShardedProver {
     // its fixed-base table, built with the window that suits the slice (2^17-point shards at G = 8: window 16 and fused small batches)
     // srs_file (nullable): the commit key is the file's first n + 3 powers, decoded and validated on every device, instead of [beta^i] G
     void setup(const BenchCircuitHost<C>& host, const std::array<uint64_t, 4>& beta_canonical, int host_witness = 0, bool lagrange = true, bool slice_srs = true,
-               const SrsFile* srs_file = nullptr) {
+               const SrsFile* srs_file = nullptr, bool device_preprocess = false) {
         if (srs_file && srs_file->count < host.n + 3)
             throw std::runtime_error("--srs: the file holds " + std::to_string(srs_file->count) + " powers, the circuit needs n + 3 = " + std::to_string(host.n + 3));
         each([&](int r) {
@@ -673,7 +696,7 @@ struct ShardedProver {
                     *key = part;
                 }
             }
-            circuit[r] = std::make_unique<BenchCircuit<C>>(BenchCircuit<C>::upload(host, host_witness));
+            circuit[r] = std::make_unique<BenchCircuit<C>>(BenchCircuit<C>::upload(host, host_witness, device_preprocess));
             mzk_comm cm{&rank_ctx[r], r, G, &cb_all_gather, &cb_barrier, nullptr};
             prover[r] = std::make_unique<P>(srs[r], *circuit[r], srs_lagrange[r], G > 1 ? &cm : nullptr);
         });

@@ -77,6 +77,8 @@ _SIGS = {
     "mzk_plookup_product_dev": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_plonk_perm_product_dev": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_plonk_perm_product": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_plonk_wire_permutation_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p],
+    "mzk_plonk_sigma_values_dev": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_plonk_gather_witness_dev": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_poly_eval_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_poly_lincomb_dev": [C.c_int32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p],
@@ -120,6 +122,10 @@ _SIGS = {
     # the prover's rounds (csrc/prover.hip); mzk_comm* travels as a void pointer (sharding.TorchComm)
     "mzk_prover_create": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
                           C.POINTER(C.c_uint64)],
+    "mzk_prover_create_from_circuit": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                       C.c_void_p, C.POINTER(C.c_uint64)],
+    "mzk_prover_create_from_circuit_dev": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                           C.c_void_p, C.POINTER(C.c_uint64)],
     "mzk_prover_destroy": [C.c_uint64],
     "mzk_prover_vk_commitments": [C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_prover_set_wire_variables": [C.c_uint64, C.c_void_p, C.c_uint64],

@@ -211,16 +211,8 @@ class TurboPlonkProver:
 
     def __init__(self, curve, domain_size: int, selector_polys, sigma_polys, k, commit_key: kzg.UnivariateProverParam, plookup=None,
                  lagrange_ck: kzg.UnivariateProverParam | None = None, comm=None):
-        self.curve = c = _curve(curve)
-        self.n = domain_size
-        self.log_n = domain_size.bit_length() - 1
-        self.k = list(k)
-        self.ck = commit_key
-        self.lagrange_ck = lagrange_ck
-        self.ultra = plookup is not None
-        self.W = len(sigma_polys)
-        self.nsel = len(selector_polys)
-        assert commit_key.offset == 0, "the prover takes the SRS handle itself: a trimmed view must start at power 0"
+        c = self._describe(curve, domain_size, k, commit_key, lagrange_ck, len(sigma_polys), len(selector_polys))
+        assert self.ultra == (plookup is not None)
         pad = lambda p: np.concatenate([np.asarray(p, dtype=np.uint64).reshape(-1, 4),
                                         np.zeros((domain_size - np.asarray(p).reshape(-1, 4).shape[0], 4), dtype=np.uint64)])
         sel = np.ascontiguousarray(np.stack([pad(p) for p in selector_polys]))
@@ -232,10 +224,64 @@ class TurboPlonkProver:
         _check(L.mzk_prover_create(c.curve_id, self.log_n, self.W, _ptr(sel), _ptr(sig), _ptr(tab) if self.ultra else None, domain_size, _ptr(kk),
                                    commit_key.handle, lagrange_ck.handle if lagrange_ck is not None else 0, comm.struct_ptr() if comm is not None else None,
                                    C.byref(h)), "mzk_prover_create")
-        self.handle = h.value
+        self._adopt(h.value, comm)
+
+    def _describe(self, curve, domain_size, k, commit_key, lagrange_ck, num_wire_types, num_selectors):
+        self.curve = c = _curve(curve)
+        self.n = domain_size
+        self.log_n = domain_size.bit_length() - 1
+        self.k = list(k)
+        self.ck = commit_key
+        self.lagrange_ck = lagrange_ck
+        self.W = num_wire_types
+        self.ultra = num_wire_types == 6
+        self.nsel = num_selectors
+        assert commit_key.offset == 0, "the prover takes the SRS handle itself: a trimmed view must start at power 0"
+        return c
+
+    def _adopt(self, handle, comm):
+        self.handle = handle
         self.comm = comm                                               # (keeps the callbacks alive)
         self._vk = self._pvk = None
         self.timings_ms = {}
+
+    @classmethod
+    def from_circuit(cls, curve, domain_size: int, selector_values, wire_variables, n_vars: int, k, commit_key: kzg.UnivariateProverParam,
+                     table_values=None, lagrange_ck: kzg.UnivariateProverParam | None = None, comm=None) -> "TurboPlonkProver":
+        """The prover of a FINALISED CIRCUIT (mzk_prover_create_from_circuit[_dev]): selector_values (nsel, n, 4) and table_values
+        (4, n, 4; UltraPlonk) are VALUES on the gate domain (Montgomery), wire_variables the (W, n) variable table with entries below
+        n_vars.  Wire permutation, sigma values, all inverse NTTs and the key run on the device; CUDA tensors are read where they are
+        (all three on the device, or none).  The table stays with the prover: check_witness checks the copy constraints of every
+        witness kind and a HostWitness needs no set_wire_variables."""
+        import torch
+        self = cls.__new__(cls)
+        W = int(wire_variables.shape[0])
+        c = self._describe(curve, domain_size, k, commit_key, lagrange_ck, W, int(selector_values.shape[0]))
+        assert (table_values is not None) == self.ultra and self.nsel == (14 if self.ultra else 13)
+        ins = [selector_values, wire_variables] + ([table_values] if self.ultra else [])
+        on_dev = all(torch.is_tensor(t) and t.is_cuda for t in ins)
+        assert on_dev or not any(torch.is_tensor(t) and t.is_cuda for t in ins), "selector values, variable table and tables: all on the device or none"
+        kk = fr_to_mont(c, self.k)
+        L = _lib.ensure_init()
+        h = C.c_uint64()
+        tail = (_ptr(kk), commit_key.handle, lagrange_ck.handle if lagrange_ck is not None else 0, comm.struct_ptr() if comm is not None else None, C.byref(h))
+        if on_dev:
+            sel, tab = selector_values.contiguous(), table_values.contiguous() if self.ultra else None
+            var = wire_variables.to(torch.int32).contiguous()
+            assert sel.dtype == torch.int64 and tuple(sel.shape) == (self.nsel, domain_size, 4) and tuple(var.shape) == (W, domain_size)
+            torch.cuda.synchronize()
+            _check(L.mzk_prover_create_from_circuit_dev(c.curve_id, self.log_n, W, C.c_void_p(sel.data_ptr()), C.c_void_p(var.data_ptr()), n_vars,
+                                                        C.c_void_p(tab.data_ptr()) if self.ultra else None, *tail), "mzk_prover_create_from_circuit_dev")
+        else:
+            np_of = lambda t: t.numpy() if torch.is_tensor(t) else np.asarray(t)
+            sel = np.ascontiguousarray(np_of(selector_values)).view(np.uint64).reshape(self.nsel, domain_size, 4)
+            var = np.ascontiguousarray(np_of(wire_variables)).astype(np.uint32).reshape(W, domain_size)
+            tab = np.ascontiguousarray(np_of(table_values)).view(np.uint64).reshape(4, domain_size, 4) if self.ultra else None
+            _check(L.mzk_prover_create_from_circuit(c.curve_id, self.log_n, W, _ptr(sel), _ptr(var), n_vars, _ptr(tab) if self.ultra else None, *tail),
+                   "mzk_prover_create_from_circuit")
+        self._adopt(h.value, comm)
+        self._own_table = True
+        return self
 
     def release(self):
         if self.handle:
@@ -284,7 +330,7 @@ class TurboPlonkProver:
         import torch
         if hasattr(wire_values, "wire_variables"):                       # snark.HostWitness: the witness vector, gathered on the device
             w = wire_values.witness
-            if getattr(self, "_vars_of", None) is not wire_values.wire_variables:       # the circuit's variable table goes to the device once
+            if not getattr(self, "_own_table", False) and getattr(self, "_vars_of", None) is not wire_values.wire_variables:   # the circuit's variable table goes to the device once (from_circuit: it is there)
                 wv = wire_values.wire_variables
                 self.set_wire_variables(wv.cpu().numpy() if torch.is_tensor(wv) else wv, int(w.shape[0]))
                 self._vars_of = wire_values.wire_variables

@@ -173,7 +173,7 @@ def witness_is_small(curve, wire_values) -> bool:
 
 
 def preprocess(commit_key: kzg.UnivariateProverParam, circuit: BenchCircuit, lagrange: bool | None = None, lagrange_ck=None,
-               comm=None) -> _prover.TurboPlonkProver:
+               comm=None, from_structure: bool = False) -> _prover.TurboPlonkProver:
     """snark.rs:529-617: interpolate selectors, sigmas (and Plookup tables) and hand the coefficient forms to the library
     (mzk_prover_create keeps them, their evaluations on the needed residue classes and the workspace of one proof in HBM).  The
     verifying-key commitments come on demand from `TurboPlonkProver.vk_commitments()`.
@@ -182,24 +182,30 @@ def preprocess(commit_key: kzg.UnivariateProverParam, circuit: BenchCircuit, lag
     gates on (below, an MSM is a chain of latencies and small scalars only add over-long buckets to it) AND only when a sample of the
     circuit's witness shows small values (witness_is_small: a dense witness gains nothing from the key).  lagrange_ck: an existing key.
     comm: a sharding.TorchComm -- this process is one rank of a sharded proof and keeps only its point range of the SRS (and of the
-    Lagrange key): mzk_srs_slice."""
+    Lagrange key): mzk_srs_slice.
+    from_structure: the key comes from what a finalised circuit holds -- `selector_values`, `wire_variables` (and `table_values`) --
+    with the permutation, the sigma values and every inverse NTT on the device (TurboPlonkProver.from_circuit); `sigma_values` is not
+    read.  Same key, same proofs; the prover keeps the variable table."""
     c, n = circuit.curve, circuit.n
+    if from_structure and circuit.wire_variables is None:
+        raise ValueError("from_structure: the circuit carries no wire_variables")
     if commit_key.length < n + 3:
         raise ValueError("SRS too small: need domain size + 3 powers (srs.rs:88)")          # snark.rs:535-541
     if commit_key.length > n + 3:       # snark.rs:535, 561: the proving key keeps trim(srs_size) = n + 3 powers -- a view of the same registration
         commit_key = commit_key.trim(n + 2)
-    dom = Radix2EvaluationDomain(c, n.bit_length() - 1)
-    sel = circuit.selector_values.clone()
-    sig = circuit.sigma_values.clone()
-    dom.ifft_in_place(sel)
-    dom.ifft_in_place(sig)
     host = lambda t: t.cpu().numpy().view(np.uint64)
     plookup = None
-    if circuit.table_values is not None:
-        tab = circuit.table_values.clone()
-        dom.ifft_in_place(tab)
-        tab_h = host(tab)
-        plookup = {name: tab_h[i] for i, name in enumerate(("range_table_poly", "key_table_poly", "table_dom_sep_poly", "q_dom_sep_poly"))}
+    if not from_structure:
+        dom = Radix2EvaluationDomain(c, n.bit_length() - 1)
+        sel = circuit.selector_values.clone()
+        sig = circuit.sigma_values.clone()
+        dom.ifft_in_place(sel)
+        dom.ifft_in_place(sig)
+        if circuit.table_values is not None:
+            tab = circuit.table_values.clone()
+            dom.ifft_in_place(tab)
+            tab_h = host(tab)
+            plookup = {name: tab_h[i] for i, name in enumerate(("range_table_poly", "key_table_poly", "table_dom_sep_poly", "q_dom_sep_poly"))}
     if lagrange is None:
         lagrange = n >= LAGRANGE_MIN_DOMAIN and witness_is_small(c, circuit.wire_values)
     lck = lagrange_ck if lagrange_ck is not None else (commit_key.lagrange_key(n) if lagrange else None)
@@ -216,7 +222,12 @@ def preprocess(commit_key: kzg.UnivariateProverParam, circuit: BenchCircuit, lag
                 full.release()                                   # derived here: only this rank's range of it stays
     elif lagrange_ck is None and lck is not None:
         owned.append(lck)
-    pk = _prover.TurboPlonkProver(c, n, list(host(sel)), list(host(sig)), circuit.k, commit_key, plookup=plookup, lagrange_ck=lck, comm=comm)
+    if from_structure:
+        n_vars = int(circuit.witness.shape[0]) if circuit.witness is not None else int(circuit.wire_variables.max()) + 1
+        pk = _prover.TurboPlonkProver.from_circuit(c, n, circuit.selector_values, circuit.wire_variables, n_vars, circuit.k, commit_key,
+                                                   table_values=circuit.table_values, lagrange_ck=lck, comm=comm)
+    else:
+        pk = _prover.TurboPlonkProver(c, n, list(host(sel)), list(host(sig)), circuit.k, commit_key, plookup=plookup, lagrange_ck=lck, comm=comm)
     pk.owned_keys = owned
     return pk
 
