@@ -389,9 +389,9 @@ MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uin
 
 /* ---- the prover's rounds on device-resident state: replaces the BODIES of Prover::run_1st_round .. compute_opening_proofs
  *      (plonk/src/proof_system/prover.rs:72-419) as PlonkKzgSnark::batch_prove_internal calls them (snark.rs:263-431).
- * One mzk_prover per (proving key, instance slot): it owns, in HBM, the coefficient forms of the key's fixed polynomials, their
- * evaluations on the residue classes of the quotient domain that the quotient needs (mzk_plonk_pk_register_chunked), and the
- * workspace of one proof in flight (`Oracles`, structs.rs:875-887).  The CALLER keeps what the reference's snark.rs keeps: the
+ * One mzk_prover per (proving key, instance slot): it holds, in HBM, the coefficient forms of the key's fixed polynomials, their
+ * evaluations on the residue classes of the quotient domain that the quotient needs (mzk_plonk_pk_register_chunked) -- the key part,
+ * which mzk_prover_fork shares among several handles -- and owns the workspace of one proof in flight (`Oracles`, structs.rs:875-887).  The CALLER keeps what the reference's snark.rs keeps: the
  * transcript (challenges in, commitments / evaluations out), the rng (blinders in, in the reference's draw order: SURVEY.md
  * Appendix C) and the `Proof` struct.  Nothing but challenges, blinders, public inputs, commitments (affine x||y, mont; (0,0) =
  * infinity: `Commitment(G1Affine)`) and evaluations crosses the boundary per round; the witness crosses once (or not at all:
@@ -424,6 +424,10 @@ MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uin
  * synchronised by the caller); every round returns when its outputs are in host memory; mzk_prover_poly_dev's pointers are valid to read
  * on any stream once round 5 has returned.  Two proofs on one card -- two host threads, each bound (mzk_init) to its own device context
  * (MZK_VIRTUAL_DEVICES maps several contexts onto one GPU), or two handles of one context -- run concurrently where the hardware allows.
+ * A prover and its forks (mzk_prover_fork) are such handles of one context, and may run their rounds from different host threads: the
+ * key part they share is read-only once a second handle holds it, every handle has its own workspace, state and stream, and enqueueing is
+ * under the context's device lock as for any two handles of one context.  One handle still belongs to one thread at a time, and
+ * mzk_prover_fork / mzk_prover_set_wire_variables / mzk_prover_destroy of a handle must not run concurrently with each other on that handle.
  * Domains whose quotient does not fit the 8n-point domain (num_wire_types * (n + 1) + 2 >= 8 n: n = 2; n = 4 with six wire types) are
  * refused by mzk_prover_create with MZK_ERR_UNSUPPORTED. */
 #define MZK_ERR_WRONG_QUOTIENT_DEGREE (-9) /* PlonkError::WrongQuotientPolyDegree: the witness does not satisfy the circuit */
@@ -478,11 +482,24 @@ MZK_API int32_t mzk_prover_create_from_circuit_dev(int32_t curve_id, uint32_t lo
                                                    const void* d_wire_variables, uint64_t n_vars, const void* d_table_values, const uint64_t* k_mont,
                                                    uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, uint64_t* out_prover);
 MZK_API int32_t mzk_prover_destroy(uint64_t prover);
+/* Another slot on the same proving key: a new handle on `prover`'s device context that SHARES its key part -- the coefficient forms, the
+ * chunked proving key with its resident class evaluations, the SRS handles and the resident variable table -- and owns a fresh
+ * workspace, state (the next call must be round 1) and stream (the next of the context's rotation); profiling is off on it.  The
+ * reference's batch_prove takes `&[&ProvingKey]` in which one key may appear K times (snark.rs:263-431): here that is a prover and
+ * K - 1 forks as the K instances of rounds 3 and 5 (the SAME handle twice is still refused), and the same family serves K proofs in
+ * flight on one key.  The call does no SRS work, no NTT and no upload: it allocates the workspace mzk_prover_create allocates.  A fork
+ * of a fork is a peer of all the others; handles are destroyed in any order and the key lives until its last holder is gone.  `prover`
+ * may have a proof in flight: its state is not touched.  A fork of a prover that has the variable table (mzk_prover_create_from_circuit,
+ * or mzk_prover_set_wire_variables before the fork) has it too.  MZK_ERR_BAD_HANDLE: unknown handle; MZK_ERR_INVALID_ARG: null
+ * out_prover; MZK_ERR_UNSUPPORTED: `prover` was created with an mzk_comm of world > 1 (two slots would interleave one communicator's
+ * collectives); MZK_ERR_OOM: the workspace did not fit, nothing stays allocated. */
+MZK_API int32_t mzk_prover_fork(uint64_t prover, uint64_t* out_prover);
 /* `VerifyingKey{selector_comms, sigma_comms}` (preprocess, snark.rs:562-594) from the resident coefficient forms: nsel + W affine points,
  * then -- UltraPlonk, out_plookup_xy non-NULL -- range_table_comm, key_table_comm, table_dom_sep_comm, q_dom_sep_comm (:575-590). */
 MZK_API int32_t mzk_prover_vk_commitments(uint64_t prover, uint64_t* out_xy_mont, uint64_t* out_plookup_xy_mont);      /* (with a comm: a collective, every rank calls it) */
 /* `wire_variables` of the finalised circuit (relation/src/constraint_system.rs:1225-1247), W x n u32 (host), every entry < n_vars (checked:
- * MZK_ERR_INVALID_ARG -- the reference panics on such an index): resident circuit structure for MZK_WITNESS_*_VECTOR. */
+ * MZK_ERR_INVALID_ARG -- the reference panics on such an index): resident circuit structure for MZK_WITNESS_*_VECTOR.  On a handle that
+ * shares its key (mzk_prover_fork) the table is replaced for THAT handle only (copy-on-write): the other handles keep the shared one. */
 MZK_API int32_t mzk_prover_set_wire_variables(uint64_t prover, const uint32_t* wire_variables, uint64_t n_vars);
 #define MZK_WITNESS_DEV_WIRES 0   /* device, W x n: witness[wire_variable(i, j)] already gathered.  The prover keeps the POINTER, not a copy:
                                    * the buffer must stay valid and unmodified until round 2 (round 2.5 for UltraPlonk) has returned --
@@ -568,6 +585,12 @@ MZK_API int32_t mzk_prover_profile(uint64_t prover, int32_t on);
 MZK_API int32_t mzk_prover_timings(uint64_t prover, char* buf, uint64_t cap);
 /* Bytes of HBM this prover holds: coefficient forms, resident class evaluations (proving key), per-proof workspace. */
 MZK_API int32_t mzk_prover_hbm_bytes(uint64_t prover, uint64_t* out_fixed, uint64_t* out_proving_key, uint64_t* out_workspace);
+/* Of the bytes mzk_prover_hbm_bytes reports for this handle -- it reports what the handle REACHES, shared parts included, forked or not --
+ * those held in common with other living handles (mzk_prover_fork), and the number of handles on that key, this one included.  One
+ * sharer: 0 bytes.  Otherwise out_fixed + out_proving_key + the shared variable table; that table is counted in out_workspace (as it
+ * always was) and here, unless this handle has replaced it by one of its own (mzk_prover_set_wire_variables, counted in out_workspace
+ * only).  HBM of a family of handles on one key: sum over the handles of (fixed + proving_key + workspace) - (sharers - 1) x shared. */
+MZK_API int32_t mzk_prover_shared_hbm_bytes(uint64_t prover, uint64_t* out_shared_bytes, uint32_t* out_sharers);
 
 /* ---- page-locked host memory for the host-pointer entry points (mzk_ntt, mzk_ntt_batch, mzk_msm, mzk_msm_batch) ----
  * A shim that swaps only the two third-party call sites moves every operand over PCIe.  From memory

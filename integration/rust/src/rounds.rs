@@ -15,6 +15,7 @@ use ark_ec::{pairing::Pairing, short_weierstrass::Affine, AffineRepr};
 use ark_ff::{PrimeField, UniformRand};
 use ark_std::rand::{CryptoRng, RngCore};
 use core::ffi::c_void;
+use std::sync::Arc;
 
 use crate::{check, mzk_srs_release, Mi355Error, SrsHandle};
 
@@ -60,6 +61,9 @@ extern "C" {
                                           n_vars: u64, table_values: *const u64, k_mont: *const u64, commit_key: u64, lagrange_key: u64,
                                           comm: *const c_void, out_prover: *mut u64) -> i32;
     pub fn mzk_prover_destroy(prover: u64) -> i32;
+    pub fn mzk_prover_fork(prover: u64, out_prover: *mut u64) -> i32;
+    pub fn mzk_prover_hbm_bytes(prover: u64, out_fixed: *mut u64, out_proving_key: *mut u64, out_workspace: *mut u64) -> i32;
+    pub fn mzk_prover_shared_hbm_bytes(prover: u64, out_shared_bytes: *mut u64, out_sharers: *mut u32) -> i32;
     pub fn mzk_prover_set_wire_variables(prover: u64, wire_variables: *const u32, n_vars: u64) -> i32;
     pub fn mzk_prover_round1(prover: u64, witness_kind: i32, witness: *const c_void, witness_len: u64, pub_input_rows: *const u64,
                              pub_input_mont: *const u64, n_pub: u64, blinders_mont: *const u64, out_comms_xy: *mut u64) -> i32;
@@ -73,26 +77,39 @@ extern "C" {
     pub fn mzk_prover_round5(provers: *const u64, n_instances: u32, v: *const u64, out_comms_xy: *mut u64) -> i32;
 }
 
+/// A Lagrange-basis key derived for a prover: its points and fixed-base table live in HBM until the last slot that uses it is dropped.
+struct LagrangeKey(u64);
+
+impl Drop for LagrangeKey {
+    fn drop(&mut self) {
+        unsafe {
+            mzk_srs_release(self.0);
+        }
+    }
+}
+
 /// One instance's device-resident state: `ProvingKey{selectors, sigmas, plookup_pk}` (structs.rs:575-590) uploaded once, the
-/// circuit's wire-variable table, and the workspace of the proof in flight.  Created once per (proving key, instance slot).
+/// circuit's wire-variable table, and the workspace of the proof in flight.  Created once per proving key; `fork` makes the further
+/// instance slots on the same key.
 pub struct Mi355Prover {
     pub handle: u64,
     pub num_wire_types: usize,
     pub ultra: bool,
     fq_limbs: usize,
-    /// the Lagrange-basis key derived for this prover (0 = none): its points and fixed-base table live in HBM until released
-    lagrange_key: u64,
+    /// the Lagrange-basis key derived for this prover (None = round 1 commits the coefficient forms), shared with its forks
+    lagrange_key: Option<Arc<LagrangeKey>>,
 }
 
 impl Drop for Mi355Prover {
     fn drop(&mut self) {
         unsafe {
-            mzk_prover_destroy(self.handle);
-            if self.lagrange_key != 0 {
-                mzk_srs_release(self.lagrange_key);
-            }
+            mzk_prover_destroy(self.handle); // (the Lagrange key goes after it, with the last slot: fields drop after this body)
         }
     }
+}
+
+fn owned(lagrange: u64) -> Option<Arc<LagrangeKey>> {
+    if lagrange != 0 { Some(Arc::new(LagrangeKey(lagrange))) } else { None }
 }
 
 fn flat<F: PrimeField>(v: &[F]) -> *const u64 {
@@ -123,7 +140,7 @@ impl Mi355Prover {
             made?;
         }
         // from here on Drop releases both handles
-        let me = Self { handle, num_wire_types, ultra: tables.is_some(), fq_limbs, lagrange_key: lagrange };
+        let me = Self { handle, num_wire_types, ultra: tables.is_some(), fq_limbs, lagrange_key: owned(lagrange) };
         unsafe { check(mzk_prover_set_wire_variables(handle, wire_variables.as_ptr(), n_vars as u64))? };
         Ok(me)
     }
@@ -151,7 +168,28 @@ impl Mi355Prover {
             }
             made?;
         }
-        Ok(Self { handle, num_wire_types, ultra: table_values.is_some(), fq_limbs, lagrange_key: lagrange })
+        Ok(Self { handle, num_wire_types, ultra: table_values.is_some(), fq_limbs, lagrange_key: owned(lagrange) })
+    }
+
+    /// Another slot on this prover's proving key (`mzk_prover_fork`): the key, its Lagrange key and the variable table stay ONE copy in
+    /// HBM, the slot brings its own workspace and stream.  `batch_prove(&[&circuit; K], &[&pk; K])` -- one `ProvingKey` K times,
+    /// snark.rs:64-78 -- becomes `prove_rounds` over the prover and K - 1 forks of it; the same slots serve K proofs in flight from K
+    /// threads.  Slots are peers and drop in any order.  No SRS work, no NTT, no upload.
+    pub fn fork(&self) -> Result<Self, Mi355Error> {
+        let mut handle = 0u64;
+        unsafe { check(mzk_prover_fork(self.handle, &mut handle))? };
+        Ok(Self { handle, num_wire_types: self.num_wire_types, ultra: self.ultra, fq_limbs: self.fq_limbs, lagrange_key: self.lagrange_key.clone() })
+    }
+
+    /// (fixed coefficient forms, proving-key evaluations, workspace) this slot reaches, then the bytes among them that other living
+    /// slots reach too and the number of slots on the key: K slots hold sum(fixed + key + workspace) - (K - 1) * shared.
+    pub fn hbm_bytes(&self) -> Result<(u64, u64, u64, u64, u32), Mi355Error> {
+        let (mut fixed, mut key, mut ws, mut shared, mut sharers) = (0u64, 0u64, 0u64, 0u64, 0u32);
+        unsafe {
+            check(mzk_prover_hbm_bytes(self.handle, &mut fixed, &mut key, &mut ws))?;
+            check(mzk_prover_shared_hbm_bytes(self.handle, &mut shared, &mut sharers))?;
+        }
+        Ok((fixed, key, ws, shared, sharers))
     }
 
     /// `Circuit::check_circuit_satisfiability` (relation/src/constraint_system.rs:389-451) on the device, for the witness vector

@@ -47,14 +47,16 @@ def _pt(c, cm: kzg.Commitment):
 
 def batch_prove(provers, wire_values: list, pub_inputs: list, blinds: list, quot_blinders: list, extra_transcript_init_msg: bytes | None = None):
     """PlonkKzgSnark::batch_prove (snark.rs:64-78, 201-469) over K native handles: rounds 1 - 2.5 and 4 per instance, rounds 3 and 5
-    once over all handles.  pub_inputs[k]: instance k's public input as ints, on rows 0.. of its circuit.  Returns batch.BatchProofCore."""
+    once over all handles.  pub_inputs[k]: instance k's public input as ints, on rows 0.. of its circuit.  Returns batch.BatchProofCore.
+    One circuit several times in the aggregate -- the reference's `prove_keys` with one key repeated -- is `[pk, pk.fork(), pk.fork()]`:
+    one key in HBM, one workspace per instance (TurboPlonkProver.fork).  The same prover object twice is refused."""
     if not provers:
         raise ValueError("zero number of circuits/proving keys")
     if not (len(provers) == len(wire_values) == len(pub_inputs) == len(blinds)):
         raise ValueError("the number of circuits != the number of proving keys")
     if len({id(p) for p in provers}) != len(provers):
-        # the device workspace belongs to the handle: two instances of one circuit need two provers (preprocess twice) -- the reference's
-        # `prove_keys` may repeat because its Oracles live on the host
+        # the device workspace belongs to the handle: two instances of one circuit need two handles (pk and pk.fork(), on one key) -- the
+        # reference's `prove_keys` may repeat because its Oracles live on the host
         raise ValueError("one TurboPlonkProver per instance: the same prover object was passed twice")
     p0 = provers[0]
     c = p0.curve

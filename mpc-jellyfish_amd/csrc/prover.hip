@@ -45,6 +45,7 @@ struct Buf {                                                           // device
     }
     void* at(size_t idx) const { return static_cast<uint8_t*>(p) + idx * EL; }
     size_t bytes() const { return p ? (elems ? elems : 1) * EL : 0; }
+    void swap(Buf& o) { std::swap(p, o.p); std::swap(elems, o.elems); }
 };
 struct Pinned {                                                        // page-locked staging memory
     void* p = nullptr;
@@ -113,6 +114,8 @@ struct ProverBase {
     virtual void set_peer_buffers(void* const* ptrs, const int32_t* devices) = 0;
     virtual void poly_dev(uint32_t which, const void** out_p, uint64_t* out_len) = 0;
     virtual void hbm_bytes(uint64_t* fixed_b, uint64_t* pk_b, uint64_t* ws_b) = 0;
+    virtual void shared_hbm_bytes(uint64_t* shared_b, uint32_t* sharers) = 0;
+    virtual std::shared_ptr<ProverBase> fork() = 0;
 };
 
 template <class FrP, int CURVE>
@@ -121,29 +124,49 @@ struct ProverT final : ProverBase {
     static constexpr int QL = CURVE == MZK_CURVE_BLS12_381 ? 6 : 4;   // u64 limbs of Fq
     static constexpr size_t PT = 2 * QL;                               // u64 words of an affine point
 
+    // What the handles on one circuit hold in common (mzk_prover_fork): the proving key and what is derived from it once.  Written by the
+    // constructor, and by set / take_wire_variables while the key has ONE holder; after that the rounds reach it through key() alone,
+    // which is const, so that nothing a proof does can write through it -- any number of slots read it at the same time.
+    struct Key {
+        std::vector<Fr> k;
+        uint64_t srs = 0, srs_lagrange = 0, pk = 0;
+        Buf fixed;                                                     // (nsel + W [+ 4]) x n coefficient forms
+        Buf vars;                                                      // W x n u32: the resident variable table
+        uint64_t n_vars = 0;
+        bool use_top = false;                                          // W classes + mzk_plonk_quotient_top_dev
+        std::vector<uint32_t> classes;                                 // the classes that determine the quotient
+        Fr w_n, gen;
+        Key() = default;
+        Key(const Key&) = delete;
+        Key& operator=(const Key&) = delete;
+        ~Key() {                                                       // with the last holder, on the prover's device (mzk_prover_destroy)
+            (void)mzk_dev_sync();
+            if (pk) (void)mzk_plonk_pk_release(pk);
+        }
+    };
+    std::shared_ptr<Key> key_;
+    const Key& key() const { return *key_; }
+
+    // ---- everything below belongs to this handle (the slot): the workspace, state and stream of one proof in flight ----
     int rows = 0;
     uint64_t m = 0;
-    std::vector<Fr> k;
-    uint64_t srs = 0, srs_lagrange = 0, pk = 0;
     // several ranks: this prover commits over the SRS points [lo, hi) of every polynomial (one fixed partition of the
     // n + 3 powers), owns the residue classes `own` of the quotient domain, and runs rounds 4-5 on its coefficient range
     int rank = 0, world = 1;
     mzk_comm comm{};
     uint64_t lo = 0, hi = 0;
     uint64_t key_first = 0;                                            // SRS index of the commit key's first point: lo when the key is this rank's slice
-    Buf fixed;                                                         // (nsel + W [+ 4]) x n coefficient forms
-    Buf slab, quot, coeff, split, lin, batch, opening, shifted, hh, table, lookup, sorted, tmp, deg, rem, wv, wit, top, vals_ext, qsum, vars;
+    Buf slab, quot, coeff, split, lin, batch, opening, shifted, hh, table, lookup, sorted, tmp, deg, rem, wv, wit, top, vals_ext, qsum;
+    Buf own_vars;                                                      // a variable table of this handle's own: set on a handle that shared its key
+    uint64_t own_n_vars = 0;
     Pinned stage_pi;
     Pinned stage_back;                                                 // 64 B: the words a round reads back AFTER its commitments (quotient degree, batch value at zeta)
                                                                        // are copied here asynchronously BEFORE them: no second device round trip at the end of the round
-    uint64_t n_vars = 0;
-    bool use_top = false;                                              // W classes + mzk_plonk_quotient_top_dev
-    std::vector<uint32_t> classes, own;                                // the classes that determine the quotient; this rank's share of them
+    std::vector<uint32_t> own;                                         // this rank's share of the key's classes
     std::vector<void*> peer_rem;
     std::vector<int32_t> peer_dev;
     void* copy_stream = nullptr;
     bool one_ready = false;
-    Fr w_n, gen;
 
     // what Oracles + Challenges carry for the proof in flight
     struct State {
@@ -176,13 +199,20 @@ struct ProverT final : ProverBase {
     // one slab: rows 0..W-1 wires, W z, W+1 public input (, h_1, h_2, Plookup product), n + 3 coefficient slots each; the rounds read
     // their polynomials from here from round 1 to the openings
     void* row(int r) const { return slab.at((size_t)r * (n + 3)); }
-    void* fix(int r) const { return fixed.at((size_t)r * n); }
+    const void* fix(int r) const { return key().fixed.at((size_t)r * n); }
+    const void* vars_dev() const { return own_vars.p ? own_vars.p : key().vars.p; }
+    uint64_t vars_n() const { return own_vars.p ? own_n_vars : key().n_vars; }
     static Fr load(const uint64_t* p) { Fr v; std::memcpy(v.l, p, EL); return v; }
 
     ProverT(int log_n_, int W_, const uint64_t* sel, const uint64_t* sig, const uint64_t* tab, uint64_t poly_len, const uint64_t* k_mont,
         uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* cm, CoeffsAt at);   // prover_setup.inc
+    explicit ProverT(const ProverT& parent);   // a new slot on parent's key (mzk_prover_fork), prover_setup.inc
     ~ProverT() override;   // prover_setup.inc
+    void take_stream();   // prover_setup.inc
+    void alloc_workspace();   // prover_setup.inc
     void hbm_bytes(uint64_t* fixed_b, uint64_t* pk_b, uint64_t* ws_b) override;   // prover_setup.inc
+    void shared_hbm_bytes(uint64_t* shared_b, uint32_t* sharers) override;   // prover_setup.inc
+    std::shared_ptr<ProverBase> fork() override { return std::make_shared<ProverT>(*this); }
 
     // ---- commitments ---------------------------------------------------------------------------------------------------------
     std::vector<uint64_t> msm_partials(const std::vector<const void*>& polys, const std::vector<uint64_t>& lens, uint64_t a, uint64_t b,
@@ -295,7 +325,7 @@ struct ProverT final : ProverBase {
 
     void exchange_buffer(void** out_p, uint64_t* out_bytes) override {
         if (out_p) *out_p = rem.p;
-        if (out_bytes) *out_bytes = classes.size() * n * EL;
+        if (out_bytes) *out_bytes = key().classes.size() * n * EL;
     }
     void set_peer_buffers(void* const* ptrs, const int32_t* devices) override {
         peer_rem.assign(ptrs, ptrs + world);
@@ -587,6 +617,15 @@ int32_t mzk_prover_timings(uint64_t prover, char* buf, uint64_t cap) {
 int32_t mzk_prover_hbm_bytes(uint64_t prover, uint64_t* out_fixed, uint64_t* out_proving_key, uint64_t* out_workspace) {
     PROVER(prover);
     return guarded(*p_, [&] { p_->hbm_bytes(out_fixed, out_proving_key, out_workspace); });
+}
+int32_t mzk_prover_shared_hbm_bytes(uint64_t prover, uint64_t* out_shared_bytes, uint32_t* out_sharers) {
+    PROVER(prover);
+    return guarded(*p_, [&] { p_->shared_hbm_bytes(out_shared_bytes, out_sharers); });
+}
+int32_t mzk_prover_fork(uint64_t prover, uint64_t* out_prover) {
+    PROVER(prover);
+    if (!out_prover) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    return guarded(*p_, [&] { *out_prover = publish(p_->fork(), p_->device); });
 }
 
 }  // extern "C"

@@ -9,8 +9,8 @@ void ProverT<FrP, CURVE>::check_witness(int kind, const void* witness, uint64_t 
     if (!out || !witness || (n_pi && !pi)) fail(MZK_ERR_INVALID_ARG, "null pointer");
     const bool vec = kind == MZK_WITNESS_HOST_VECTOR || kind == MZK_WITNESS_DEV_VECTOR;
     if (!vec && kind != MZK_WITNESS_DEV_WIRES && kind != MZK_WITNESS_HOST_WIRES) fail(MZK_ERR_INVALID_ARG, "unknown witness_kind");
-    if (vec && !vars.p) fail(MZK_ERR_INVALID_ARG, "mzk_prover_set_wire_variables has not been called");
-    if (vec ? witness_len != n_vars : witness_len != (uint64_t)W * n)
+    if (vec && !vars_dev()) fail(MZK_ERR_INVALID_ARG, "mzk_prover_set_wire_variables has not been called");
+    if (vec ? witness_len != vars_n() : witness_len != (uint64_t)W * n)
         fail(MZK_ERR_INVALID_ARG, vec ? "witness_len != the n_vars of mzk_prover_set_wire_variables" : "witness_len != num_wire_types * domain size");
     if (!pi_rows && n_pi > n) fail(MZK_ERR_INVALID_ARG, "more public inputs than rows");
     for (uint64_t i = 0; pi_rows && i < n_pi; i++)
@@ -23,8 +23,8 @@ void ProverT<FrP, CURVE>::check_witness(int kind, const void* witness, uint64_t 
     in.d_sel_coeffs = static_cast<const uint32_t*>(fix(0));
     in.kind = kind;
     in.witness = witness;
-    in.d_vars = static_cast<const uint32_t*>(vars.p);
-    in.n_vars = n_vars;
+    in.d_vars = static_cast<const uint32_t*>(vars_dev());
+    in.n_vars = vars_n();
     in.pi_rows = pi_rows; in.pi = pi; in.n_pi = n_pi;
-    ck(mzk_ctx_check_witness(pk, &in, out, S));
+    ck(mzk_ctx_check_witness(key().pk, &in, out, S));
 }

@@ -43,20 +43,20 @@ void ProverT<FrP, CURVE>::round1(int kind, const void* witness, uint64_t witness
         ck(mzk_ntt_dev(CURVE, coeff.p, n, log_n, 1, nullptr, W, n, S));
     } else if (kind == MZK_WITNESS_HOST_VECTOR || kind == MZK_WITNESS_DEV_VECTOR) {
         // the witness vector crosses PCIe; `witness[wire_variable(i, j)]` (constraint_system.rs:1239) is gathered on the device
-        if (!vars.p) fail(MZK_ERR_STATE, "mzk_prover_set_wire_variables has not been called");
-        if (witness_len != n_vars) fail(MZK_ERR_INVALID_ARG, "witness_len != the n_vars of mzk_prover_set_wire_variables");
+        if (!vars_dev()) fail(MZK_ERR_STATE, "mzk_prover_set_wire_variables has not been called");
+        if (witness_len != vars_n()) fail(MZK_ERR_INVALID_ARG, "witness_len != the n_vars of mzk_prover_set_wire_variables");
         if (!wv.p) wv.alloc(cells);
         st.wire_values = wv.p;
         const void* d_wit = witness;
         if (kind == MZK_WITNESS_HOST_VECTOR) {
-            if (wit.elems < n_vars) wit.alloc(n_vars);
+            if (wit.elems < vars_n()) wit.alloc(vars_n());
             if (!copy_stream) ck(mzk_stream_create(&copy_stream));
             ck(mzk_stream_wait_stream(copy_stream, S));                                       // the previous proof is done with `wit`
-            ck(mzk_dev_upload_async(wit.p, witness, n_vars * EL, copy_stream));
+            ck(mzk_dev_upload_async(wit.p, witness, vars_n() * EL, copy_stream));
             ck(mzk_stream_wait_stream(S, copy_stream));
             d_wit = wit.p;
         }
-        ck(mzk_plonk_gather_witness_dev(d_wit, n_vars, vars.p, cells, wv.p, S));
+        ck(mzk_plonk_gather_witness_dev(d_wit, vars_n(), vars_dev(), cells, wv.p, S));
         ck(mzk_dev_copy(coeff.p, wv.p, cells * EL, S));
         ck(mzk_ntt_dev(CURVE, coeff.p, n, log_n, 1, nullptr, W, n, S));
     } else if (kind == MZK_WITNESS_HOST_WIRES) {
@@ -82,7 +82,7 @@ void ProverT<FrP, CURVE>::round1(int kind, const void* witness, uint64_t witness
     { std::vector<int> rs; for (int i = 0; i < W; i++) rs.push_back(i); mask(rs, blinders, 2); }
     tick.mark("r1_ntt_mask");
     std::vector<const void*> p; std::vector<uint64_t> l;
-    if (srs_lagrange) {
+    if (key().srs_lagrange) {
         // sum_i v_i [L_i(beta)]g + b_0 [Z_H(beta)]g + b_1 [beta Z_H(beta)]g: rows of n + 3 slots, the values, then the blinders
         if (!vals_ext.p) vals_ext.alloc((size_t)W * (n + 3));
         ck(mzk_dev_copy2d(vals_ext.p, (n + 3) * EL, st.wire_values, n * EL, n * EL, W, S));
@@ -92,7 +92,7 @@ void ProverT<FrP, CURVE>::round1(int kind, const void* witness, uint64_t witness
     } else {
         for (int i = 0; i < W; i++) { p.push_back(row(i)); l.push_back(n + 2); }
     }
-    commit(p, l, out, srs_lagrange);                                // (synchronises the null stream, which has waited for the copy stream: the
+    commit(p, l, out, key().srs_lagrange);                                // (synchronises the null stream, which has waited for the copy stream: the
     tick.mark("r1_commit");                                         // caller's host buffers are free again when this returns)
     stage = R1;
 }
@@ -104,10 +104,10 @@ void ProverT<FrP, CURVE>::round1_5(const uint64_t* tau, const uint64_t* blinders
     Tick tick(*this);
     st.tau = load(tau);
     const int H1 = rowH1();
-    ck(mzk_plookup_sorted_vec_dev(pk, st.wire_values, st.tau.l, table.p, lookup.p, sorted.p, S));
+    ck(mzk_plookup_sorted_vec_dev(key().pk, st.wire_values, st.tau.l, table.p, lookup.p, sorted.p, S));
     ck(mzk_dev_copy(hh.p, sorted.p, n * EL, S));
     ck(mzk_dev_copy(hh.at(n), sorted.at(n - 1), n * EL, S));
-    if (srs_lagrange) {
+    if (key().srs_lagrange) {
         // h_1, h_2 are committed from the sorted vector's VALUES (table entries and looked-up values: small numbers unless the circuit
         // looks up keyed tables) plus their three blinders, over the Lagrange-basis key -- as the wires in round 1
         if (!vals_ext.p) vals_ext.alloc((size_t)W * (n + 3));
@@ -119,7 +119,7 @@ void ProverT<FrP, CURVE>::round1_5(const uint64_t* tau, const uint64_t* blinders
     ck(mzk_dev_copy2d(row(H1), (n + 3) * EL, hh.p, n * EL, n * EL, 2, S));
     mask({H1, H1 + 1}, blinders, 3);
     tick.mark("r1_5_sorted_vec");
-    if (srs_lagrange) commit({vals_ext.p, vals_ext.at(n + 3)}, {n + 3, n + 3}, out, srs_lagrange);
+    if (key().srs_lagrange) commit({vals_ext.p, vals_ext.at(n + 3)}, {n + 3, n + 3}, out, key().srs_lagrange);
     else commit({row(H1), row(H1 + 1)}, {n + 3, n + 3}, out);
     tick.mark("r1_5_commit");
     stage = R1_5;

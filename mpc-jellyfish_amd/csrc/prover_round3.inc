@@ -10,14 +10,14 @@ void ProverT<FrP, CURVE>::quotient(const Fr& alpha) {
     // per OWN class: fold mod X^n - h_k^n, size-n coset NTTs, the fused kernel, size-n inverse coset NTT -> t mod (X^n - h_k^n), straight
     // into this class's slot of `rem` (the rows of the slab are read, not overwritten)
     if (!own.empty())
-        ck(mzk_plonk_quotient_chunked_flags_dev(pk, slab.p, n + 3, n + 3, st.pi_zero ? MZK_QUOTIENT_PI_ZERO : 0u, ultra ? st.tau.l : nullptr, alpha.l,
+        ck(mzk_plonk_quotient_chunked_flags_dev(key().pk, slab.p, n + 3, n + 3, st.pi_zero ? MZK_QUOTIENT_PI_ZERO : 0u, ultra ? st.tau.l : nullptr, alpha.l,
                                                 st.beta.l, st.gamma.l, rem.at((size_t)own[0] * n), S));
     if (world > 1) {
         // THE one exchange (SURVEY.md 8(e).3)
         const uint32_t first = own.empty() ? 0u : own[0];
         if (comm.exchange_classes) {
             ck(mzk_dev_sync());
-            if (comm.exchange_classes(comm.ctx, rem.p, n * EL, first, (uint32_t)own.size(), (uint32_t)classes.size())) fail(MZK_ERR_INVALID_ARG, "mzk_comm.exchange_classes failed");
+            if (comm.exchange_classes(comm.ctx, rem.p, n * EL, first, (uint32_t)own.size(), (uint32_t)key().classes.size())) fail(MZK_ERR_INVALID_ARG, "mzk_comm.exchange_classes failed");
         } else {
             // every rank pushes its class remainders into the same slots of every other rank's `rem`, device to device (xGMI peer
             // copies; n x 32 B per class and peer), then all ranks meet
@@ -32,11 +32,11 @@ void ProverT<FrP, CURVE>::quotient(const Fr& alpha) {
         }
     }
     // the inverse Vandermonde per coefficient index (replicated: every rank needs the quotient's coefficients for the split)
-    if (use_top) {
-        ck(mzk_plonk_quotient_top_dev(pk, slab.p, n + 3, n + 3, alpha.l, st.beta.l, st.gamma.l, top.p, nullptr, S));
-        ck(mzk_plonk_quotient_combine_top_dev(CURVE, log_n, classes.data(), (uint32_t)classes.size(), rem.p, top.p, (uint32_t)W + 3, quot.p, S));
+    if (key().use_top) {
+        ck(mzk_plonk_quotient_top_dev(key().pk, slab.p, n + 3, n + 3, alpha.l, st.beta.l, st.gamma.l, top.p, nullptr, S));
+        ck(mzk_plonk_quotient_combine_top_dev(CURVE, log_n, key().classes.data(), (uint32_t)key().classes.size(), rem.p, top.p, (uint32_t)W + 3, quot.p, S));
     } else {
-        ck(mzk_plonk_quotient_combine_classes_dev(CURVE, log_n, classes.data(), (uint32_t)classes.size(), rem.p, quot.p, S));
+        ck(mzk_plonk_quotient_combine_classes_dev(CURVE, log_n, key().classes.data(), (uint32_t)key().classes.size(), rem.p, quot.p, S));
     }
 }
 

@@ -8,7 +8,7 @@ void ProverT<FrP, CURVE>::round4(const uint64_t* zeta_p, uint64_t* out_evals) {
     need(R3, R4, "round 4 follows round 3");
     Tick tick(*this);
     const Fr zeta = st.zeta = load(zeta_p);
-    const Fr zeta_w = zeta * w_n;
+    const Fr zeta_w = zeta * key().w_n;
     const int sigma0 = nsel, tab0 = nsel + W, H1 = rowH1(), PL = rowPL();
     EvalBatch ev(*this);
     // the wires and, in the same launch, z and the public-input polynomial (rows W, W + 1; every row is zero above its own length):

@@ -23,7 +23,7 @@ auto ProverT<FrP, CURVE>::lin_poly_terms(const Fr& alpha_base) const -> std::vec
     const Fr vanish = pow_u64(zeta, n) - one;
     const Fr lagrange_1 = vanish * inv(nf * (zeta - one));
     Fr cf = alpha;
-    for (int j = 0; j < W; j++) cf = cf * (we[j] + beta * k[j] * zeta + gamma);
+    for (int j = 0; j < W; j++) cf = cf * (we[j] + beta * key().k[j] * zeta + gamma);
     terms.push_back({cf + alpha * alpha * lagrange_1, row(rowZ()), n + 3});
     cf = alpha * beta * st.perm_next_eval;
     for (int j = 0; j < W - 1; j++) cf = cf * (we[j] + beta * st.wire_sigma_evals[j] + gamma);
@@ -35,7 +35,7 @@ auto ProverT<FrP, CURVE>::lin_poly_terms(const Fr& alpha_base) const -> std::vec
         const Fr mt = em(pe[RANGE_TABLE], pe[Q_LOOKUP], pe[TABLE_DOM_SEP], pe[KEY_TABLE], we[3], we[4]);
         const Fr mt_next = em(pe[RANGE_TABLE_NEXT], pe[Q_LOOKUP_NEXT], pe[TABLE_DOM_SEP_NEXT], pe[KEY_TABLE_NEXT], pe[W_3_NEXT], pe[W_4_NEXT]);
         const Fr ml = em(we[5], pe[Q_LOOKUP], pe[Q_DOM_SEP], we[0], we[1], we[2]);
-        const Fr w_inv = inv(w_n);
+        const Fr w_inv = inv(key().w_n);
         const Fr lagrange_n = vanish * w_inv * inv(nf * (zeta - w_inv));
         const Fr a2 = alpha * alpha, a4 = a2 * a2, a5 = a4 * alpha, a6 = a4 * a2;
         const Fr b1 = one + beta, g1 = gamma * b1, zmg = zeta - w_inv;
@@ -61,7 +61,7 @@ auto ProverT<FrP, CURVE>::lin_poly_constant(const Fr& alpha_base) const -> Fr {
     for (int j = 0; j < W - 1; j++) acc = acc * (gamma + we[j] + beta * st.wire_sigma_evals[j]);
     t = t - acc;
     if (ultra) {
-        const Fr a3 = a2 * alpha, w_inv = inv(w_n);
+        const Fr a3 = a2 * alpha, w_inv = inv(key().w_n);
         const Fr lagrange_n = vanish * w_inv * inv(nf * (zeta - w_inv));
         const Fr g1 = gamma * (one + beta);
         const Fr pc = lagrange_n * (pe[H_1] - pe[H_2_NEXT] - a2) - alpha * lagrange_1
@@ -150,7 +150,7 @@ void ProverT<FrP, CURVE>::openings_ranged(const std::vector<Term>& lin_terms, co
         }
         return o;
     };
-    const Fr zw = zeta * w_n;
+    const Fr zw = zeta * key().w_n;
     std::vector<Term> open_terms = lin_terms, shift_terms;         // 1 * lin + sum_i v^(i+1) p_i
     Fr c = v;
     for (auto& p : open_polys) { open_terms.push_back({c, p.p, p.len}); c = c * v; }
@@ -212,7 +212,7 @@ void ProverT<FrP, CURVE>::round5(const std::vector<ProverBase*>& inst, const uin
         open_polys.push_back({Fr::one(), lin.p, n + 3});
         for (ProverBase* b : inst) static_cast<ProverT*>(b)->open_lists(open_polys, shifted_polys);
         batched_witness(open_polys, v, zeta, opening, rem_dev());
-        batched_witness(shifted_polys, v, zeta * w_n, shifted);
+        batched_witness(shifted_polys, v, zeta * key().w_n, shifted);
         ck(mzk_dev_download_async(static_cast<uint8_t*>(stage_back.reserve(64)) + 32, rem_dev(), EL, S));       // read after the commitments, copied before them
         tick.mark("r5_polys");
         commit({opening.p, shifted.p}, {n + 2, n + 2}, out);

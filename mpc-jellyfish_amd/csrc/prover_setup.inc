@@ -10,32 +10,30 @@ ProverT<FrP, CURVE>::ProverT(int log_n_, int W_, const uint64_t* sel, const uint
     curve = CURVE; log_n = log_n_; W = W_; ultra = W_ == 6; nsel = ultra ? 14 : 13;
     rows = W + 2 + (ultra ? 3 : 0);
     n = 1ull << log_n; m = 8 * n;
-    srs = commit_key; srs_lagrange = lagrange_key;
+    key_ = std::make_shared<Key>();
+    Key& K = *key_;                                                // (the one place, with set / take_wire_variables, that writes the key part)
+    K.srs = commit_key; K.srs_lagrange = lagrange_key;
     if (cm) { comm = *cm; rank = cm->rank; world = cm->world; }
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && (!comm.all_gather || !comm.barrier)))
         fail(MZK_ERR_INVALID_ARG, "mzk_comm: 0 <= rank < world, all_gather and barrier callbacks required");
-    for (int i = 0; i < W; i++) k.push_back(load(k_mont + 4 * i));
+    for (int i = 0; i < W; i++) K.k.push_back(load(k_mont + 4 * i));
     std::tie(lo, hi) = shard_range(n + 3, rank, world);            // the proving key keeps trim(n + 2) = n + 3 powers (snark.rs:535, 561)
     uint64_t srs_len = 0;
-    ck(mzk_srs_len(srs, &srs_len));
+    ck(mzk_srs_len(K.srs, &srs_len));
     const bool sliced = world > 1 && srs_len == hi - lo;           // the key IS this rank's range of the SRS (mzk_srs_slice)
     if (sliced) key_first = lo;
     else if (srs_len < n + 3) fail(MZK_ERR_INVALID_ARG, "commit key too small: need domain size + 3 powers (srs.rs:88), or exactly this rank's point range");
-    if (srs_lagrange) {
-        ck(mzk_srs_len(srs_lagrange, &srs_len));
+    if (K.srs_lagrange) {
+        ck(mzk_srs_len(K.srs_lagrange, &srs_len));
         if (sliced ? srs_len != hi - lo : srs_len < n + 3)
             fail(MZK_ERR_INVALID_ARG, "Lagrange-basis key: 2^log_n + 3 points (mzk_srs_lagrange_from_srs(.., log_n, 3)), sliced like the commit key");
     }
     const int nfix = nsel + W + (ultra ? 4 : 0);
-    // a stream of the context (two per context, handed out in turn), made in one burst with the MSM's sort streams so that none of them
-    // shares a hardware queue with another (csrc/msm.hip sort_stream_init); the handle does not own it
-    static std::atomic<uint32_t> next_stream[16];                        // per logical device: its first handle takes stream 0, the next stream 1, ..
-    int32_t dev_now = 0;
-    ck(mzk_get_device(&dev_now));
-    if (!std::getenv("MZK_PROVER_NULL_STREAM")) ck(mzk_ctx_prover_stream(next_stream[dev_now & 15]++, &S));
-    fixed.alloc((size_t)nfix * n);
-    ck(mzk_dev_memset(fixed.p, 0, (size_t)nfix * n * EL, S));
+    take_stream();
+    K.fixed.alloc((size_t)nfix * n);
+    ck(mzk_dev_memset(K.fixed.p, 0, (size_t)nfix * n * EL, S));
     sync_stream();                                                 // the uploads below are synchronous copies, not ordered after S
+    auto fix = [&](int r) { return K.fixed.at((size_t)r * n); };
     auto up_rows = [&](int first, int cnt, const uint64_t* src) {
         if (at == COEFFS_ON_DEVICE) ck(mzk_dev_copy2d(fix(first), n * EL, src, poly_len * EL, poly_len * EL, (uint64_t)cnt, S));   // (complete before the call: mzk_prover_create_from_circuit)
         else if (poly_len == n) ck(mzk_dev_upload(fix(first), src, (size_t)cnt * n * EL));
@@ -50,39 +48,78 @@ ProverT<FrP, CURVE>::ProverT(int log_n_, int W_, const uint64_t* sel, const uint
     // rest -- 5 for TurboPlonk, 6 for UltraPlonk -- and only those are resident and evaluated; the polynomial so recovered has the
     // expected degree whatever the witness, which is why round 5 checks the quotient identity at zeta.  Tiny domains: W + 1 classes
     // with one spare coefficient above the expected degree (or an unsatisfied witness could not trip WrongQuotientPolyDegree), else all 8.
-    use_top = n > (uint64_t)W + 2 && n >= 8;
-    const uint32_t needed = use_top ? (uint32_t)W : (((uint64_t)W * (n + 1) + 2 < (uint64_t)(W + 1) * n - 1 && W + 1 <= 8) ? (uint32_t)W + 1 : 8u);
-    for (uint32_t kc = 0; kc < needed; kc++) classes.push_back(kc);
+    K.use_top = n > (uint64_t)W + 2 && n >= 8;
+    const uint32_t needed = K.use_top ? (uint32_t)W : (((uint64_t)W * (n + 1) + 2 < (uint64_t)(W + 1) * n - 1 && W + 1 <= 8) ? (uint32_t)W + 1 : 8u);
+    for (uint32_t kc = 0; kc < needed; kc++) K.classes.push_back(kc);
     own = class_range(rank, world, needed);                        // contiguous blocks of ceil(needed / world); the last ranks may own none
     // a rank that owns no class still registers one (a key cannot be empty); it is never evaluated
-    const std::vector<uint32_t> resident = own.empty() ? std::vector<uint32_t>{classes.back()} : own;
-    rem.alloc(classes.size() * n);                                 // the remainders of ALL needed classes: own ones computed here, the others received
-    top.alloc(16);
-    slab.alloc((size_t)rows * (n + 3)); quot.alloc(m); coeff.alloc((size_t)(W + 1) * n);
-    split.alloc((size_t)W * (n + 3)); lin.alloc(n + 4); batch.alloc(n + 4); opening.alloc(n + 3); shifted.alloc(n + 3); tmp.alloc(64); deg.alloc(1);
-    if (ultra) { hh.alloc(2 * n); table.alloc(n); lookup.alloc(n); sorted.alloc(2 * n); }
-    // (last: a constructor that throws runs no destructor, and the key is the one resource the members do not release themselves)
-    ck(mzk_ctx_pk_register_chunked(CURVE, log_n, W, sel, sig, tab, poly_len, k_mont, resident.data(), (uint32_t)resident.size(), at == COEFFS_ON_DEVICE, &pk));
-    w_n = root_of_unity<FrP>(log_n);
-    gen = Fr::from_words(FrP::GENERATOR);
+    const std::vector<uint32_t> resident = own.empty() ? std::vector<uint32_t>{K.classes.back()} : own;
+    alloc_workspace();
+    // (last: were the constructor to throw after it, ~Key would release it with the members)
+    ck(mzk_ctx_pk_register_chunked(CURVE, log_n, W, sel, sig, tab, poly_len, k_mont, resident.data(), (uint32_t)resident.size(), at == COEFFS_ON_DEVICE, &K.pk));
+    K.w_n = root_of_unity<FrP>(log_n);
+    K.gen = Fr::from_words(FrP::GENERATOR);
+}
+
+// mzk_prover_fork: a new slot on parent's key.  No SRS work, no NTT, no upload: the shape, a stream and the workspace the constructor above
+// allocates.  Reads nothing of parent's that a proof in flight on it writes (its workspace, state, stage, timings).
+template <class FrP, int CURVE>
+ProverT<FrP, CURVE>::ProverT(const ProverT& parent) {
+    if (parent.world > 1)
+        fail(MZK_ERR_UNSUPPORTED, "mzk_prover_fork: a prover with an mzk_comm of world > 1 cannot be forked (two slots would interleave one communicator's collectives)");
+    curve = parent.curve; log_n = parent.log_n; W = parent.W; ultra = parent.ultra; nsel = parent.nsel; n = parent.n; device = parent.device;
+    rows = parent.rows; m = parent.m;
+    lo = parent.lo; hi = parent.hi; key_first = parent.key_first; own = parent.own;
+    key_ = parent.key_;
+    take_stream();
+    alloc_workspace();
 }
 
 template <class FrP, int CURVE>
 ProverT<FrP, CURVE>::~ProverT() {
-    (void)mzk_dev_sync();
-    if (pk) (void)mzk_plonk_pk_release(pk);
+    (void)mzk_dev_sync();                                          // (the key part, once its last holder goes, does the same before it releases the key)
     if (copy_stream) (void)mzk_stream_destroy(copy_stream);
+}
+
+// a stream of the context (two per context, handed out in turn), made in one burst with the MSM's sort streams so that none of them
+// shares a hardware queue with another (csrc/msm.hip sort_stream_init); the handle does not own it
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::take_stream() {
+    static std::atomic<uint32_t> next_stream[16];                        // per logical device: its first handle takes stream 0, the next stream 1, ..
+    int32_t dev_now = 0;
+    ck(mzk_get_device(&dev_now));
+    if (!std::getenv("MZK_PROVER_NULL_STREAM")) ck(mzk_ctx_prover_stream(next_stream[dev_now & 15]++, &S));
+}
+
+// the workspace of one proof in flight; the rounds allocate the rest on first use (wv, wit, vals_ext, qsum)
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::alloc_workspace() {
+    rem.alloc(key().classes.size() * n);                           // the remainders of ALL needed classes: own ones computed here, the others received
+    top.alloc(16);
+    slab.alloc((size_t)rows * (n + 3)); quot.alloc(m); coeff.alloc((size_t)(W + 1) * n);
+    split.alloc((size_t)W * (n + 3)); lin.alloc(n + 4); batch.alloc(n + 4); opening.alloc(n + 3); shifted.alloc(n + 3); tmp.alloc(64); deg.alloc(1);
+    if (ultra) { hh.alloc(2 * n); table.alloc(n); lookup.alloc(n); sorted.alloc(2 * n); }
 }
 
 template <class FrP, int CURVE>
 void ProverT<FrP, CURVE>::hbm_bytes(uint64_t* fixed_b, uint64_t* pk_b, uint64_t* ws_b) {
     uint64_t ws = 0;
-    for (const Buf* b : {&slab, &quot, &coeff, &split, &lin, &batch, &opening, &shifted, &hh, &table, &lookup, &sorted, &tmp, &deg, &rem, &wv, &wit, &top,
-                         &vals_ext, &qsum, &vars})
+    for (const Buf* b : std::initializer_list<const Buf*>{&slab, &quot, &coeff, &split, &lin, &batch, &opening, &shifted, &hh, &table, &lookup, &sorted, &tmp, &deg, &rem, &wv, &wit, &top,
+                         &vals_ext, &qsum, own_vars.p ? &own_vars : &key().vars})
         ws += b->bytes();
-    if (fixed_b) *fixed_b = fixed.bytes();
+    if (fixed_b) *fixed_b = key().fixed.bytes();
     if (ws_b) *ws_b = ws;
-    if (pk_b) ck(mzk_plonk_pk_hbm_bytes(pk, pk_b));
+    if (pk_b) ck(mzk_plonk_pk_hbm_bytes(key().pk, pk_b));
+}
+
+// of those bytes, the ones other living handles reach too: the key part (with its variable table, unless this handle uses one of its own)
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::shared_hbm_bytes(uint64_t* shared_b, uint32_t* sharers) {
+    const long holders = key_.use_count();
+    uint64_t pk_b = 0;
+    if (holders > 1) ck(mzk_plonk_pk_hbm_bytes(key().pk, &pk_b));
+    if (shared_b) *shared_b = holders > 1 ? key().fixed.bytes() + pk_b + (own_vars.p ? 0 : key().vars.bytes()) : 0;
+    if (sharers) *sharers = (uint32_t)holders;
 }
 
 // Jacobian sums of the coefficients [a, b) of every polynomial over the SRS points of the same indices
@@ -98,7 +135,7 @@ std::vector<uint64_t> ProverT<FrP, CURVE>::msm_partials(const std::vector<const 
         l[i] = s1 - s0;
         off[i] = (s1 > s0 ? s0 : a) - key_first;                     // (a sliced key starts at this rank's lo: a >= lo there)
     }
-    ck(mzk_msm_batch_dev(key ? key : srs, kp, p.data(), l.data(), off.data(), 1, xyz.data(), S));
+    ck(mzk_msm_batch_dev(key ? key : this->key().srs, kp, p.data(), l.data(), off.data(), 1, xyz.data(), S));
     return xyz;
 }
 
@@ -123,7 +160,7 @@ template <class FrP, int CURVE>
 void ProverT<FrP, CURVE>::commit_slices(const std::vector<const void*>& slices, const std::vector<uint64_t>& lens, uint64_t* out_xy) {
     const uint32_t kp = (uint32_t)slices.size();
     std::vector<uint64_t> off(kp, lo - key_first), xyz((size_t)kp * 3 * QL);
-    ck(mzk_msm_batch_dev(srs, kp, slices.data(), lens.data(), off.data(), 1, xyz.data(), S));
+    ck(mzk_msm_batch_dev(key().srs, kp, slices.data(), lens.data(), off.data(), 1, xyz.data(), S));
     combine_partials(xyz, out_xy);
 }
 
@@ -200,17 +237,20 @@ void ProverT<FrP, CURVE>::set_wire_variables(const uint32_t* v, uint64_t nv) {
     const size_t cnt = (size_t)W * n;
     for (size_t i = 0; i < cnt; i++)
         if (v[i] >= nv) fail(MZK_ERR_INVALID_ARG, "wire_variables: variable index " + std::to_string(v[i]) + " >= number of variables " + std::to_string(nv));
-    vars.alloc((cnt * 4 + EL - 1) / EL);
-    ck(mzk_dev_upload(vars.p, v, cnt * 4));
-    n_vars = nv;
+    // a key with other holders is theirs too: the table is replaced for this handle alone (copy-on-write)
+    const bool sole = key_.use_count() == 1;
+    Buf& dst = sole ? key_->vars : own_vars;
+    dst.alloc((cnt * 4 + EL - 1) / EL);
+    ck(mzk_dev_upload(dst.p, v, cnt * 4));
+    (sole ? key_->n_vars : own_n_vars) = nv;
+    if (sole && own_vars.p) { sync_stream(); Buf().swap(own_vars); own_n_vars = 0; }   // (set while the key was shared; the handle is alone again)
 }
 
 // the same table, resident already and validated where it was sorted (mzk_prover_create_from_circuit): the buffer changes hands
 template <class FrP, int CURVE>
 void ProverT<FrP, CURVE>::take_wire_variables(Buf& d_vars, uint64_t nv) {
-    std::swap(vars.p, d_vars.p);
-    std::swap(vars.elems, d_vars.elems);
-    n_vars = nv;
+    key_->vars.swap(d_vars);                                       // (at construction: the key has one holder)
+    key_->n_vars = nv;
 }
 
 template <class FrP, int CURVE>

@@ -14,6 +14,10 @@
 // --gpus G: G devices driven from this ONE process, one host thread per device (ShardedProver, mzk_prover.hpp): commitments sharded by
 // point range, the quotient by residue class with one device-to-device exchange, rounds 4-5 by coefficient range; same proof bytes.
 // With MZK_VIRTUAL_DEVICES=G in the environment the G device contexts share one card (rehearsal on a one-GPU box).
+// --slots K (turbo, ultra; one device): K host threads prove `reps` proofs each on ONE proving key through K slots -- the prover and K - 1
+// forks of it (mzk_prover_fork) -- and one JSON line reports proofs per second (against one slot alone), the family's HBM from
+// mzk_prover_hbm_bytes / mzk_prover_shared_hbm_bytes, and with --check-agree whether every proof equals the one a single slot makes
+// from the same rng seed.
 //   mzk_prove <curve> link <num_gates_1> <num_gates_2> <alignment> <offset> <size> [reps]
 //   mzk_prove <curve> batch <turbo|ultra> <range_bit_len> <num_gates_1> <num_gates_2> ...
 // PlonkKzgSnark::batch_prove: one aggregated BatchProof over bench circuits of one domain size; prints its bytes.
@@ -33,6 +37,7 @@ struct Options {
     int host_witness = 0;         // --host-witness: every proof uploads its W x n wire values from page-locked host memory;
                                   // --host-witness-vars: only the witness vector, gathered per wire on the device
     bool check_agree = false;     // --check-agree: every rank's proof bytes are compared (tests)
+    int slots = 0;                // --slots K: K threads on one key through K slots (run_slots)
     const char* srs_path = nullptr;  // --srs FILE: the commit key from a serialized setup
     bool slice_srs = true;        // --no-slice: with --gpus G every rank keeps the whole commit key (and its table) instead of its point range
     bool device_preprocess = false;  // --device-preprocess: the proving key from the circuit's selector values and variable table, permutation and
@@ -126,6 +131,70 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     return 0;
 }
 
+// --slots K: K proofs in flight on ONE key.  Every thread draws from its own rng with the bench's seed, so that proof i of every slot is
+// proof i of the single-slot run made first on the original prover.
+template <class C>
+int run_slots(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options& opt) {
+    using Fr = Fp64<typename C::Fr>;
+    using P = Prover<C>;
+    check(mzk_init(-1), "mzk_init");
+    int32_t device = 0;
+    check(mzk_get_device(&device), "mzk_get_device");
+    const BenchCircuit<C> cs = BenchCircuit<C>::generate(num_gates, ultra, range_bits);
+    const Fr beta = [&] { ChaChaRng r = test_rng(); return fr_rand<typename C::Fr>(r); }();
+    const auto beta_c = canonical(beta);
+    uint64_t srs = 0;
+    check(mzk_srs_generate_for_testing(C::ID, beta_c.data(), cs.n + 3, &srs), "mzk_srs_generate_for_testing");
+    const int K = opt.slots, count = std::max(reps, 1);
+    std::vector<std::unique_ptr<P>> slots;
+    slots.push_back(std::make_unique<P>(srs, cs));
+    for (int i = 1; i < K; i++) slots.push_back(slots[i % 2 ? 0 : i - 1]->fork());           // forks of the prover and forks of forks: all peers
+    std::vector<P*> family;
+    for (auto& s : slots) family.push_back(s.get());
+    const typename P::Hbm hbm = slots[0]->hbm();
+    const uint64_t family_bytes = P::family_hbm_bytes(family);
+    // `count` proofs on one slot; the first call of each pass is warm-up and not timed
+    auto pass = [&](P& p, std::vector<std::vector<uint8_t>>& out) {
+        ChaChaRng rng = test_rng();
+        (void)fr_rand<typename C::Fr>(rng);                                 // the trapdoor's draw (bench.rs:50-54): the blinders follow it
+        for (int i = 0; i < count; i++) out.push_back(p.prove(rng, cs).serialize_compressed());
+    };
+    std::vector<std::vector<uint8_t>> alone, warm;
+    pass(*slots[0], warm);
+    auto t0 = std::chrono::steady_clock::now();
+    pass(*slots[0], alone);
+    const double alone_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (int i = 1; i < K; i++) { ChaChaRng rng = test_rng(); (void)slots[i]->prove(rng, cs); }                          // warm-up of the other slots
+    std::vector<std::vector<std::vector<uint8_t>>> got(K);
+    std::vector<std::exception_ptr> errors(K);
+    std::vector<std::thread> threads;
+    t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < K; i++)
+        threads.emplace_back([&, i] {
+            try {
+                check(mzk_set_device(device), "mzk_set_device");
+                pass(*slots[i], got[i]);
+            } catch (...) { errors[i] = std::current_exception(); }
+        });
+    for (auto& t : threads) t.join();
+    const double slots_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    for (auto& e : errors) if (e) std::rethrow_exception(e);
+    bool agree = true;
+    for (int i = 0; i < K; i++) agree = agree && got[i] == alone;
+    std::printf("{\"curve\": %d, \"plonk_type\": \"%s\", \"num_gates\": %llu, \"log_n\": %d, \"slots\": %d, \"proofs_per_slot\": %d, \"proofs_per_s\": %.3f, "
+                "\"one_slot_proofs_per_s\": %.3f, \"hbm_fixed_bytes\": %llu, \"hbm_proving_key_bytes\": %llu, \"hbm_workspace_bytes\": %llu, \"hbm_shared_bytes\": %llu, "
+                "\"sharers\": %u, \"family_hbm_bytes\": %llu",
+                C::ID, ultra ? "UltraPlonk" : "TurboPlonk", (unsigned long long)num_gates, cs.log_n, K, count, (double)K * count / slots_s, count / alone_s,
+                (unsigned long long)hbm.fixed, (unsigned long long)hbm.proving_key, (unsigned long long)hbm.workspace, (unsigned long long)hbm.shared, hbm.sharers,
+                (unsigned long long)family_bytes);
+    if (opt.check_agree) std::printf(", \"slots_agree_with_one_slot\": %s", agree ? "true" : "false");
+    std::printf(", \"proof_hex\": \"%s\"}\n", [&] { std::string h; static const char* d = "0123456789abcdef"; for (uint8_t b : alone[0]) { h.push_back(d[b >> 4]); h.push_back(d[b & 15]); } return h; }().c_str());
+    std::fflush(stdout);
+    slots.clear();
+    (void)mzk_srs_release(srs);
+    return opt.check_agree && !agree ? 1 : 0;
+}
+
 static std::string to_hex(const std::vector<uint8_t>& bytes) {
     std::string hex;
     static const char* d = "0123456789abcdef";
@@ -202,6 +271,7 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--host-witness") opt.host_witness = 1;
         else if (a == "--host-witness-vars") opt.host_witness = 2;
         else if (a == "--check-agree") opt.check_agree = true;
+        else if (a == "--slots" && i + 1 < argc_in) opt.slots = std::atoi(argv_in[++i]);
         else if (a == "--check-witness") opt.check_witness = true;
         else if (a == "--device-preprocess") opt.device_preprocess = true;
         else if (a == "--lagrange") opt.lagrange = 1;
@@ -256,6 +326,15 @@ int main(int argc_in, char** argv_in) {
     const bool ultra = std::string(argv[2]) == "ultra";
     const uint64_t gates = std::strtoull(argv[3], nullptr, 10);
     const int reps = argc > 4 ? std::atoi(argv[4]) : 0, range_bits = argc > 5 ? std::atoi(argv[5]) : 8;
+    if (opt.slots) {
+        if (opt.slots < 1 || opt.slots > 16 || opt.gpus != 1) { std::fprintf(stderr, "mzk_prove: --slots 1..16, on one device (a sharded prover cannot be forked)\n"); return 2; }
+        try {
+            return curve == 0 ? run_slots<Bls12_381>(ultra, gates, reps, range_bits, opt) : run_slots<Bn254>(ultra, gates, reps, range_bits, opt);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "mzk_prove: %s\n", e.what());
+            return 1;
+        }
+    }
     try {
         return curve == 0 ? run<Bls12_381>(ultra, gates, reps, range_bits, opt) : run<Bn254>(ultra, gates, reps, range_bits, opt);
     } catch (const std::exception& e) {

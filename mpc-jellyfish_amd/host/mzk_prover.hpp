@@ -385,6 +385,36 @@ struct Prover {
     Prover& operator=(const Prover&) = delete;
     ~Prover() { if (handle) (void)mzk_prover_destroy(handle); }
 
+    // Another slot on this prover's key (mzk_prover_fork): the key stays ONE copy in device memory, the slot has its own workspace and
+    // stream -- another instance of one batch_prove, or another proof in flight, from another host thread if wanted.  The slots are
+    // peers: destroyed in any order.  The verifying-key commitments are the key's, copied.
+    std::unique_ptr<Prover> fork() const {
+        std::unique_ptr<Prover> f(new Prover(*this, Slot{}));
+        check(mzk_prover_fork(handle, &f->handle), "mzk_prover_fork");
+        return f;
+    }
+    struct Hbm { uint64_t fixed = 0, proving_key = 0, workspace = 0, shared = 0; uint32_t sharers = 0; };
+    Hbm hbm() const {
+        Hbm h;
+        check(mzk_prover_hbm_bytes(handle, &h.fixed, &h.proving_key, &h.workspace), "mzk_prover_hbm_bytes");
+        check(mzk_prover_shared_hbm_bytes(handle, &h.shared, &h.sharers), "mzk_prover_shared_hbm_bytes");
+        return h;
+    }
+    // what a family of slots on one key holds: sum (fixed + proving key + workspace) - (sharers - 1) x shared
+    static uint64_t family_hbm_bytes(const std::vector<Prover*>& slots) {
+        uint64_t sum = 0;
+        Hbm h;
+        for (const Prover* p : slots) { h = p->hbm(); sum += h.fixed + h.proving_key + h.workspace; }
+        return slots.empty() ? 0 : sum - (uint64_t)(h.sharers - 1) * h.shared;
+    }
+
+  private:
+    struct Slot {};
+    Prover(const Prover& o, Slot)
+        : ultra(o.ultra), log_n(o.log_n), W(o.W), nsel(o.nsel), n(o.n), k(o.k), srs(o.srs), selector_comms(o.selector_comms), sigma_comms(o.sigma_comms) {}
+
+  public:
+
     static std::vector<Affine> points(const std::vector<uint64_t>& xy) {
         std::vector<Affine> out(xy.size() / (2 * QL));
         for (size_t i = 0; i < out.size(); i++) std::memcpy(out[i].data(), &xy[i * 2 * QL], sizeof(Affine));

@@ -127,6 +127,7 @@ _SIGS = {
     "mzk_prover_create_from_circuit_dev": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                            C.c_void_p, C.POINTER(C.c_uint64)],
     "mzk_prover_destroy": [C.c_uint64],
+    "mzk_prover_fork": [C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_prover_vk_commitments": [C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_prover_set_wire_variables": [C.c_uint64, C.c_void_p, C.c_uint64],
     "mzk_prover_round1": [C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
@@ -143,6 +144,7 @@ _SIGS = {
     "mzk_prover_profile": [C.c_uint64, C.c_int32],
     "mzk_prover_timings": [C.c_uint64, C.c_char_p, C.c_uint64],
     "mzk_prover_hbm_bytes": [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "mzk_prover_shared_hbm_bytes": [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)],
 }
 _STR_FUNCS = ("mzk_strerror", "mzk_last_error", "mzk_version")
 EXPORTS = tuple(_SIGS) + _STR_FUNCS

@@ -283,6 +283,25 @@ class TurboPlonkProver:
         self._own_table = True
         return self
 
+    def fork(self) -> "TurboPlonkProver":
+        """Another slot on the same proving key (mzk_prover_fork): a prover that shares this one's key in HBM -- coefficient forms, class
+        evaluations, variable table -- and has its own workspace, state and stream, so that it can be another instance of one
+        `batch_prove` or carry another proof in flight (from another thread too).  Same curve, domain, `k`, commit key and Lagrange key
+        objects; the fork owns none of them (`owned_keys` stays with the prover snark.preprocess returned: release that one last, or
+        keep the keys alive some other way, while forks still prove).  Forks and parent are peers: `release()` in any order, the key
+        lives until the last of them is gone.  Not for a prover with a `comm` of more than one rank."""
+        h = C.c_uint64()
+        _check(_lib.load().mzk_prover_fork(self.handle, C.byref(h)), "mzk_prover_fork")
+        f = type(self).__new__(type(self))
+        for name in ("curve", "n", "log_n", "k", "ck", "lagrange_ck", "W", "ultra", "nsel"):
+            setattr(f, name, getattr(self, name))
+        f._adopt(h.value, self.comm)
+        f._vk, f._pvk = self._vk, self._pvk                               # (of the key: the same for every slot)
+        for name in ("_own_table", "_vars_of"):      # the variable table is shared until one of them replaces its own
+            if name in self.__dict__:
+                setattr(f, name, getattr(self, name))
+        return f
+
     def release(self):
         if self.handle:
             _check(_lib.load().mzk_prover_destroy(self.handle), "mzk_prover_destroy")
@@ -320,6 +339,13 @@ class TurboPlonkProver:
         a, b, w = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(_lib.load().mzk_prover_hbm_bytes(self.handle, C.byref(a), C.byref(b), C.byref(w)), "mzk_prover_hbm_bytes")
         return {"fixed_coefficient_forms": a.value, "proving_key_evaluations": b.value, "prover_workspace": w.value}
+
+    def shared_hbm_bytes(self):
+        """(bytes among those of hbm_bytes() that other living handles on this key hold too, handles on the key counting this one):
+        a family on one key holds sum(hbm_bytes) - (sharers - 1) * shared."""
+        b, s = C.c_uint64(), C.c_uint32()
+        _check(_lib.load().mzk_prover_shared_hbm_bytes(self.handle, C.byref(b), C.byref(s)), "mzk_prover_shared_hbm_bytes")
+        return b.value, s.value
 
     # ---- argument plumbing ---------------------------------------------------------------------------------------------------
     def _mont(self, ints):

@@ -307,7 +307,8 @@ def draw_batch_blinders(curve, rng: _rng.ChaChaRng, num_wire_types: int, ultras:
 
 def batch_prove(rng: _rng.ChaChaRng, circuits: list, pks: list, extra_transcript_init_msg: bytes | None = None):
     """PlonkKzgSnark::batch_prove (snark.rs:64-78): one aggregated proof for several instances of one domain size.
-    Returns (BatchProofCore, compressed BatchProof bytes)."""
+    Returns (BatchProofCore, compressed BatchProof bytes).  To put one circuit three times into an aggregate pass
+    `[pk, pk.fork(), pk.fork()]`: the forks share pk's key on the device and bring a workspace each (a repeated prover is refused)."""
     from . import batch as _batch
     if not circuits:
         raise ValueError("zero number of circuits/proving keys")

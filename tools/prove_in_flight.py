@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""tools/prove_in_flight.py [--log-n 20] [--in-flight 1,2,3] [--reps 10] [--dense] -- K proofs IN FLIGHT on ONE card.
+"""tools/prove_in_flight.py [--log-n 20] [--in-flight 1,2,3] [--reps 10] [--dense] [--shared-key] -- K proofs IN FLIGHT on ONE card.
 
 K host threads, each bound to its own device context of libmi355zk (MZK_VIRTUAL_DEVICES=K maps K contexts onto the one GPU: own
 lock, workspace, streams, keys), each proving the same 2^log_n-gate bench circuit through the round-level C ABI (mzk_prover_*) `reps`
 times: proofs/s of the card against 1000 / prove_ms of one prover alone.  What overlaps: the host Horner tails, transcript hashing,
 blinder draws and the launch gaps of one proof with the kernels of the other -- and, when the provers run on their own streams, the
 latency-bound narrow levels of one MSM reduction with the accumulation of the other.
+--shared-key: ONE device context instead, with one prover and K - 1 forks of it (TurboPlonkProver.fork): K slots on one proving key in
+HBM, one device lock, one shared scratch, the context's two prover streams handed out in turn.  The result then also carries the
+family's HBM from mzk_prover_hbm_bytes / mzk_prover_shared_hbm_bytes.
 Prints one JSON line.  (The process sets MZK_VIRTUAL_DEVICES itself, before the library is loaded.)"""
 import argparse
 import hashlib
@@ -19,8 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, check=False):
-    os.environ["MZK_VIRTUAL_DEVICES"] = str(max(ks))
+def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, check=False, shared_key=False):
+    os.environ["MZK_VIRTUAL_DEVICES"] = str(1 if shared_key else max(ks))
+    ctx = (lambda k: 0) if shared_key else (lambda k: k)                 # the device context slot k lives on
     if os.environ.get("MZK_INFLIGHT_HW_QUEUES"):                          # (experiment: more hardware queues for the K x 4 streams; read by HIP at start-up)
         os.environ["GPU_MAX_HW_QUEUES"] = os.environ["MZK_INFLIGHT_HW_QUEUES"]
     import torch
@@ -37,12 +41,16 @@ def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, c
 
     def setup(k):
         try:
-            mlib.check(L.mzk_init(k), "mzk_init")
+            mlib.check(L.mzk_init(ctx(k)), "mzk_init")
             rng = mj.rng.test_rng()
             beta = mj.rng.fr_rand(curve, rng)
-            ck = mj.UnivariateProverParam.gen_srs_for_testing(curve, beta, n + 2)
-            cs = mj.snark.gen_circuit_for_bench(curve, n, plonk_type, **({"dense_seed": 77} if dense else {}))
-            pk = native.preprocess(ck, cs, lagrange=False if dense else None)
+            if shared_key and k:                                          # another slot on slot 0's key: its circuit, no SRS of its own
+                _, cs, pk0, _ = state[0]
+                ck, pk = None, pk0.fork()
+            else:
+                ck = mj.UnivariateProverParam.gen_srs_for_testing(curve, beta, n + 2)
+                cs = mj.snark.gen_circuit_for_bench(curve, n, plonk_type, **({"dense_seed": 77} if dense else {}))
+                pk = native.preprocess(ck, cs, lagrange=False if dense else None)
             for _ in range(3):
                 native.prove(rng, cs, pk)
             torch.cuda.synchronize()
@@ -64,7 +72,7 @@ def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, c
 
         def work(k):
             try:
-                mlib.check(L.mzk_init(k), "mzk_init")
+                mlib.check(L.mzk_init(ctx(k)), "mzk_init")
                 rng, cs, pk, _ = state[k]
                 start.wait()
                 for _ in range(reps):
@@ -98,7 +106,7 @@ def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, c
 
         def work_check(k):
             try:
-                mlib.check(L.mzk_init(k), "mzk_init")
+                mlib.check(L.mzk_init(ctx(k)), "mzk_init")
                 _, cs, pk, _ = state[k]
                 start.wait()
                 for _ in range(4):
@@ -118,7 +126,7 @@ def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, c
     # every context must emit the same bytes for the same rng stream
     for k in range(K):
         def one(k=k):
-            mlib.check(L.mzk_init(k), "mzk_init")
+            mlib.check(L.mzk_init(ctx(k)), "mzk_init")
             _, cs, pk, _ = state[k]
             digests.add(hashlib.sha256(native.prove(mj.rng.test_rng(), cs, pk)[1]).hexdigest()[:16])
         t = threading.Thread(target=one)
@@ -127,18 +135,26 @@ def measure(log_n, ks, reps, dense=False, plonk_type="TurboPlonk", curve_id=0, c
     res = {"log_n": log_n, "plonk_type": plonk_type, "curve": curve.name, "dense_witness": dense, "reps_per_prover": reps,
            "in_flight": {str(k): v for k, v in out.items()}, "contexts_agree_on_proof": len(digests) == 1,
            "proofs_made_concurrently_identical": concurrent_ok}
+    if shared_key:
+        hb = [state[k][2].hbm_bytes() for k in range(K)]
+        shared, sharers = state[0][2].shared_hbm_bytes()
+        res["shared_key"] = True
+        res["hbm_per_slot"] = hb[0]
+        res["hbm_shared_bytes"], res["sharers"] = shared, sharers
+        res["family_hbm_bytes"] = sum(sum(h.values()) for h in hb) - (sharers - 1) * shared
     if 1 in out:
         for k, v in out.items():
             if k != 1:
                 res["gain_%d_in_flight" % k] = round(v["proofs_per_s"] / out[1]["proofs_per_s"], 3)
     for k in range(K):
         def rel(k=k):
-            mlib.check(L.mzk_init(k), "mzk_init")
+            mlib.check(L.mzk_init(ctx(k)), "mzk_init")
             _, _, pk, ck = state[k]
-            if pk.lagrange_ck is not None:
+            if ck is not None and pk.lagrange_ck is not None:           # (a fork's keys are slot 0's)
                 pk.lagrange_ck.release()
             pk.release()
-            ck.release()
+            if ck is not None:
+                ck.release()
         t = threading.Thread(target=rel)
         t.start()
         t.join()
@@ -152,7 +168,8 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--dense", action="store_true")
     ap.add_argument("--ultra", action="store_true", help="UltraPlonk over BN254 instead of TurboPlonk over BLS12-381")
+    ap.add_argument("--shared-key", action="store_true", help="one context, one prover and K - 1 forks of it, instead of K contexts with K provers")
     ap.add_argument("--check", action="store_true", help="also: K threads prove concurrently from identical rng streams; all proofs must be the same bytes")
     a = ap.parse_args()
     print(json.dumps(measure(a.log_n, [int(x) for x in a.in_flight.split(",")], a.reps, a.dense, "UltraPlonk" if a.ultra else "TurboPlonk",
-                             1 if a.ultra else 0, a.check)))
+                             1 if a.ultra else 0, a.check, a.shared_key)))
