@@ -665,6 +665,9 @@ MZK_API int32_t mzk_workspace_release(void);
 MZK_API int32_t mzk_launch_count(uint64_t* out_launches);
 /* Last MSM's shape: window bits, windows, buckets per window (for DESIGN.md's op counts). */
 MZK_API int32_t mzk_msm_last_shape(uint32_t* out_window_bits, uint32_t* out_windows, uint32_t* out_buckets);
+/* Rare-path sizing of the calling context's last MSM group: per-thread run cap, chunk-descriptor capacity and level-1 capacity per
+ * bucket set of its last MSM, and how many times the group ran (1 = no overflow).  For tests. */
+MZK_API int32_t mzk_msm_last_rare(uint32_t* out_cap, uint32_t* out_desc_cap, uint32_t* out_h1_cap, uint32_t* out_attempts);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,7 @@ struct Ctx {
     Workspace ws;
     std::vector<ProfRec> prof_recs;
     uint32_t last_c = 0, last_w = 0, last_m = 0;   // shape of the context's last MSM (mzk_msm_last_shape)
+    uint32_t last_cap = 0, last_desc_cap = 0, last_h1_cap = 0, last_attempts = 0;   // rare-path sizing of its last MSM group (mzk_msm_last_rare)
     std::map<uint64_t, Srs> srs;
     uint64_t next_handle = 1;
     IoSlot io[IO_SLOTS];

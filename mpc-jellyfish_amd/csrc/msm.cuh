@@ -598,7 +598,8 @@ __device__ __forceinline__ void msm_heavy_push(uint32_t b, uint32_t start, uint3
     const uint32_t r0 = atomicAdd(&cnt[0], n1);
     if (r0 + n1 > run_cap) return;                                     // cannot happen: run_cap >= 2 * entries / MSM_HEAVY_RUN + 2 (a heavy bucket holds more than MSM_HEAVY_RUN entries)
     constexpr uint32_t PER_RUN = MSM_HEAVY_RUN / MSM_HEAVY_PER_THREAD;
-    if (n1 == 1) { runs0[r0] = HeavyRun{start, rem, b, p1}; return; }
+    // (n1 >= 2 always: a heavy bucket holds more than cap + MSM_HEAVY_RUN entries, msm_is_heavy -- there is no single-run bucket whose
+    // level A stores into the bucket directly; the smallest heavy bucket has a full run and one of cap + 1 entries)
     const uint32_t p2 = atomicAdd(&cnt[3], n1);
     for (uint32_t i = 0; i < n1; i++)
         runs0[r0 + i] = HeavyRun{start + i * MSM_HEAVY_RUN, min(MSM_HEAVY_RUN, rem - i * MSM_HEAVY_RUN), MSM_HEAVY_DEST_PART | (p2 + i), p1 + i * PER_RUN};
@@ -635,7 +636,15 @@ __device__ __forceinline__ void msm_long_register(uint32_t w, uint32_t b, uint32
     }
     const uint32_t nch = (c - cap + cap - 1) / cap;
     const uint32_t pos = atomicAdd(&desc_count[w], nch);
-    if (pos + nch > desc_cap) return;                        // optimistic size (msm.hip): all of the bucket's chunks or none -- the host sees desc_count > desc_cap and runs the group again
+    if (pos + nch > desc_cap) {                              // optimistic size (msm.hip): all of the bucket's chunks or none -- the host sees desc_count > desc_cap and runs the group again
+        // The consumers of THIS attempt still walk min(desc_count, desc_cap) descriptors before the host sees the overflow, and the array is
+        // grow-only scratch that nobody clears.  Reservations only move forward, so exactly one bucket per window straddles the end
+        // (pos < desc_cap < pos + nch): it fills [pos, desc_cap) with descriptors that do nothing -- no entries to sum (len 0: the leaf
+        // stores infinity into its own slot of `parts`) and not the head of a run (idx_in_run != 0: the combination skips it).  An
+        // overflowed attempt touches only what it wrote.
+        for (uint32_t i = pos; i < desc_cap; i++) desc[(size_t)w * desc_cap + i] = LongDesc{b, offs_t, 0u, 1u, 0u};
+        return;
+    }
     for (uint32_t j = 0; j < nch; j++) {
         LongDesc d;
         d.bucket = b;

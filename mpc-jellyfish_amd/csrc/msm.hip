@@ -331,6 +331,7 @@ int32_t msm_group_dev(const MsmItem* items, int count, int c, int is_mont, const
             const uint32_t run_cap = (uint32_t)(2 * (n_sorted / MSM_HEAVY_RUN) + 2);
             const uint32_t h1_cap = std::min(h1_cap_max, h1_cap_of(n_sorted, run_cap, h1_frac));
             h1_caps[p] = h1_cap;
+            cur().last_cap = cap; cur().last_desc_cap = desc_cap; cur().last_h1_cap = h1_cap;
             count_ptrs[p] = desc_count;
             HeavyRun* heavy_runs = reinterpret_cast<HeavyRun*>(desc_count + (((size_t)sets * (1 + MSM_HEAVY_COUNTERS) + 3) & ~(size_t)3));
             uint32_t* h1 = parts + (size_t)sets * desc_cap * EC::PT_WORDS;                           // level-1 sums: one per MSM_HEAVY_PER_THREAD entries of a run
@@ -616,6 +617,7 @@ int32_t msm_batch_dev(const MsmItem* items, int count, int is_mont, const PreInf
             for (auto& it : run) it.d_bases = plain_table + it.base_off * aff_words;   // plain path: pointer to the first base
         for (int attempt = 0;; attempt++) {                          // (MSM_RETRY: the heavy-bucket scratch was too small; it has been enlarged)
             const int32_t rc = msm_group_dev<FR, EC>(run.data(), j - i, c, is_mont, p0 ? pre : PreInfo{}, st);
+            cur().last_attempts = (uint32_t)attempt + 1;
             if (rc == MSM_RETRY && attempt < 8) continue;
             if (rc == MSM_RETRY) { set_error("MSM heavy-bucket scratch: no fit after 8 attempts"); return MZK_ERR_UNSUPPORTED; }
             MZK_TRY(rc);

@@ -1255,5 +1255,13 @@ int32_t mzk_msm_last_shape(uint32_t* out_window_bits, uint32_t* out_windows, uin
     if (out_buckets) *out_buckets = cx_->last_m;
     return MZK_OK;
 }
+int32_t mzk_msm_last_rare(uint32_t* out_cap, uint32_t* out_desc_cap, uint32_t* out_h1_cap, uint32_t* out_attempts) {
+    ENTER_CUR();
+    if (out_cap) *out_cap = cx_->last_cap;
+    if (out_desc_cap) *out_desc_cap = cx_->last_desc_cap;
+    if (out_h1_cap) *out_h1_cap = cx_->last_h1_cap;
+    if (out_attempts) *out_attempts = cx_->last_attempts;
+    return MZK_OK;
+}
 
 }  // extern "C"

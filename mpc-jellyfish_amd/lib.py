@@ -113,6 +113,7 @@ _SIGS = {
     "mzk_msm_set_precompute": [C.c_int32],
     "mzk_srs_precompute": [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)],
     "mzk_msm_last_shape": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
+    "mzk_msm_last_rare": [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)],
     "mzk_srs_hbm_bytes": [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_plonk_pk_hbm_bytes": [C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_workspace_hbm_bytes": [C.POINTER(C.c_uint64)],
@@ -211,3 +212,11 @@ def msm_last_shape():
     a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
     L.mzk_msm_last_shape(C.byref(a), C.byref(b), C.byref(c))
     return a.value, b.value, c.value
+
+
+def msm_last_rare():
+    """(cap, desc_cap, h1_cap, attempts) of the last MSM group: include/mzk.h, mzk_msm_last_rare."""
+    L = load()
+    a, b, c, d = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    L.mzk_msm_last_rare(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return a.value, b.value, c.value, d.value

@@ -190,7 +190,9 @@ def test_heavy_bucket_scratch_grows_on_demand_and_the_group_runs_again(gpu, mj, 
     """Round 5: the level-1 sums of heavy buckets are sized for an eighth of the worst case; a batch whose scalars put EVERY entry into heavy
     buckets (all-equal scalars) overflows it, the library enlarges the scratch from the counters it reads with the results and runs the
     group again (csrc/msm.hip MSM_RETRY).  Same points as the oracle, from a freshly released workspace (the share starts again there),
-    and uniform scalars afterwards leave the scratch as it is."""
+    and uniform scalars afterwards leave the scratch as it is.  (The OTHER optimistic array, the chunk descriptors of the over-long buckets,
+    has its own tests: tests/test_msm_rare_paths_gpu.py, test_chunk_descriptor_overflow_reruns_the_group and
+    test_descriptor_and_heavy_overflow_in_one_group.)"""
     import ctypes as C
     c = mj.params.CURVES[0]
     n = (1 << 17) + 5
