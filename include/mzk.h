@@ -315,6 +315,24 @@ MZK_API int32_t mzk_plonk_wire_permutation_dev(const void* d_wire_variables, uin
  * mzk_plonk_wire_permutation_dev over num_wire_types * n cells (< 2^32).  Asynchronous. */
 MZK_API int32_t mzk_plonk_sigma_values_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_next_u32, const uint64_t* k_mont, void* d_out,
                                            void* stream);
+/* The way back, for a holder of a `ProvingKey` alone (which carries sigma but not `wire_variables`): the inverses of the two above.
+ * mzk_plonk_sigma_decode_dev: d_sigma_values = num_wire_types x n Montgomery elements, wire-major (what mzk_plonk_sigma_values_dev writes,
+ * or the forward NTTs of `ProvingKey::sigmas`); for every cell c = wire * n + row the cell (a, b) with sigma[c] = k_a w^b is found and
+ * d_out_next_u32[c] = a * n + b.  A hash join against the W n identity values (csrc/unperm.cuh: open addressing, full 32-byte key
+ * comparison; scratch: 4 B x the power of two >= 2 W n, the context's shared scratch).  Synchronises.  MZK_ERR_INVALID_ARG, with
+ * mzk_last_error() naming the lowest offending cell: a sigma value that is no identity value ("cell <c>: not k_a w^b"), or identity values
+ * that collide because the cosets k_a H are not disjoint (named as such).  MZK_ERR_UNSUPPORTED: num_wire_types * n >= 2^32. */
+MZK_API int32_t mzk_plonk_sigma_decode_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_sigma_values, const uint64_t* k_mont,
+                                           void* d_out_next_u32, void* stream);
+/* A wire-variable table from a permutation of `cells` cells (< 2^32: MZK_ERR_UNSUPPORTED at or above): cells in one cycle share a
+ * variable, in CANONICAL numbering -- the variable of a cell is the number of cycle minima below the minimum cell of its cycle, i.e.
+ * scanning the cells in order, the first unseen cell gets the next number; *out_n_vars = the number of cycles.  The compute_wire_permutation
+ * of that table is d_next_u32 again up to the order inside a cycle, and its copy constraints are the same.  Field-independent.
+ * d_next_u32 is validated: MZK_ERR_INVALID_ARG names the lowest cell holding an entry >= cells, else the lowest cell that is the
+ * successor of no cell (not a permutation).  Cycle minima by pointer doubling (csrc/unperm.cuh): ceil(log2(longest cycle)) + 1 passes
+ * over 16 B per cell of the context's shared scratch, the same work per pass whatever the cycle lengths; no order is left to atomics,
+ * the table is a function of d_next_u32 alone.  Synchronises. */
+MZK_API int32_t mzk_plonk_variables_from_permutation_dev(const void* d_next_u32, uint64_t cells, void* d_out_variables_u32, uint64_t* out_n_vars, void* stream);
 
 /* Round 2: replaces Arithmetization::compute_prod_permutation_polynomial
  * (relation/src/constraint_system.rs:1197-1223), whose loop performs one field division per gate.
@@ -427,7 +445,8 @@ MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uin
  * A prover and its forks (mzk_prover_fork) are such handles of one context, and may run their rounds from different host threads: the
  * key part they share is read-only once a second handle holds it, every handle has its own workspace, state and stream, and enqueueing is
  * under the context's device lock as for any two handles of one context.  One handle still belongs to one thread at a time, and
- * mzk_prover_fork / mzk_prover_set_wire_variables / mzk_prover_destroy of a handle must not run concurrently with each other on that handle.
+ * mzk_prover_fork / mzk_prover_set_wire_variables / mzk_prover_derive_wire_variables / mzk_prover_destroy of a handle must not run concurrently with
+ * each other on that handle.
  * Domains whose quotient does not fit the 8n-point domain (num_wire_types * (n + 1) + 2 >= 8 n: n = 2; n = 4 with six wire types) are
  * refused by mzk_prover_create with MZK_ERR_UNSUPPORTED. */
 #define MZK_ERR_WRONG_QUOTIENT_DEGREE (-9) /* PlonkError::WrongQuotientPolyDegree: the witness does not satisfy the circuit */
@@ -501,6 +520,19 @@ MZK_API int32_t mzk_prover_vk_commitments(uint64_t prover, uint64_t* out_xy_mont
  * MZK_ERR_INVALID_ARG -- the reference panics on such an index): resident circuit structure for MZK_WITNESS_*_VECTOR.  On a handle that
  * shares its key (mzk_prover_fork) the table is replaced for THAT handle only (copy-on-write): the other handles keep the shared one. */
 MZK_API int32_t mzk_prover_set_wire_variables(uint64_t prover, const uint32_t* wire_variables, uint64_t n_vars);
+/* The same table recovered from the key itself, for a prover created from coefficient forms (mzk_prover_create): W forward NTTs of the
+ * resident sigma polynomials onto the gate domain, mzk_plonk_sigma_decode_dev, mzk_plonk_variables_from_permutation_dev, all in the
+ * context's shared scratch, then installed exactly as mzk_prover_set_wire_variables installs one: copy-on-write on a handle that shares
+ * its key, counted in mzk_prover_hbm_bytes' workspace, the same concurrency rule, a proof in flight treated the same.  A table the handle
+ * already has is replaced; on any error the handle keeps what it had.  Variables are in canonical numbering (above): the representative
+ * of a variable -- its smallest cell -- is the minimum of its sigma-cycle, and a *_VECTOR witness holds, at index v, the value on the
+ * minimum cell of cycle v (build it from mzk_prover_get_wire_variables).  *out_n_vars (nullable): the number of variables.  With an
+ * mzk_comm: no collective call, any rank may call it alone (every rank holds the full coefficient forms).  Synchronises.
+ * MZK_ERR_INVALID_ARG: the sigma polynomials are not those of a permutation of the cells (mzk_last_error() as for the two primitives). */
+MZK_API int32_t mzk_prover_derive_wire_variables(uint64_t prover, uint64_t* out_n_vars);
+/* The resident table, whatever installed it: W x n u32 into out_wire_variables (host; NULL: only *out_n_vars is written), capacity_cells
+ * >= W x n.  MZK_ERR_INVALID_ARG: the handle has no table, or capacity_cells is too small.  Synchronises. */
+MZK_API int32_t mzk_prover_get_wire_variables(uint64_t prover, uint32_t* out_wire_variables, uint64_t capacity_cells, uint64_t* out_n_vars);
 #define MZK_WITNESS_DEV_WIRES 0   /* device, W x n: witness[wire_variable(i, j)] already gathered.  The prover keeps the POINTER, not a copy:
                                    * the buffer must stay valid and unmodified until round 2 (round 2.5 for UltraPlonk) has returned --
                                    * rounds 1.5 and 2 read the wire values again (sorted vector, permutation product) */
@@ -530,8 +562,9 @@ MZK_API int32_t mzk_prover_round1(uint64_t prover, int32_t witness_kind, const v
  *   copy    *_VECTOR kinds: the copy constraints hold by construction (copy_checked = 1, no failures).  *_WIRES kinds with a table from
  *           mzk_prover_set_wire_variables: the representative of a variable is its cell of smallest index wire * n + row; a cell fails
  *           iff its value differs from its representative's; copy_cell is the failing cell of smallest index.  *_WIRES kinds without a
- *           table: copy_checked = 0 and `kind` is decided by the other two families (sigma is not decoded back to cells).  A prover from
- *           mzk_prover_create_from_circuit has the table.
+ *           table: copy_checked = 0 and `kind` is decided by the other two families (nothing decodes sigma unless asked).  A prover from
+ *           mzk_prover_create_from_circuit has the table; any other gets it from mzk_prover_set_wire_variables or, from its own sigma
+ *           polynomials, mzk_prover_derive_wire_variables -- the counts, copy_cell and copy_rep_cell are then those of the circuit's table.
  * Counts and locations are exact and deterministic.  MZK_ERR_INVALID_ARG: null report, wrong witness_len, a *_VECTOR kind without
  * mzk_prover_set_wire_variables, a public-input row >= n.  MZK_ERR_UNSUPPORTED: copy check with W n >= 2^32.
  * The call synchronises, needs no SRS and makes no collective call (with an mzk_comm any rank may call it alone).  Like a new

@@ -65,6 +65,14 @@ extern "C" {
     pub fn mzk_prover_hbm_bytes(prover: u64, out_fixed: *mut u64, out_proving_key: *mut u64, out_workspace: *mut u64) -> i32;
     pub fn mzk_prover_shared_hbm_bytes(prover: u64, out_shared_bytes: *mut u64, out_sharers: *mut u32) -> i32;
     pub fn mzk_prover_set_wire_variables(prover: u64, wire_variables: *const u32, n_vars: u64) -> i32;
+    // the same table recovered from the key's sigma polynomials (a `ProvingKey` does not carry `wire_variables`), and its download;
+    // the two stateless steps underneath, on device arrays
+    pub fn mzk_prover_derive_wire_variables(prover: u64, out_n_vars: *mut u64) -> i32;
+    pub fn mzk_prover_get_wire_variables(prover: u64, out_wire_variables: *mut u32, capacity_cells: u64, out_n_vars: *mut u64) -> i32;
+    pub fn mzk_plonk_sigma_decode_dev(curve_id: i32, log_n: u32, num_wire_types: u32, d_sigma_values: *const c_void, k_mont: *const u64,
+                                      d_out_next_u32: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn mzk_plonk_variables_from_permutation_dev(d_next_u32: *const c_void, cells: u64, d_out_variables_u32: *mut c_void, out_n_vars: *mut u64,
+                                                    stream: *mut c_void) -> i32;
     pub fn mzk_prover_round1(prover: u64, witness_kind: i32, witness: *const c_void, witness_len: u64, pub_input_rows: *const u64,
                              pub_input_mont: *const u64, n_pub: u64, blinders_mont: *const u64, out_comms_xy: *mut u64) -> i32;
     pub fn mzk_prover_check_witness(prover: u64, witness_kind: i32, witness: *const c_void, witness_len: u64, pub_input_rows: *const u64,

@@ -23,6 +23,8 @@ extern "C" int32_t mzk_ctx_pk_register_chunked(int32_t curve_id, uint32_t log_n,
                                                const void* table_coeffs, uint64_t poly_len, const uint64_t* k_mont, const uint32_t* classes, uint32_t n_classes,
                                                int32_t coeffs_on_device, uint64_t* out_handle);
 extern "C" int32_t mzk_ctx_check_witness(uint64_t pk_handle, const mzk::WitnessCheckIn* in, mzk_witness_report* out_report, void* stream);
+// ... and derives the wire-variable table of a prover handle from its key's sigma coefficient forms (plonk.hip plonk_derive_variables_dev)
+extern "C" int32_t mzk_ctx_derive_variables(uint64_t pk_handle, const void* d_sigma_coeffs, void* d_out_variables_u32, uint64_t* out_n_vars, void* stream);
 
 namespace mzk {
 
@@ -214,6 +216,11 @@ int32_t plonk_pk_register(int curve, int log_n, int W, const uint32_t* sel, cons
 // the wire permutation of a variable table and its sigma values (perm.cuh)
 int32_t plonk_wire_permutation_dev(const uint32_t* d_vars, uint64_t cells, uint64_t n_vars, uint32_t* d_next, hipStream_t st);
 int32_t plonk_sigma_values_dev(int curve, int log_n, int W, const uint32_t* d_next, const uint32_t* k_mont, uint32_t* d_out, hipStream_t st);
+// ... and the way back (unperm.cuh): sigma values -> permutation -> variables in canonical numbering; the three steps from a key's resident
+// sigma coefficient forms (mzk_prover_derive_wire_variables)
+int32_t plonk_sigma_decode_dev(int curve, int log_n, int W, const uint32_t* d_sigma, const uint32_t* k_mont, uint32_t* d_next, hipStream_t st);
+int32_t plonk_variables_from_permutation_dev(const uint32_t* d_next, uint64_t cells, uint32_t* d_vars, uint64_t* out_n_vars, hipStream_t st);
+int32_t plonk_derive_variables_dev(uint64_t handle, const uint32_t* d_sigma_coeffs, uint32_t* d_vars, uint64_t* out_n_vars, hipStream_t st);
 int32_t plonk_quotient_chunked_dev(uint64_t handle, const uint32_t* d_polys, uint64_t in_stride, uint64_t in_len, uint32_t flags, const uint32_t* tau,
                                    const uint32_t* alpha, const uint32_t* beta, const uint32_t* gamma, uint32_t* d_out, hipStream_t st);
 int32_t plonk_quotient_top_dev(uint64_t handle, const uint32_t* d_polys, uint64_t in_stride, uint64_t in_len, const uint32_t* alpha, const uint32_t* beta,

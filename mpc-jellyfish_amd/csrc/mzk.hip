@@ -832,6 +832,18 @@ int32_t mzk_plonk_sigma_values_dev(int32_t curve_id, uint32_t log_n, uint32_t nu
     return plonk_sigma_values_dev(curve_id, (int)log_n, (int)num_wire_types, reinterpret_cast<const uint32_t*>(d_next_u32),
                                   reinterpret_cast<const uint32_t*>(k_mont), reinterpret_cast<uint32_t*>(d_out), (hipStream_t)stream);
 }
+int32_t mzk_plonk_sigma_decode_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_sigma_values, const uint64_t* k_mont, void* d_out_next_u32,
+                                   void* stream) {
+    ENTER_CUR();
+    if (log_n > 32) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    return plonk_sigma_decode_dev(curve_id, (int)log_n, (int)num_wire_types, reinterpret_cast<const uint32_t*>(d_sigma_values),
+                                  reinterpret_cast<const uint32_t*>(k_mont), reinterpret_cast<uint32_t*>(d_out_next_u32), (hipStream_t)stream);
+}
+int32_t mzk_plonk_variables_from_permutation_dev(const void* d_next_u32, uint64_t cells, void* d_out_variables_u32, uint64_t* out_n_vars, void* stream) {
+    ENTER_CUR();
+    return plonk_variables_from_permutation_dev(reinterpret_cast<const uint32_t*>(d_next_u32), cells, reinterpret_cast<uint32_t*>(d_out_variables_u32), out_n_vars,
+                                                (hipStream_t)stream);
+}
 int32_t mzk_plonk_pk_hbm_bytes(uint64_t pk_handle, uint64_t* out_bytes) {
     ENTER_HANDLE(pk_handle);
     if (!out_bytes) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
@@ -1120,6 +1132,11 @@ int32_t mzk_ctx_prover_stream(uint32_t k, void** out_stream) {
 int32_t mzk_ctx_check_witness(uint64_t pk_handle, const WitnessCheckIn* in, mzk_witness_report* out_report, void* stream) {
     ENTER_HANDLE(pk_handle);
     return plonk_check_witness_dev(pk_handle, *in, out_report, (hipStream_t)stream);
+}
+int32_t mzk_ctx_derive_variables(uint64_t pk_handle, const void* d_sigma_coeffs, void* d_out_variables_u32, uint64_t* out_n_vars, void* stream) {
+    ENTER_HANDLE(pk_handle);
+    return plonk_derive_variables_dev(pk_handle, reinterpret_cast<const uint32_t*>(d_sigma_coeffs), reinterpret_cast<uint32_t*>(d_out_variables_u32), out_n_vars,
+                                      (hipStream_t)stream);
 }
 int32_t mzk_stream_destroy(void* stream) {
     BIND_CUR();

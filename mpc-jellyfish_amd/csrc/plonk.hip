@@ -11,6 +11,7 @@
 #include "plookup.cuh"
 #include "check.cuh"
 #include "perm.cuh"
+#include "unperm.cuh"
 
 namespace mzk {
 namespace {
@@ -836,6 +837,116 @@ int32_t sigma_values_run(int log_n, int W, const uint32_t* d_next, const uint32_
     return MZK_OK;
 }
 
+// The way back (unperm.cuh; include/mzk.h mzk_plonk_sigma_decode_dev): next[c] = the cell whose identity value k_a w^b is sigma[c].
+// Scratch: the context's shared buffers (poly_tmp: the n powers of w; io: the hash slots, 4 B each, the power of two >= 2 W n of them;
+// misc: the validation's four words).  Synchronises: the validation result is read back.
+template <class P>
+int32_t sigma_decode_run(int log_n, int W, const uint32_t* d_sigma, const uint32_t* k_mont, uint32_t* d_next, hipStream_t st) {
+    using F = Fp<P>;
+    const uint64_t n = 1ull << log_n, cells = (uint64_t)W * n;
+    uint64_t slots = 64;
+    while (slots < 2 * cells && slots < (1ull << 32)) slots <<= 1;
+    F wn = F::from_const(P::ROOT);
+    for (int i = log_n; i < P::TWO_ADICITY; i++) wn = sqr(wn);
+    ProfScope total("sigma_decode", st);
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->poly_tmp.reserve(n * 32));
+    MZK_TRY(ws->io.reserve(slots * 4));
+    MZK_TRY(ws->misc.reserve(512));
+    uint32_t* d_omega = ws->poly_tmp.as<uint32_t>();
+    uint32_t* d_res = ws->misc.as<uint32_t>();
+    launch_powers<P>(st, &wn, 1, n, &d_omega);
+    DecodeArgs a;
+    a.sigma = d_sigma; a.omega = d_omega; a.slots = ws->io.as<uint32_t>(); a.next = d_next; a.res = d_res;
+    a.cells = cells; a.log_n = (unsigned)log_n; a.mask = (uint32_t)(slots - 1);
+    std::memset(a.k, 0, sizeof a.k);
+    std::memcpy(a.k, k_mont, (size_t)W * 32);
+    const uint32_t init[4] = {0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu};
+    HIP_TRY(hipMemcpyAsync(d_res, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(a.slots, 0xFF, slots * 4, st));
+    const unsigned grid = (unsigned)((cells + PERM_THREADS - 1) / PERM_THREADS);
+    hipLaunchKernelGGL((unperm_insert_kernel<P>), dim3(grid), dim3(PERM_THREADS), 0, st, a);
+    hipLaunchKernelGGL((unperm_probe_kernel<P>), dim3(grid), dim3(PERM_THREADS), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    uint32_t res[4];
+    HIP_TRY(hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (res[2]) {
+        set_error("sigma decode: cell " + std::to_string(res[3]) + ": its identity value k_a w^b is that of another cell -- the cosets k_a H are not disjoint (" +
+                  std::to_string(res[2]) + " such collisions)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    if (res[0]) {
+        set_error("sigma decode: cell " + std::to_string(res[1]) + ": not k_a w^b (" + std::to_string(res[0]) + " such cells)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return MZK_OK;
+}
+
+// Variables in canonical numbering from a permutation of the cells (unperm.cuh; include/mzk.h mzk_plonk_variables_from_permutation_dev).
+// Scratch: the context's shared buffers (sorted: the two (min, jump) arrays the rounds alternate between, 16 B per cell -- the second one
+// holds the predecessor marks first; hist: minima per block of 256 cells and their scan; misc: the validation's four words and one
+// `changed` word per round).  Synchronises after the validation, after every round (the `changed` word decides whether another follows)
+// and at the end (n_vars).
+int32_t variables_from_permutation_run(const uint32_t* d_next, uint64_t cells, uint32_t* d_vars, uint64_t* out_n_vars, hipStream_t st) {
+    *out_n_vars = 0;
+    if (cells == 0) return MZK_OK;
+    int max_rounds = 0;
+    while ((1ull << max_rounds) < cells) max_rounds++;                  // ceil(log2(cells)) <= 32
+    const unsigned grid = (unsigned)((cells + PERM_THREADS - 1) / PERM_THREADS);
+    ProfScope total("variables_from_permutation", st);
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->sorted.reserve(cells * 16));
+    MZK_TRY(ws->hist.reserve(((size_t)grid + 1) * 4));
+    MZK_TRY(ws->misc.reserve(512));
+    unsigned long long* state[2] = {ws->sorted.as<unsigned long long>(), ws->sorted.as<unsigned long long>() + cells};
+    uint32_t* d_mark = reinterpret_cast<uint32_t*>(state[1]);
+    uint32_t* d_totals = ws->hist.as<uint32_t>();
+    uint32_t* d_res = ws->misc.as<uint32_t>();
+    uint32_t* d_changed = d_res + 4;                                    // 32 words
+    uint32_t init[4 + 32] = {0u, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu};
+    HIP_TRY(hipMemcpyAsync(d_res, init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_mark, 0, cells * 4, st));
+    hipLaunchKernelGGL(unperm_mark_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, d_next, (unsigned long long)cells, d_mark, d_res);
+    hipLaunchKernelGGL(unperm_unmarked_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, d_mark, (unsigned long long)cells, d_res);
+    HIP_TRY(hipGetLastError());
+    uint32_t res[4];
+    HIP_TRY(hipMemcpyAsync(res, d_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (res[0]) {
+        uint32_t v = 0;
+        HIP_TRY(hipMemcpy(&v, d_next + res[1], 4, hipMemcpyDeviceToHost));
+        set_error("permutation: cell " + std::to_string(res[1]) + " holds " + std::to_string(v) + " >= number of cells " + std::to_string(cells) + " (" +
+                  std::to_string(res[0]) + " such cells)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    if (res[2]) {
+        set_error("permutation: cell " + std::to_string(res[3]) + " is the successor of no cell (" + std::to_string(res[2]) + " such cells): not a permutation");
+        return MZK_ERR_INVALID_ARG;
+    }
+    hipLaunchKernelGGL(unperm_init_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, d_next, (unsigned long long)cells, state[0]);
+    int cur = 0;
+    for (int r = 0; r < max_rounds; r++) {
+        hipLaunchKernelGGL(unperm_round_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, state[cur], state[cur ^ 1], (unsigned long long)cells, d_changed + r);
+        cur ^= 1;
+        uint32_t changed = 0;
+        HIP_TRY(hipMemcpyAsync(&changed, d_changed + r, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!changed) break;
+    }
+    HIP_TRY(hipMemsetAsync(d_totals + grid, 0, 4, st));
+    hipLaunchKernelGGL(unperm_count_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, state[cur], (unsigned long long)cells, d_totals);
+    hipLaunchKernelGGL(perm_scan_kernel, dim3(1), dim3(1024), 0, st, d_totals, grid + 1u);
+    hipLaunchKernelGGL(unperm_rank_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, state[cur], (unsigned long long)cells, d_totals, d_vars);
+    hipLaunchKernelGGL(unperm_spread_kernel, dim3(grid), dim3(PERM_THREADS), 0, st, state[cur], (unsigned long long)cells, d_vars);
+    HIP_TRY(hipGetLastError());
+    uint32_t n_vars = 0;
+    HIP_TRY(hipMemcpyAsync(&n_vars, d_totals + grid, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out_n_vars = n_vars;
+    return MZK_OK;
+}
+
 // frees a key's device buffers (called explicitly: a registry-held key has no freeing destructor)
 void pk_free(PlonkPk& pk) {
     for (auto* d : pk.bufs()) if (d) (void)hipFree(d);
@@ -972,6 +1083,37 @@ int32_t plonk_sigma_values_dev(int curve, int log_n, int W, const uint32_t* d_ne
         return MZK_ERR_INVALID_ARG;
     }
     return curve == 0 ? sigma_values_run<BlsFr>(log_n, W, d_next, k_mont, d_out, st) : sigma_values_run<BnFr>(log_n, W, d_next, k_mont, d_out, st);
+}
+int32_t plonk_sigma_decode_dev(int curve, int log_n, int W, const uint32_t* d_sigma, const uint32_t* k_mont, uint32_t* d_next, hipStream_t st) {
+    if (!valid_curve(curve) || (W != PLK_WIRES && W != PLK_MAX_WIRES) || log_n < 0 || log_n > (curve == 0 ? 32 : 28) || !d_sigma || !k_mont || !d_next) {
+        set_error("bad argument (5 or 6 wire types, 2^log_n within the field's two-adicity)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    if (((uint64_t)W << log_n) >= (1ull << 32)) { set_error("sigma decode: num_wire_types * 2^log_n must be below 2^32"); return MZK_ERR_UNSUPPORTED; }
+    return curve == 0 ? sigma_decode_run<BlsFr>(log_n, W, d_sigma, k_mont, d_next, st) : sigma_decode_run<BnFr>(log_n, W, d_sigma, k_mont, d_next, st);
+}
+int32_t plonk_variables_from_permutation_dev(const uint32_t* d_next, uint64_t cells, uint32_t* d_vars, uint64_t* out_n_vars, hipStream_t st) {
+    if (cells >= (1ull << 32)) { set_error("variables from permutation: the number of cells must be below 2^32"); return MZK_ERR_UNSUPPORTED; }
+    if ((cells && (!d_next || !d_vars)) || !out_n_vars) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    return variables_from_permutation_run(d_next, cells, d_vars, out_n_vars, st);
+}
+// mzk_prover_derive_wire_variables on the key's context: the W sigma polynomials onto H (out of place: the resident coefficient forms
+// are read, not copied), decode, label.  Scratch: plonk_polys (W n sigma values), plonk_out (next) and what the two steps take.
+int32_t plonk_derive_variables_dev(uint64_t handle, const uint32_t* d_sigma_coeffs, uint32_t* d_vars, uint64_t* out_n_vars, hipStream_t st) {
+    const PlonkPk* pk = find_pk(handle);
+    if (!pk) return MZK_ERR_BAD_HANDLE;
+    if (!d_sigma_coeffs || !d_vars || !out_n_vars) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    const uint64_t n = 1ull << pk->log_n, cells = (uint64_t)pk->W * n;
+    if (cells >= (1ull << 32)) { set_error("derive wire variables: num_wire_types * domain size must be below 2^32"); return MZK_ERR_UNSUPPORTED; }
+    ProfScope total("derive_variables", st);
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->plonk_polys.reserve(cells * 32));
+    MZK_TRY(ws->plonk_out.reserve(cells * 4));
+    uint32_t* d_sigma = ws->plonk_polys.as<uint32_t>();
+    uint32_t* d_next = ws->plonk_out.as<uint32_t>();
+    MZK_TRY(ntt_dispatch(pk->curve, d_sigma, n, pk->log_n, false, nullptr, (uint32_t)pk->W, n, st, 0, d_sigma_coeffs, n));
+    MZK_TRY(plonk_sigma_decode_dev(pk->curve, pk->log_n, pk->W, d_sigma, &pk->k[0][0], d_next, st));
+    return plonk_variables_from_permutation_dev(d_next, cells, d_vars, out_n_vars, st);
 }
 int32_t plonk_check_witness_dev(uint64_t handle, const WitnessCheckIn& in, mzk_witness_report* out, hipStream_t st) {
     const PlonkPk* pk = find_pk(handle);

@@ -100,6 +100,8 @@ struct ProverBase {
     virtual void vk_commitments(uint64_t* out_xy, uint64_t* out_plookup_xy) = 0;
     virtual void set_wire_variables(const uint32_t* vars, uint64_t n_vars) = 0;
     virtual void take_wire_variables(Buf& d_vars, uint64_t n_vars) = 0;
+    virtual void derive_wire_variables(uint64_t* out_n_vars) = 0;
+    virtual void get_wire_variables(uint32_t* out, uint64_t capacity, uint64_t* out_n_vars) = 0;
     virtual void round1(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
                         const uint64_t* blinders, uint64_t* out) = 0;
     virtual void check_witness(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
@@ -294,6 +296,9 @@ struct ProverT final : ProverBase {
     // ---- round 1 (prover.rs:72-87; constraint_system.rs:1225-1259) -------------------------------------------------------------
     void set_wire_variables(const uint32_t* v, uint64_t nv) override;   // prover_setup.inc
     void take_wire_variables(Buf& d_vars, uint64_t nv) override;   // prover_setup.inc
+    void install_wire_variables(Buf& fresh, uint64_t nv);   // prover_setup.inc
+    void derive_wire_variables(uint64_t* out_nv) override;   // prover_setup.inc
+    void get_wire_variables(uint32_t* out, uint64_t capacity, uint64_t* out_nv) override;   // prover_setup.inc
     void public_input_row(const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi);   // prover_round1.inc
     void round1(int kind, const void* witness, uint64_t witness_len, const uint64_t* pi_rows, const uint64_t* pi, uint64_t n_pi,
         const uint64_t* blinders, uint64_t* out) override;   // prover_round1.inc
@@ -533,6 +538,14 @@ int32_t mzk_prover_set_wire_variables(uint64_t prover, const uint32_t* wire_vari
     PROVER(prover);
     if (!wire_variables || n_vars == 0 || n_vars >= (1ull << 32)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     return guarded(*p_, [&] { p_->set_wire_variables(wire_variables, n_vars); });
+}
+int32_t mzk_prover_derive_wire_variables(uint64_t prover, uint64_t* out_n_vars) {
+    PROVER(prover);
+    return guarded(*p_, [&] { p_->derive_wire_variables(out_n_vars); });
+}
+int32_t mzk_prover_get_wire_variables(uint64_t prover, uint32_t* out_wire_variables, uint64_t capacity_cells, uint64_t* out_n_vars) {
+    PROVER(prover);
+    return guarded(*p_, [&] { p_->get_wire_variables(out_wire_variables, capacity_cells, out_n_vars); });
 }
 int32_t mzk_prover_round1(uint64_t prover, int32_t witness_kind, const void* witness, uint64_t witness_len, const uint64_t* pub_input_rows,
                           const uint64_t* pub_input_mont, uint64_t n_pub, const uint64_t* blinders_mont, uint64_t* out_comms_xy) {

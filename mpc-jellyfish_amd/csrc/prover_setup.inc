@@ -11,7 +11,7 @@ ProverT<FrP, CURVE>::ProverT(int log_n_, int W_, const uint64_t* sel, const uint
     rows = W + 2 + (ultra ? 3 : 0);
     n = 1ull << log_n; m = 8 * n;
     key_ = std::make_shared<Key>();
-    Key& K = *key_;                                                // (the one place, with set / take_wire_variables, that writes the key part)
+    Key& K = *key_;                                                // (the one place, with install / take_wire_variables, that writes the key part)
     K.srs = commit_key; K.srs_lagrange = lagrange_key;
     if (cm) { comm = *cm; rank = cm->rank; world = cm->world; }
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && (!comm.all_gather || !comm.barrier)))
@@ -237,13 +237,46 @@ void ProverT<FrP, CURVE>::set_wire_variables(const uint32_t* v, uint64_t nv) {
     const size_t cnt = (size_t)W * n;
     for (size_t i = 0; i < cnt; i++)
         if (v[i] >= nv) fail(MZK_ERR_INVALID_ARG, "wire_variables: variable index " + std::to_string(v[i]) + " >= number of variables " + std::to_string(nv));
-    // a key with other holders is theirs too: the table is replaced for this handle alone (copy-on-write)
+    Buf fresh;
+    fresh.alloc((cnt * 4 + EL - 1) / EL);
+    ck(mzk_dev_upload(fresh.p, v, cnt * 4));
+    install_wire_variables(fresh, nv);
+}
+
+// where a table becomes the handle's (mzk_prover_set_wire_variables, mzk_prover_derive_wire_variables): `fresh` leaves with the table it
+// replaces, or empty.  A key with other holders is theirs too: the table is replaced for this handle alone (copy-on-write)
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::install_wire_variables(Buf& fresh, uint64_t nv) {
     const bool sole = key_.use_count() == 1;
-    Buf& dst = sole ? key_->vars : own_vars;
-    dst.alloc((cnt * 4 + EL - 1) / EL);
-    ck(mzk_dev_upload(dst.p, v, cnt * 4));
+    sync_stream();                                                 // (what this handle has queued may still read the table that leaves)
+    (sole ? key_->vars : own_vars).swap(fresh);
     (sole ? key_->n_vars : own_n_vars) = nv;
-    if (sole && own_vars.p) { sync_stream(); Buf().swap(own_vars); own_n_vars = 0; }   // (set while the key was shared; the handle is alone again)
+    if (sole && own_vars.p) { Buf().swap(own_vars); own_n_vars = 0; }   // (set while the key was shared; the handle is alone again)
+}
+
+// mzk_prover_derive_wire_variables: the table from the key's own sigma polynomials (plonk.hip plonk_derive_variables_dev, on the handle's
+// stream, in the context's shared scratch).  It is written into memory of its own and installed once complete: an error leaves the handle as it was
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::derive_wire_variables(uint64_t* out_nv) {
+    const size_t cnt = (size_t)W * n;
+    Buf fresh;
+    fresh.alloc((cnt * 4 + EL - 1) / EL);
+    uint64_t nv = 0;
+    ck(mzk_ctx_derive_variables(key().pk, fix(nsel), fresh.p, &nv, S));
+    install_wire_variables(fresh, nv);
+    if (out_nv) *out_nv = nv;
+}
+
+template <class FrP, int CURVE>
+void ProverT<FrP, CURVE>::get_wire_variables(uint32_t* out, uint64_t capacity, uint64_t* out_nv) {
+    const size_t cnt = (size_t)W * n;
+    if (!vars_dev()) fail(MZK_ERR_INVALID_ARG, "the handle has no wire-variable table (mzk_prover_set_wire_variables, mzk_prover_derive_wire_variables)");
+    if (out && capacity < cnt) fail(MZK_ERR_INVALID_ARG, "capacity_cells < num_wire_types * domain size");
+    if (out) {
+        sync_stream();
+        ck(mzk_dev_download(out, vars_dev(), cnt * 4));
+    }
+    if (out_nv) *out_nv = vars_n();
 }
 
 // the same table, resident already and validated where it was sorted (mzk_prover_create_from_circuit): the buffer changes hands

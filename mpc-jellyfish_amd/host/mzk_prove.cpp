@@ -5,6 +5,10 @@
 // --check-witness (turbo, ultra, file): mzk_prover_check_witness before proving; prints one line -- `witness: satisfied`, or
 // `witness: gate row R residual 0x..`, `witness: lookup row R`, `witness: copy cell (wire,row) != (wire,row)` -- followed by the numbers of
 // failing gate rows, lookup rows and copy cells, and exits with status 3 without proving when the witness is not satisfied (--gpus G: rank 0 checks).
+// --derive-variables (turbo, ultra, file): mzk_prover_derive_wire_variables after the set-up -- the wire-variable table recovered from the key's
+// sigma polynomials, so that --check-witness checks the copy constraints of a prover that came from coefficient forms (a circuit file
+// holds sigma values, not variables); when the first failing family is not the copy family, the first failing copy cell follows the counts.
+// Not with --host-witness-vars: that witness vector is in the circuit's numbering, the derived table in the canonical one.
 // --srs FILE (turbo, ultra, file): commit over the powers of a setup file -- CanonicalSerialize of UnivariateUniversalParams, compressed --
 // decoded and validated on every device, instead of the testing SRS [beta^i] G.  The trapdoor is still drawn (and discarded) from the rng,
 // so the blinders are those of a run without --srs.  A file with fewer than n + 3 powers is an error.
@@ -42,6 +46,7 @@ struct Options {
     bool slice_srs = true;        // --no-slice: with --gpus G every rank keeps the whole commit key (and its table) instead of its point range
     bool device_preprocess = false;  // --device-preprocess: the proving key from the circuit's selector values and variable table, permutation and
                                   // sigma values on the device (mzk_prover_create_from_circuit_dev) -- same key, same bytes; bench circuits only
+    bool derive_variables = false;  // --derive-variables: the wire-variable table from the key's sigma polynomials (mzk_prover_derive_wire_variables)
     bool check_witness = false;   // --check-witness: say where the witness fails before proving; exit status 3 if it does
     int lagrange = -1;            // round 1 commits the wires from their VALUES over the Lagrange-basis key derived from the SRS (same proof
                                   // bytes): -1 = from 2^18 gates on (below, the heavy-bucket paths of small scalars cost more than they save: 2^15 gates 3.93 against 3.73 ms) when a sample of the witness
@@ -71,6 +76,7 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     const bool lagrange = opt.lagrange < 0 ? (host.log_n >= 18 && host.witness_is_small()) : opt.lagrange != 0;
     sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr, opt.device_preprocess);    // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
     const double preprocess_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (opt.derive_variables) sp.derive_wire_variables();
     if (opt.check_witness) {
         const mzk_witness_report rep = sp.check_witness();
         const unsigned long long n = 1ull << host.log_n;
@@ -84,8 +90,12 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
         } else if (rep.kind == MZK_CHECK_LOOKUP) std::printf("witness: lookup row %llu", (unsigned long long)rep.lookup_row);
         else std::printf("witness: copy cell (%llu,%llu) != (%llu,%llu)", (unsigned long long)(rep.copy_cell / n), (unsigned long long)(rep.copy_cell % n),
                          (unsigned long long)(rep.copy_rep_cell / n), (unsigned long long)(rep.copy_rep_cell % n));
-        std::printf("; failing gate rows %llu, lookup rows %llu, copy cells %llu%s\n", (unsigned long long)rep.gate_failures, (unsigned long long)rep.lookup_failures,
+        std::printf("; failing gate rows %llu, lookup rows %llu, copy cells %llu%s", (unsigned long long)rep.gate_failures, (unsigned long long)rep.lookup_failures,
                     (unsigned long long)rep.copy_failures, rep.copy_checked ? "" : " (copy constraints not checked: no wire-variable table)");
+        if (opt.derive_variables && rep.copy_failures && rep.kind != MZK_CHECK_COPY)
+            std::printf("; first copy cell (%llu,%llu) != (%llu,%llu)", (unsigned long long)(rep.copy_cell / n), (unsigned long long)(rep.copy_cell % n),
+                        (unsigned long long)(rep.copy_rep_cell / n), (unsigned long long)(rep.copy_rep_cell % n));
+        std::printf("\n");
         std::fflush(stdout);
         if (rep.kind != MZK_CHECK_SATISFIED) return 3;
     }
@@ -273,6 +283,7 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--check-agree") opt.check_agree = true;
         else if (a == "--slots" && i + 1 < argc_in) opt.slots = std::atoi(argv_in[++i]);
         else if (a == "--check-witness") opt.check_witness = true;
+        else if (a == "--derive-variables") opt.derive_variables = true;
         else if (a == "--device-preprocess") opt.device_preprocess = true;
         else if (a == "--lagrange") opt.lagrange = 1;
         else if (a == "--no-lagrange") opt.lagrange = 0;
@@ -283,11 +294,16 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     if (opt.gpus < 1 || opt.gpus > 16) { std::fprintf(stderr, "mzk_prove: --gpus 1..16\n"); return 2; }
-    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--device-preprocess] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--derive-variables] [--device-preprocess] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
     const int curve = std::atoi(argv[1]);
     if (opt.device_preprocess && (std::string(argv[2]) == "file" || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
         std::fprintf(stderr, "mzk_prove: --device-preprocess needs the circuit's variable table: a circuit file holds sigma values, not variables "
                              "(bench circuits only: <turbo|ultra> <num_gates>)\n");
+        return 2;
+    }
+    if (opt.derive_variables && (opt.host_witness == 2 || opt.slots || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
+        std::fprintf(stderr, "mzk_prove: --derive-variables goes with turbo, ultra and file, and not with --host-witness-vars (a witness vector in the circuit's "
+                             "numbering) or --slots\n");
         return 2;
     }
     if (std::string(argv[2]) == "link") {

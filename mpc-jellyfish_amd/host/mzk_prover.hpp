@@ -381,6 +381,13 @@ struct Prover {
         const uint64_t* sig = sel + (size_t)nsel * n * 4;
         check(mzk_prover_create(C::ID, log_n, W, sel, sig, ultra ? sig + (size_t)W * n * 4 : nullptr, n, kk.data(), srs, lagrange_key, comm, &handle), "mzk_prover_create");
     }
+    // the wire-variable table from the key's own sigma polynomials (mzk_prover_derive_wire_variables): a prover from coefficient forms can
+    // then check copy constraints; variables come in canonical numbering, so a witness VECTOR in the circuit's own numbering no longer fits
+    uint64_t derive_wire_variables() {
+        uint64_t n_vars = 0;
+        check(mzk_prover_derive_wire_variables(handle, &n_vars), "mzk_prover_derive_wire_variables");
+        return n_vars;
+    }
     Prover(const Prover&) = delete;
     Prover& operator=(const Prover&) = delete;
     ~Prover() { if (handle) (void)mzk_prover_destroy(handle); }
@@ -757,6 +764,12 @@ struct ShardedProver {
         mzk_witness_report rep{};
         each([&](int r) { if (r == 0) rep = prover[0]->check_witness(*circuit[0]); });
         return rep;
+    }
+    // no collective either: rank 0 derives the table the check reads
+    uint64_t derive_wire_variables() {
+        uint64_t n_vars = 0;
+        each([&](int r) { if (r == 0) n_vars = prover[0]->derive_wire_variables(); });
+        return n_vars;
     }
     void sync() { each([&](int) { check(mzk_dev_sync(), "sync"); }); }
 };

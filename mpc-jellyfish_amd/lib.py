@@ -79,6 +79,8 @@ _SIGS = {
     "mzk_plonk_perm_product": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_plonk_wire_permutation_dev": [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_plonk_sigma_values_dev": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_plonk_sigma_decode_dev": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_plonk_variables_from_permutation_dev": [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_plonk_gather_witness_dev": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_poly_eval_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_poly_lincomb_dev": [C.c_int32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p],
@@ -131,6 +133,8 @@ _SIGS = {
     "mzk_prover_fork": [C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_prover_vk_commitments": [C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_prover_set_wire_variables": [C.c_uint64, C.c_void_p, C.c_uint64],
+    "mzk_prover_derive_wire_variables": [C.c_uint64, C.POINTER(C.c_uint64)],
+    "mzk_prover_get_wire_variables": [C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_prover_round1": [C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_prover_check_witness": [C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(WitnessReport)],
     "mzk_prover_round1_5": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -231,6 +231,34 @@ def _to_dev(x):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.uint64).view(np.int64)).cuda()
 
 
+def sigma_decode(curve, sigma_values_dev, k):
+    """mzk_plonk_sigma_decode_dev, the inverse of compute_extended_permutation: (W, n, 4) sigma VALUES on the gate domain (CUDA, Montgomery)
+    -> (W, n) int32 CUDA tensor `next`, next[c] = a n + b where sigma[c] = k_a w^b.  Synchronises; a value that is no k_a w^b raises."""
+    import torch
+    c = _curve(curve)
+    W, n = int(sigma_values_dev.shape[0]), int(sigma_values_dev.shape[1])
+    assert sigma_values_dev.is_cuda and sigma_values_dev.is_contiguous() and sigma_values_dev.dtype == torch.int64 and tuple(sigma_values_dev.shape) == (W, n, 4)
+    kk = fr_to_mont(c, list(k))
+    out = torch.empty((W, n), dtype=torch.int32, device=sigma_values_dev.device)
+    _lib.check(_lib.ensure_init().mzk_plonk_sigma_decode_dev(c.curve_id, n.bit_length() - 1, W, C.c_void_p(sigma_values_dev.data_ptr()), C.c_void_p(kk.ctypes.data),
+                                                             C.c_void_p(out.data_ptr()), torch.cuda.current_stream(out.device).cuda_stream), "mzk_plonk_sigma_decode_dev")
+    return out
+
+
+def variables_from_permutation(next_dev):
+    """mzk_plonk_variables_from_permutation_dev, the inverse of compute_wire_permutation up to renaming: an int32 CUDA tensor holding a
+    permutation of its own indices -> (variables, n_vars), same shape, cells of one cycle sharing a variable, numbered by first
+    occurrence in index order.  Synchronises; raises when `next_dev` is no permutation."""
+    import torch
+    assert next_dev.is_cuda and next_dev.is_contiguous() and next_dev.dtype == torch.int32
+    out = torch.empty_like(next_dev)
+    n_vars = C.c_uint64()
+    _lib.check(_lib.ensure_init().mzk_plonk_variables_from_permutation_dev(C.c_void_p(next_dev.data_ptr()), next_dev.numel(), C.c_void_p(out.data_ptr()),
+                                                                           C.byref(n_vars), torch.cuda.current_stream(out.device).cuda_stream),
+               "mzk_plonk_variables_from_permutation_dev")
+    return out, n_vars.value
+
+
 def compute_prod_permutation_polynomial_dev(pk: ProvingKeyDevice, beta: int, gamma: int, wire_values_dev, out_dev=None):
     """constraint_system.rs:1197-1223 on device tensors: (W, n, 4) wire values -> (n, 4) coefficients.  Asynchronous."""
     import torch

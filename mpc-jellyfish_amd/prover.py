@@ -335,6 +335,22 @@ class TurboPlonkProver:
         v = np.ascontiguousarray(wire_variables, dtype=np.uint32).reshape(self.W, self.n)
         _check(_lib.load().mzk_prover_set_wire_variables(self.handle, _ptr(v), n_vars), "mzk_prover_set_wire_variables")
 
+    def derive_wire_variables(self) -> int:
+        """mzk_prover_derive_wire_variables: the variable table from the key's own sigma polynomials, in canonical numbering (variables
+        numbered by their smallest cell), resident as after set_wire_variables -> the number of variables.  A HostWitness given to this
+        prover afterwards is gathered through THIS table: build its vector from wire_variables()."""
+        n_vars = C.c_uint64()
+        _check(_lib.load().mzk_prover_derive_wire_variables(self.handle, C.byref(n_vars)), "mzk_prover_derive_wire_variables")
+        self._own_table = True
+        return n_vars.value
+
+    def wire_variables(self):
+        """mzk_prover_get_wire_variables: the resident table, whatever installed it -> ((W, n) uint32, n_vars)"""
+        out = np.zeros((self.W, self.n), dtype=np.uint32)
+        n_vars = C.c_uint64()
+        _check(_lib.load().mzk_prover_get_wire_variables(self.handle, _ptr(out), self.W * self.n, C.byref(n_vars)), "mzk_prover_get_wire_variables")
+        return out, n_vars.value
+
     def hbm_bytes(self):
         a, b, w = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(_lib.load().mzk_prover_hbm_bytes(self.handle, C.byref(a), C.byref(b), C.byref(w)), "mzk_prover_hbm_bytes")
