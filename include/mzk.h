@@ -140,6 +140,65 @@ MZK_API int32_t mzk_srs_serialize(uint64_t handle, uint64_t first, uint64_t n_po
 
 MZK_API int32_t mzk_srs_len(uint64_t handle, uint64_t* out_n_points);
 
+/* ---- serialized ProvingKey / VerifyingKey: the CanonicalSerialize image of jf-plonk's keys (ark-serialize 0.4, derive order;
+ * DESIGN.md section 4.13).  The image names neither its curve nor its mode: the caller states both, as for the SRS; the mode
+ * (MZK_SER_COMPRESSED or not) applies to every point in it.
+ *   usize            u64 little-endian
+ *   bool             1 byte, 0 or 1 (anything else is invalid);  Option<T>: a bool, then T if it is 1;  Vec<T>: u64 LE count, then the items
+ *   Fr               32 B little-endian, the canonical integer, no flag bits, below r (both curves)
+ *   DensePolynomial  its coeffs: Vec<Fr> (from_coefficients_vec strips trailing zeros: shorter than n is normal, the zero polynomial has
+ *                    count 0; trailing zero coefficients are accepted, as ark accepts them)
+ *   Commitment       its G1Affine: records and flags as for the serialized SRS above
+ *   G2               opaque bytes, neither decoded nor validated: BLS12-381 96 / 192 B, BN254 64 / 128 B (compressed / uncompressed)
+ *   ProvingKey    (plonk/src/proof_system/structs.rs:575-590)
+ *     sigmas: Vec<Poly>  selectors: Vec<Poly>  commit_key: Vec<G1>  vk: VerifyingKey  plookup_pk: Option<PlookupProvingKey>
+ *   PlookupProvingKey (:595-607)  range_table_poly, key_table_poly, table_dom_sep_poly, q_dom_sep_poly (4 Poly)
+ *   VerifyingKey  (:682-707)
+ *     domain_size: usize  num_inputs: usize  sigma_comms: Vec<G1>  selector_comms: Vec<G1>  k: Vec<Fr>
+ *     open_key: { g: G1, h: G2, beta_h: G2 } (primitives/src/pcs/univariate_kzg/srs.rs:48-55)  is_merged: bool  plookup_vk: Option<4 x G1> (:771-785)
+ * Parity of this restatement with the Rust code is UNPINNED until tests/golden/ref_proving_keys.json (integration/rust gen_fixtures,
+ * family proving_key) exists: the tests build their images from the format as written here.
+ *
+ * mzk_key_layout: host-only (no GPU, no mzk_init), reads nothing outside [bytes, bytes + len), and of the image only length prefixes
+ * and tags.  flags: MZK_SER_COMPRESSED (the mode) and MZK_KEY_VK_ONLY (the image is a bare VerifyingKey: the polynomial, commit-key and
+ * has_plookup fields stay zero, vk_off = 0); other bits are ignored.  Offsets are byte offsets into the image; those of a Vec point at
+ * its first item, past the count.  MZK_ERR_ENCODING, with mzk_last_error() naming the field and the reason: "truncated in <field> at
+ * byte <len>" (every count is compared with the bytes left divided by the record size, so a count of 2^64 - 1 is truncated, never a
+ * wrapped product); a bool or Option tag that is not 0 or 1; a sigma count that is not 5 or 6; a selector count that is not 13 (W = 5) /
+ * 14 (W = 6); plookup_pk present when W is not 6 or absent when it is; plookup_pk and plookup_vk not both present or absent;
+ * sigma_comms / selector_comms / k counts that do not match W and nsel; domain_size no power of two or above 2^27; a polynomial with
+ * more than domain_size coefficients; fewer than domain_size + 3 commit-key points; bytes left over after the last field. */
+#define MZK_KEY_CHECK_COMMITMENTS 4u   /* mzk_prover_create_serialized: the commitments of vk must commit the polynomials of the key */
+#define MZK_KEY_VK_ONLY 8u             /* mzk_key_layout: a bare VerifyingKey image */
+typedef struct mzk_key_layout {
+    uint32_t num_wire_types, num_selectors;             /* W = 5 or 6, nsel = 13 or 14 */
+    uint32_t has_plookup, has_plookup_vk, is_merged, reserved;
+    uint64_t domain_size, num_inputs;
+    uint64_t g1_record_bytes, g2_record_bytes;          /* of the stated curve and mode */
+    uint64_t sigma_off[6], sigma_len[6];                /* per polynomial: offset of its first coefficient, coefficient count */
+    uint64_t selector_off[14], selector_len[14];
+    uint64_t table_off[4], table_len[4];                /* range, key, table_dom_sep, q_dom_sep */
+    uint64_t commit_key_off, commit_key_count;
+    uint64_t vk_off, vk_len;                            /* the embedded VerifyingKey as a whole */
+    uint64_t sigma_comms_off, selector_comms_off, k_off, g_off, h_off, beta_h_off, plookup_comms_off;
+    uint64_t total_len;
+} mzk_key_layout_t;
+MZK_API int32_t mzk_key_layout(int32_t curve_id, const uint8_t* bytes, uint64_t len, uint32_t flags, mzk_key_layout_t* out);
+
+/* Fr records on the device (csrc/key_io.cuh), the primitives of the key loader as mzk_srs_register_serialized_dev's decode is of the
+ * SRS loader.  mzk_fr_decode_dev: ONE launch for up to 32 segments of one staged image (device, image_len bytes; its base 4-byte
+ * aligned, as any allocation is; the records at any byte alignment): segment s holds
+ * counts[s] records of 32 B from byte src_offsets[s] of d_image on and fills row dst_rows[s] < n_rows of d_out (n_rows rows of row_len aligned
+ * Montgomery elements): slot i < counts[s] is the record, checked to be below r and converted; slots counts[s] <= i < row_len are zero.
+ * counts[s] <= row_len < 2^40, every segment inside the image (MZK_ERR_INVALID_ARG otherwise, nothing is launched).  A record not below r: MZK_ERR_ENCODING, *out_bad_segment / *out_bad_index (nullable; UINT32_MAX / UINT64_MAX when
+ * all is well) the LOWEST (segment, index) in segment order -- one atomicMin on a 64-bit word, the same answer on every run -- and
+ * mzk_last_error() "segment <s> coefficient <i>: not below the modulus"; the rows are then unspecified.  Synchronises `stream`.
+ * mzk_fr_encode_dev: count aligned Montgomery elements at d_in -> count records of 32 B at d_out (device, 4-byte aligned).  Asynchronous. */
+MZK_API int32_t mzk_fr_decode_dev(int32_t curve_id, const void* d_image, uint64_t image_len, uint32_t n_segments, const uint64_t* src_offsets,
+                                  const uint64_t* counts, const uint32_t* dst_rows, void* d_out, uint32_t n_rows, uint64_t row_len,
+                                  uint32_t* out_bad_segment, uint64_t* out_bad_index, void* stream);
+MZK_API int32_t mzk_fr_encode_dev(int32_t curve_id, const void* d_in, uint64_t count, void* d_out, void* stream);
+
 /* ---- MSM: replaces <E::G1 as VariableBaseMSM>::msm_bigint(bases, bigints)
  *      at univariate_kzg/mod.rs:109-111 (commit) and :151-155 (open).
  * Computes sum_{i<n} scalars[i] * srs[base_offset + i]; base_offset = num_leading_zeros of
@@ -451,7 +510,8 @@ MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uin
  * refused by mzk_prover_create with MZK_ERR_UNSUPPORTED. */
 #define MZK_ERR_WRONG_QUOTIENT_DEGREE (-9) /* PlonkError::WrongQuotientPolyDegree: the witness does not satisfy the circuit */
 #define MZK_ERR_STATE (-10)                /* prover rounds called out of order */
-#define MZK_ERR_ENCODING (-11)             /* invalid point encoding: mzk_last_error() = "point <i>: <reason>" (mzk_srs_register_serialized) */
+#define MZK_ERR_ENCODING (-11)             /* invalid point encoding: mzk_last_error() = "point <i>: <reason>" (mzk_srs_register_serialized); a serialized key
+                                            * that is refused: "<field> ..: <reason>" (mzk_key_layout, mzk_fr_decode_dev, mzk_prover_create_serialized) */
 
 /* Several devices / processes: this prover is rank `rank` of `world` -- it commits over the SRS points
  * [rank (n+3) / world ..) of every polynomial, evaluates ceil(W / world) residue classes of the quotient, runs rounds 4-5 on its
@@ -500,6 +560,37 @@ MZK_API int32_t mzk_prover_create_from_circuit(int32_t curve_id, uint32_t log_n,
 MZK_API int32_t mzk_prover_create_from_circuit_dev(int32_t curve_id, uint32_t log_n, uint32_t num_wire_types, const void* d_selector_values,
                                                    const void* d_wire_variables, uint64_t n_vars, const void* d_table_values, const uint64_t* k_mont,
                                                    uint64_t commit_key, uint64_t lagrange_key, const mzk_comm* comm, uint64_t* out_prover);
+/* The same prover from what a jf-plonk user holds: the CanonicalSerialize image of a `ProvingKey<E>` (format: mzk_key_layout above).
+ * flags: MZK_SER_COMPRESSED states the image's mode; MZK_SER_VALIDATE applies to the G1 records of the commit key, as for
+ * mzk_srs_register_serialized; MZK_KEY_CHECK_COMMITMENTS below.  The container is parsed on the host (mzk_key_layout), the image staged
+ * on the device in ONE copy, all polynomials and k decoded in ONE launch (mzk_fr_decode_dev: range check, Montgomery form, zero fill)
+ * into nsel + W (+ 4) rows of n, and the prover built from those rows: the coefficient forms never exist on the host.
+ * commit_key == 0: the embedded commit key is registered from the staged bytes (mzk_srs_register_serialized_dev) and its handle returned in
+ * *out_commit_key (required then); the caller releases it after the prover.  commit_key != 0: that handle is used, the embedded points
+ * are skipped and not compared -- one SRS and its fixed-base table serve many keys -- and *out_commit_key (nullable) is 0.
+ * out_lagrange_key non-NULL: the Lagrange-basis key is derived (mzk_srs_lagrange_from_srs(ck, log_n, 3)), given to the prover and returned;
+ * the caller releases it too.  The G2 elements and the commitments inside vk are not decoded: they pass through as bytes.
+ * MZK_KEY_CHECK_COMMITMENTS: the prover's own commitments (mzk_prover_vk_commitments), encoded in the image's mode ((0, 0) as ark's
+ * infinity: the commitment of a zero selector), must equal the records of vk bytewise, and vk.open_key.g commit-key point 0.
+ * MZK_ERR_ENCODING: mzk_last_error() names the field -- "sigmas[2] coefficient 5: not below the modulus", "commit_key point 7: not in the
+ * subgroup", "vk.selector_comms[3] does not commit selectors[3]", or mzk_key_layout's text -- and *out_bad (nullable) holds the index
+ * within the field (UINT64_MAX for container errors).  On any failure no handle exists and nothing stays allocated.  comm: NULL or world 1;
+ * world > 1 is MZK_ERR_UNSUPPORTED (sharded loading).  Domain sizes mzk_prover_create refuses are refused alike.  Synchronises.
+ * Set-up peak: the staged image (len bytes) plus the rows ((nsel + W (+ 4) + 1) x n x 32 B) besides the prover's own memory and, when
+ * it is registered here, the commit key with its decode; both are handed back before the call returns. */
+MZK_API int32_t mzk_prover_create_serialized(int32_t curve_id, const uint8_t* bytes, uint64_t len, uint32_t flags, uint64_t commit_key, const mzk_comm* comm,
+                                             uint64_t* out_prover, uint64_t* out_commit_key, uint64_t* out_lagrange_key, uint64_t* out_bad);
+/* The `ProvingKey` image of ANY prover handle, however it was created (flags: MZK_SER_COMPRESSED or 0): polynomial lengths from
+ * mzk_poly_degree_dev on the resident rows (trailing zeros stripped, as from_coefficients_vec does), records from mzk_fr_encode_dev,
+ * commitments from mzk_prover_vk_commitments, k and domain_size from the key, g = commit-key point 0, the commit key its first n + 3 points
+ * (trim(n + 2)).  What the library does not hold is the caller's: num_inputs, is_merged and the two G2 elements of the open key as bytes of
+ * the same mode (g2 record bytes each; copied, not looked at).  out_bytes == NULL: only *out_len, the size, is written (no commitment is
+ * computed); else capacity >= that size (MZK_ERR_INVALID_ARG).  mzk_prover_serialize_vk: the `VerifyingKey` image alone -- the vk slice of
+ * the former.  MZK_ERR_UNSUPPORTED: the handle's commit key is a rank's slice.  Both synchronise; staging: one row of n records. */
+MZK_API int32_t mzk_prover_serialize_key(uint64_t prover, uint32_t flags, uint64_t num_inputs, const uint8_t* h_bytes, const uint8_t* beta_h_bytes,
+                                         int32_t is_merged, uint8_t* out_bytes, uint64_t capacity, uint64_t* out_len);
+MZK_API int32_t mzk_prover_serialize_vk(uint64_t prover, uint32_t flags, uint64_t num_inputs, const uint8_t* h_bytes, const uint8_t* beta_h_bytes,
+                                        int32_t is_merged, uint8_t* out_bytes, uint64_t capacity, uint64_t* out_len);
 MZK_API int32_t mzk_prover_destroy(uint64_t prover);
 /* Another slot on the same proving key: a new handle on `prover`'s device context that SHARES its key part -- the coefficient forms, the
  * chunked proving key with its resident class evaluations, the SRS handles and the resident variable table -- and owns a fresh

@@ -181,6 +181,29 @@ macro_rules! curve_fixtures {
                 out
             }
 
+            /// Family `proving_key` (-> ref_proving_keys.json): the cases of proof_vectors_refsetup.json again, recording the reference's OWN
+            /// `pk.serialize_compressed()`, `pk.serialize_uncompressed()` and `vk.serialize_compressed()` beside the proof.  The library
+            /// restates that format (include/mzk.h, mzk_key_layout); tests/test_key_io_gpu.py loads these images, proves and saves them
+            /// back byte for byte once this file exists -- until then the format's parity with ark's derive is unpinned.
+            pub fn proving_key(case: &Value) -> Value {
+                let num_gates = case["num_gates"].as_u64().unwrap() as usize;
+                let ultra = case["plonk_type"].as_str().unwrap() == "UltraPlonk";
+                let cs = bench_circuit(num_gates, ultra, case["range_bit_len"].as_u64().unwrap() as usize);
+                let n = cs.eval_domain_size().unwrap();
+                let rng = &mut jf_utils::test_rng();
+                let srs = PlonkKzgSnark::<E>::universal_setup_for_testing(n + 2, rng).unwrap();
+                let (pk, vk) = PlonkKzgSnark::<E>::preprocess(&srs, &cs).unwrap();
+                let proof = PlonkKzgSnark::<E>::prove::<_, _, StandardTranscript>(rng, &cs, &pk, None).unwrap();
+                let (mut pk_c, mut pk_u, mut vk_c, mut bytes) = (Vec::new(), Vec::new(), Vec::new(), Vec::new());
+                pk.serialize_compressed(&mut pk_c).unwrap();
+                pk.serialize_uncompressed(&mut pk_u).unwrap();
+                vk.serialize_compressed(&mut vk_c).unwrap();
+                proof.serialize_compressed(&mut bytes).unwrap();
+                json!({"curve": case["curve"], "plonk_type": case["plonk_type"], "num_gates": num_gates, "domain_size": n,
+                       "range_bit_len": case["range_bit_len"], "pk_compressed": hex::encode(pk_c), "pk_uncompressed": hex::encode(pk_u),
+                       "vk_compressed": hex::encode(vk_c), "proof": hex::encode(bytes)})
+            }
+
             /// plonk/benches/bench.rs:29-46, finalised
             fn bench_circuit(num_gates: usize, ultra: bool, range_bits: usize) -> PlonkCircuit<Fr> {
                 let mut cs: PlonkCircuit<Fr> = if ultra { PlonkCircuit::new_ultra_plonk(range_bits) } else { PlonkCircuit::new_turbo_plonk() };
@@ -393,6 +416,7 @@ fn main() {
     run(dir, "kzg_vectors", bls::kzg, bn::kzg);
     run(dir, "proof_vectors", bls::proof, bn::proof);
     run(dir, "proof_vectors_refsetup", bls::proof, bn::proof);
+    run_to(dir, "proof_vectors_refsetup", "ref_proving_keys", bls::proving_key, bn::proving_key);
     run(dir, "batch_vectors", bls::batch, bn::batch);
     run(dir, "link_vectors", bls::link, bn::link);
     run_to(dir, "general_ref_cases", "ref_general_circuits", bls::general, bn::general);

@@ -38,6 +38,59 @@ extern "C" {
                          coset_offset_mont: *const u64) -> i32;
     pub fn mzk_host_alloc(bytes: u64, out_ptr: *mut *mut c_void) -> i32;
     pub fn mzk_host_free(ptr: *mut c_void) -> i32;
+    // serialized ProvingKey / VerifyingKey (ark-serialize 0.4 images; include/mzk.h): the container parser (host-only), the Fr record
+    // primitives, load and save.  `rounds::Mi355Prover::from_proving_key` / `serialize_key` are the callers.
+    pub fn mzk_key_layout(curve_id: i32, bytes: *const u8, len: u64, flags: u32, out: *mut KeyLayout) -> i32;
+    pub fn mzk_fr_decode_dev(curve_id: i32, d_image: *const c_void, image_len: u64, n_segments: u32, src_offsets: *const u64, counts: *const u64,
+                             dst_rows: *const u32, d_out: *mut c_void, n_rows: u32, row_len: u64, out_bad_segment: *mut u32, out_bad_index: *mut u64,
+                             stream: *mut c_void) -> i32;
+    pub fn mzk_fr_encode_dev(curve_id: i32, d_in: *const c_void, count: u64, d_out: *mut c_void, stream: *mut c_void) -> i32;
+    pub fn mzk_prover_create_serialized(curve_id: i32, bytes: *const u8, len: u64, flags: u32, commit_key: u64, comm: *const c_void, out_prover: *mut u64,
+                                        out_commit_key: *mut u64, out_lagrange_key: *mut u64, out_bad: *mut u64) -> i32;
+    pub fn mzk_prover_serialize_key(prover: u64, flags: u32, num_inputs: u64, h_bytes: *const u8, beta_h_bytes: *const u8, is_merged: i32,
+                                    out_bytes: *mut u8, capacity: u64, out_len: *mut u64) -> i32;
+    pub fn mzk_prover_serialize_vk(prover: u64, flags: u32, num_inputs: u64, h_bytes: *const u8, beta_h_bytes: *const u8, is_merged: i32,
+                                   out_bytes: *mut u8, capacity: u64, out_len: *mut u64) -> i32;
+}
+
+pub const MZK_SER_COMPRESSED: u32 = 1;
+pub const MZK_SER_VALIDATE: u32 = 2;
+pub const MZK_KEY_CHECK_COMMITMENTS: u32 = 4;
+pub const MZK_KEY_VK_ONLY: u32 = 8;
+pub const MZK_ERR_ENCODING: i32 = -11;
+
+/// `mzk_key_layout_t` (include/mzk.h): where every field of a serialized `ProvingKey` / `VerifyingKey` sits.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct KeyLayout {
+    pub num_wire_types: u32,
+    pub num_selectors: u32,
+    pub has_plookup: u32,
+    pub has_plookup_vk: u32,
+    pub is_merged: u32,
+    pub reserved: u32,
+    pub domain_size: u64,
+    pub num_inputs: u64,
+    pub g1_record_bytes: u64,
+    pub g2_record_bytes: u64,
+    pub sigma_off: [u64; 6],
+    pub sigma_len: [u64; 6],
+    pub selector_off: [u64; 14],
+    pub selector_len: [u64; 14],
+    pub table_off: [u64; 4],
+    pub table_len: [u64; 4],
+    pub commit_key_off: u64,
+    pub commit_key_count: u64,
+    pub vk_off: u64,
+    pub vk_len: u64,
+    pub sigma_comms_off: u64,
+    pub selector_comms_off: u64,
+    pub k_off: u64,
+    pub g_off: u64,
+    pub h_off: u64,
+    pub beta_h_off: u64,
+    pub plookup_comms_off: u64,
+    pub total_len: u64,
 }
 
 #[derive(Debug)]

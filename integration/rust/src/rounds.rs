@@ -17,7 +17,10 @@ use ark_std::rand::{CryptoRng, RngCore};
 use core::ffi::c_void;
 use std::sync::Arc;
 
-use crate::{check, mzk_srs_release, Mi355Error, SrsHandle};
+use ark_serialize::CanonicalSerialize;
+
+use crate::{check, mzk_prover_create_serialized, mzk_prover_serialize_key, mzk_prover_serialize_vk, mzk_srs_release, Mi355Error, SrsHandle, MZK_ERR_ENCODING,
+            MZK_KEY_CHECK_COMMITMENTS, MZK_SER_COMPRESSED, MZK_SER_VALIDATE};
 
 pub const MZK_WITNESS_HOST_VECTOR: i32 = 2;
 pub const MZK_ERR_WRONG_QUOTIENT_DEGREE: i32 = -9;
@@ -106,6 +109,8 @@ pub struct Mi355Prover {
     fq_limbs: usize,
     /// the Lagrange-basis key derived for this prover (None = round 1 commits the coefficient forms), shared with its forks
     lagrange_key: Option<Arc<LagrangeKey>>,
+    /// the commit key registered from a serialized `ProvingKey` (`from_proving_key`; None = the caller's `SrsHandle`), shared with its forks
+    embedded_commit_key: Option<Arc<LagrangeKey>>,
 }
 
 impl Drop for Mi355Prover {
@@ -148,7 +153,7 @@ impl Mi355Prover {
             made?;
         }
         // from here on Drop releases both handles
-        let me = Self { handle, num_wire_types, ultra: tables.is_some(), fq_limbs, lagrange_key: owned(lagrange) };
+        let me = Self { handle, num_wire_types, ultra: tables.is_some(), fq_limbs, lagrange_key: owned(lagrange), embedded_commit_key: None };
         unsafe { check(mzk_prover_set_wire_variables(handle, wire_variables.as_ptr(), n_vars as u64))? };
         Ok(me)
     }
@@ -176,7 +181,41 @@ impl Mi355Prover {
             }
             made?;
         }
-        Ok(Self { handle, num_wire_types, ultra: table_values.is_some(), fq_limbs, lagrange_key: owned(lagrange) })
+        Ok(Self { handle, num_wire_types, ultra: table_values.is_some(), fq_limbs, lagrange_key: owned(lagrange), embedded_commit_key: None })
+    }
+
+    /// The same prover from a `ProvingKey<E>` as it is: `pk.serialize_compressed()` (ark-serialize 0.4; the image every Rust deployment
+    /// already writes next to its SRS) handed to `mzk_prover_create_serialized`, which parses the container on the host and decodes the
+    /// polynomials, `k` and the commit key on the device -- no field element is pulled apart on the Rust side.  `commit_key`: a registered
+    /// SRS to use instead of the embedded one (one SRS and its fixed-base table then serve many keys; the embedded points are skipped, not
+    /// compared); `check_commitments`: the commitments in `pk.vk` must commit the key's polynomials (`MZK_KEY_CHECK_COMMITMENTS`).  The
+    /// prover has no wire-variable table: `mzk_prover_derive_wire_variables` recovers one from sigma, or set the circuit's.
+    /// Parity of the library's restatement of the format with ark's derive is UNPINNED until `gen_fixtures proving_key` has been run
+    /// (tests/golden/ref_proving_keys.json).
+    pub fn from_proving_key<K: CanonicalSerialize>(curve_id: i32, pk: &K, num_wire_types: usize, commit_key: Option<&SrsHandle>, lagrange_round1: bool,
+                                                   check_commitments: bool, fq_limbs: usize) -> Result<Self, Mi355Error> {
+        let mut bytes = Vec::with_capacity(pk.compressed_size());
+        pk.serialize_compressed(&mut bytes).map_err(|e| Mi355Error(MZK_ERR_ENCODING, e.to_string()))?;
+        let flags = MZK_SER_COMPRESSED | MZK_SER_VALIDATE | if check_commitments { MZK_KEY_CHECK_COMMITMENTS } else { 0 };
+        let (mut handle, mut ck, mut lagrange, mut bad) = (0u64, 0u64, 0u64, 0u64);
+        unsafe {
+            check(mzk_prover_create_serialized(curve_id, bytes.as_ptr(), bytes.len() as u64, flags, commit_key.map_or(0, |s| s.raw()), core::ptr::null(),
+                                               &mut handle, &mut ck, if lagrange_round1 { &mut lagrange } else { core::ptr::null_mut() }, &mut bad))?;
+        }
+        Ok(Self { handle, num_wire_types, ultra: num_wire_types == 6, fq_limbs, lagrange_key: owned(lagrange), embedded_commit_key: owned(ck) })
+    }
+
+    /// `CanonicalSerialize` of the `ProvingKey` (or, `vk_only`, the `VerifyingKey`) of this prover, however it was created -- a key
+    /// preprocessed on the device goes back to Rust as bytes `ProvingKey::<E>::deserialize_compressed` reads.  `h` / `beta_h`: the open
+    /// key's G2 elements serialized in the same mode (the library does not hold them).
+    pub fn serialize_key(&self, vk_only: bool, compressed: bool, num_inputs: usize, h: &[u8], beta_h: &[u8], is_merged: bool) -> Result<Vec<u8>, Mi355Error> {
+        let f = if vk_only { mzk_prover_serialize_vk } else { mzk_prover_serialize_key };
+        let flags = if compressed { MZK_SER_COMPRESSED } else { 0 };
+        let mut len = 0u64;
+        unsafe { check(f(self.handle, flags, num_inputs as u64, core::ptr::null(), core::ptr::null(), is_merged as i32, core::ptr::null_mut(), 0, &mut len))? };
+        let mut out = vec![0u8; len as usize];
+        unsafe { check(f(self.handle, flags, num_inputs as u64, h.as_ptr(), beta_h.as_ptr(), is_merged as i32, out.as_mut_ptr(), len, &mut len))? };
+        Ok(out)
     }
 
     /// Another slot on this prover's proving key (`mzk_prover_fork`): the key, its Lagrange key and the variable table stay ONE copy in
@@ -186,7 +225,8 @@ impl Mi355Prover {
     pub fn fork(&self) -> Result<Self, Mi355Error> {
         let mut handle = 0u64;
         unsafe { check(mzk_prover_fork(self.handle, &mut handle))? };
-        Ok(Self { handle, num_wire_types: self.num_wire_types, ultra: self.ultra, fq_limbs: self.fq_limbs, lagrange_key: self.lagrange_key.clone() })
+        Ok(Self { handle, num_wire_types: self.num_wire_types, ultra: self.ultra, fq_limbs: self.fq_limbs, lagrange_key: self.lagrange_key.clone(),
+                  embedded_commit_key: self.embedded_commit_key.clone() })
     }
 
     /// (fixed coefficient forms, proving-key evaluations, workspace) this slot reaches, then the bytes among them that other living

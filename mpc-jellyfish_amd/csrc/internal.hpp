@@ -25,6 +25,8 @@ extern "C" int32_t mzk_ctx_pk_register_chunked(int32_t curve_id, uint32_t log_n,
 extern "C" int32_t mzk_ctx_check_witness(uint64_t pk_handle, const mzk::WitnessCheckIn* in, mzk_witness_report* out_report, void* stream);
 // ... and derives the wire-variable table of a prover handle from its key's sigma coefficient forms (plonk.hip plonk_derive_variables_dev)
 extern "C" int32_t mzk_ctx_derive_variables(uint64_t pk_handle, const void* d_sigma_coeffs, void* d_out_variables_u32, uint64_t* out_n_vars, void* stream);
+// ... and encodes affine points in host memory as G1 records (the encoder of mzk_srs_serialize): the commitments of a serialized key
+extern "C" int32_t mzk_ctx_g1_encode(int32_t curve_id, const uint64_t* xy_mont, uint64_t n_points, uint32_t flags, uint8_t* out_bytes);
 
 namespace mzk {
 
@@ -194,6 +196,13 @@ const char* srs_bad_reason(int k);
 int32_t srs_decode_dispatch(int curve, const uint8_t* d_in, uint64_t n, bool compressed, bool validate, uint32_t* d_xy, uint64_t* out_bad, int* out_reason,
                             hipStream_t st);
 int32_t srs_encode_dispatch(int curve, const uint32_t* d_xy, uint64_t n, bool compressed, uint8_t* d_out, hipStream_t st);
+
+// key_io.hip: the Fr records of a serialized key (key_io.cuh).  Decode: n_seg <= 32 segments of one staged image into rows of row_len
+// aligned Montgomery elements, zero beyond a segment's count; *out_bad_seg / *out_bad_index = the lowest (segment, index) not below r, or
+// all ones; synchronises st.  Arguments are validated by the entry points (mzk.hip).
+int32_t fr_decode_dispatch(int curve, const uint8_t* d_image, uint32_t n_seg, const uint64_t* src, const uint64_t* count, const uint32_t* row, uint32_t* d_out,
+                           uint64_t row_len, uint32_t* out_bad_seg, uint64_t* out_bad_index, hipStream_t st);
+int32_t fr_encode_dispatch(int curve, const uint32_t* d_in, uint64_t n, uint32_t* d_out, hipStream_t st);
 
 // poly.hip
 int32_t poly_eval_dispatch(int curve, const uint32_t* d_coeffs, uint64_t stride, uint64_t len, uint32_t batch, const uint32_t* x_mont, uint32_t* out_host,

@@ -440,6 +440,54 @@ int32_t mzk_srs_serialize(uint64_t handle, uint64_t first, uint64_t n_points, ui
     ProfScope ps("srs_save.copy", nullptr);
     return hip_status(hipMemcpy(out_bytes, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy of the SRS records");
 }
+// (library-internal, internal.hpp) n affine points in host memory (x||y mont, (0, 0) = infinity) -> their records in host memory: the
+// commitments of a key under serialization or comparison (prover.hip), through the encoder of mzk_srs_serialize
+int32_t mzk_ctx_g1_encode(int32_t curve_id, const uint64_t* xy_mont, uint64_t n_points, uint32_t flags, uint8_t* out_bytes) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || !xy_mont || !out_bytes || !n_points) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    const size_t in_bytes = (size_t)n_points * srs_point_bytes(curve_id), out_len = (size_t)n_points * srs_record_bytes(curve_id, flags & MZK_SER_COMPRESSED);
+    DevScratch d_in, d_out;
+    HIP_TRY(hipMalloc((void**)&d_in.p, in_bytes));
+    HIP_TRY(hipMalloc((void**)&d_out.p, out_len));
+    HIP_TRY(hipMemcpy(d_in.p, xy_mont, in_bytes, hipMemcpyHostToDevice));
+    MZK_TRY(srs_encode_dispatch(curve_id, reinterpret_cast<const uint32_t*>(d_in.p), n_points, flags & MZK_SER_COMPRESSED, d_out.p, nullptr));
+    return hip_status(hipMemcpy(out_bytes, d_out.p, out_len, hipMemcpyDeviceToHost), "hipMemcpy of the G1 records");
+}
+// ---- Fr records of a serialized key (key_io.hip) ----
+int32_t mzk_fr_decode_dev(int32_t curve_id, const void* d_image, uint64_t image_len, uint32_t n_segments, const uint64_t* src_offsets, const uint64_t* counts,
+                          const uint32_t* dst_rows, void* d_out, uint32_t n_rows, uint64_t row_len, uint32_t* out_bad_segment, uint64_t* out_bad_index, void* stream) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || n_segments > 32 || (n_segments && (!d_image || !src_offsets || !counts || !dst_rows || !d_out)) || row_len >= (1ull << 40) ||
+        (reinterpret_cast<uintptr_t>(d_image) & 3) || (reinterpret_cast<uintptr_t>(d_out) & 15)) {
+        set_error("bad argument (at most 32 segments, rows below 2^40 slots, d_image 4-byte and d_out 16-byte aligned)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    for (uint32_t s = 0; s < n_segments; s++)                       // (no product before its bound: counts[s] <= row_len < 2^40)
+        if (counts[s] > row_len || dst_rows[s] >= n_rows || src_offsets[s] > image_len || counts[s] * 32 > image_len - src_offsets[s]) {
+            set_error("segment " + std::to_string(s) + ": records outside the image, more records than the row holds, or a row outside d_out");
+            return MZK_ERR_INVALID_ARG;
+        }
+    uint32_t bad_seg = ~0u;
+    uint64_t bad_index = ~0ull;
+    const int32_t rc = fr_decode_dispatch(curve_id, reinterpret_cast<const uint8_t*>(d_image), n_segments, src_offsets, counts, dst_rows,
+                                          reinterpret_cast<uint32_t*>(d_out), row_len, &bad_seg, &bad_index, (hipStream_t)stream);
+    if (out_bad_segment) *out_bad_segment = bad_seg;
+    if (out_bad_index) *out_bad_index = bad_index;
+    MZK_TRY(rc);
+    if (bad_seg != ~0u) {
+        set_error("segment " + std::to_string(bad_seg) + " coefficient " + std::to_string(bad_index) + ": not below the modulus");
+        return MZK_ERR_ENCODING;
+    }
+    return MZK_OK;
+}
+int32_t mzk_fr_encode_dev(int32_t curve_id, const void* d_in, uint64_t count, void* d_out, void* stream) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || (count && (!d_in || !d_out)) || (reinterpret_cast<uintptr_t>(d_out) & 3) || (reinterpret_cast<uintptr_t>(d_in) & 15)) {
+        set_error("bad argument (d_in 16-byte aligned, d_out 4-byte aligned)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return fr_encode_dispatch(curve_id, reinterpret_cast<const uint32_t*>(d_in), count, reinterpret_cast<uint32_t*>(d_out), (hipStream_t)stream);
+}
 // a new SRS holding the points [first, first + n_points) of a registered one (on its device): a rank of a multi-GPU prover keeps only
 // the range it commits over -- 1 / G of the points and of the fixed-base table, whose window then follows the slice's size
 int32_t mzk_srs_slice(uint64_t handle, uint64_t first, uint64_t n_points, uint64_t* out_handle) {

@@ -15,6 +15,7 @@
 
 #include "hostfp.hpp"
 #include "internal.hpp"
+#include "keyfmt.hpp"
 
 namespace mzk {
 namespace {
@@ -118,6 +119,9 @@ struct ProverBase {
     virtual void hbm_bytes(uint64_t* fixed_b, uint64_t* pk_b, uint64_t* ws_b) = 0;
     virtual void shared_hbm_bytes(uint64_t* shared_b, uint32_t* sharers) = 0;
     virtual std::shared_ptr<ProverBase> fork() = 0;
+    virtual void serialize(bool vk_only, uint32_t flags, uint64_t num_inputs, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, bool is_merged, uint8_t* out,
+                           uint64_t capacity, uint64_t* out_len) = 0;
+    virtual void check_vk_records(const uint8_t* image, const mzk_key_layout_t& L, bool compressed, uint64_t* out_bad) = 0;
 };
 
 template <class FrP, int CURVE>
@@ -337,6 +341,10 @@ struct ProverT final : ProverBase {
         peer_dev.assign(devices, devices + world);
     }
     void poly_dev(uint32_t which, const void** out_p, uint64_t* out_len) override;   // prover_setup.inc
+    // ---- the key as the reference's serialized ProvingKey / VerifyingKey ----------------------------------------------------------
+    void serialize(bool vk_only, uint32_t flags, uint64_t num_inputs, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, bool is_merged, uint8_t* out,
+        uint64_t capacity, uint64_t* out_len) override;   // prover_key_io.inc
+    void check_vk_records(const uint8_t* image, const mzk_key_layout_t& L, bool compressed, uint64_t* out_bad) override;   // prover_key_io.inc
 };
 
 #include "prover_setup.inc"
@@ -346,6 +354,7 @@ struct ProverT final : ProverBase {
 #include "prover_round3.inc"
 #include "prover_round4.inc"
 #include "prover_round5.inc"
+#include "prover_key_io.inc"
 
 
 // ---- registry --------------------------------------------------------------------------------------------------------------------
@@ -472,6 +481,95 @@ int32_t create_from_circuit(bool on_device, int32_t curve_id, uint32_t log_n, ui
     return MZK_OK;
 }
 
+// SRS handles a load registered itself: released on every path that does not hand them to the caller
+struct OwnedSrs {
+    uint64_t h = 0;
+    ~OwnedSrs() { if (h) (void)mzk_srs_release(h); }
+    uint64_t give() { const uint64_t r = h; h = 0; return r; }
+};
+
+// mzk_prover_create_serialized: parse the container on the host, stage the image in one copy, decode every polynomial and k in ONE launch
+// into the rows the constructor reads (COEFFS_ON_DEVICE: the coefficient forms never exist on the host), the commit key from the staged bytes
+int32_t create_serialized(int32_t curve_id, const uint8_t* bytes, uint64_t len, uint32_t flags, uint64_t commit_key, const mzk_comm* comm, uint64_t* out_prover,
+                          uint64_t* out_commit_key, uint64_t* out_lagrange_key, uint64_t* out_bad) {
+    if (out_bad) *out_bad = ~0ull;
+    if ((curve_id != 0 && curve_id != 1) || !bytes || !out_prover || (!commit_key && !out_commit_key) ||
+        (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE | MZK_KEY_CHECK_COMMITMENTS))) {
+        set_error("bad argument (out_commit_key is required when no commit_key is passed in)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    if (comm && comm->world > 1) { set_error("mzk_prover_create_serialized: sharded loading (an mzk_comm of world > 1) is not supported"); return MZK_ERR_UNSUPPORTED; }
+    mzk_key_layout_t L;
+    MZK_TRY(mzk_key_layout(curve_id, bytes, len, flags & MZK_SER_COMPRESSED, &L));
+    const uint32_t W = L.num_wire_types;
+    const int nsel = (int)L.num_selectors, nfix = nsel + (int)W + (W == 6 ? 4 : 0);
+    const uint64_t n = L.domain_size;
+    uint32_t log_n = 0;
+    while ((1ull << log_n) < n) log_n++;
+    MZK_TRY(create_args_ok(curve_id, log_n, W, true, W == 6 ? bytes : nullptr));
+    int32_t device = -1;
+    MZK_TRY(mzk_get_device(&device));
+    if (device < 0) { set_error("mzk_init has not been called"); return MZK_ERR_NOT_INIT; }
+    try {
+        Buf image, coeffs;
+        image.alloc((size_t)(len + EL - 1) / EL);
+        ck(mzk_dev_upload(image.p, bytes, len));
+        // rows 0 .. nfix - 1 in the constructor's order (selectors, sigmas, tables), then k: W elements over rows of n (n = 4 holds 5 in two)
+        const uint32_t k_rows = (uint32_t)((W + n - 1) / n);
+        coeffs.alloc((size_t)(nfix + k_rows) * n);
+        // segments in IMAGE order -- sigmas, selectors, k, tables -- so that the first failure reported is the first in the image
+        std::vector<uint64_t> src, cnt, base;
+        std::vector<uint32_t> row;
+        std::vector<std::string> name;
+        auto seg = [&](uint64_t off, uint64_t count, int r, const std::string& field, uint64_t first = 0) {
+            src.push_back(off); cnt.push_back(count); row.push_back((uint32_t)r); name.push_back(field); base.push_back(first);
+        };
+        for (uint32_t i = 0; i < W; i++) seg(L.sigma_off[i], L.sigma_len[i], nsel + (int)i, keyfmt::idx("sigmas", i));
+        for (int i = 0; i < nsel; i++) seg(L.selector_off[i], L.selector_len[i], i, keyfmt::idx("selectors", i));
+        for (uint64_t j = 0; j < W; j += n) seg(L.k_off + j * EL, std::min<uint64_t>(n, W - j), nfix + (int)(j / n), "vk.k", j);
+        static const char* const TAB[4] = {"plookup_pk.range_table_poly", "plookup_pk.key_table_poly", "plookup_pk.table_dom_sep_poly", "plookup_pk.q_dom_sep_poly"};
+        for (int i = 0; W == 6 && i < 4; i++) seg(L.table_off[i], L.table_len[i], nsel + (int)W + i, TAB[i]);
+        uint32_t bad_seg = ~0u;
+        uint64_t bad_index = ~0ull;
+        const int32_t rc = mzk_fr_decode_dev(curve_id, image.p, len, (uint32_t)src.size(), src.data(), cnt.data(), row.data(), coeffs.p, (uint32_t)(nfix + k_rows), n,
+                                             &bad_seg, &bad_index, nullptr);
+        if (rc == MZK_ERR_ENCODING) {
+            bad_index += base[bad_seg];
+            if (out_bad) *out_bad = bad_index;
+            fail(rc, name[bad_seg] + " coefficient " + std::to_string(bad_index) + ": not below the modulus");
+        }
+        ck(rc);
+        uint64_t k_mont[6 * 4];
+        ck(mzk_dev_download(k_mont, coeffs.at((size_t)nfix * n), (size_t)W * EL));
+        OwnedSrs own_ck, own_lk;
+        if (!commit_key) {
+            uint64_t bad_point = ~0ull;
+            const int32_t rs = mzk_srs_register_serialized_dev(curve_id, static_cast<const uint8_t*>(image.p) + L.commit_key_off, L.commit_key_count,
+                                                               flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), &own_ck.h, &bad_point, nullptr);
+            if (rs == MZK_ERR_ENCODING) {
+                if (out_bad) *out_bad = bad_point;
+                fail(rs, std::string("commit_key ") + mzk_last_error());
+            }
+            ck(rs);
+            commit_key = own_ck.h;
+        }
+        if (out_lagrange_key) ck(mzk_srs_lagrange_from_srs(commit_key, log_n, 3, &own_lk.h));
+        const uint64_t* c = static_cast<const uint64_t*>(coeffs.p);
+        auto p = make_prover(curve_id, log_n, W, c, c + (size_t)nsel * n * 4, W == 6 ? c + (size_t)(nsel + W) * n * 4 : nullptr, n, k_mont, commit_key, own_lk.h, nullptr,
+                             COEFFS_ON_DEVICE);
+        if (flags & MZK_KEY_CHECK_COMMITMENTS) p->check_vk_records(bytes, L, flags & MZK_SER_COMPRESSED, out_bad);
+        *out_prover = publish(std::move(p), device);
+        if (out_commit_key) *out_commit_key = own_ck.give();       // (0 when the caller passed one in)
+        if (out_lagrange_key) *out_lagrange_key = own_lk.give();
+    } catch (const Fail& e) {
+        return e.rc;
+    } catch (const std::bad_alloc&) {
+        set_error("out of host memory");
+        return MZK_ERR_OOM;
+    }
+    return MZK_OK;
+}
+
 }  // namespace
 }  // namespace mzk
 
@@ -511,6 +609,11 @@ int32_t mzk_prover_create_from_circuit_dev(int32_t curve_id, uint32_t log_n, uin
                                out_prover);
 }
 
+int32_t mzk_prover_create_serialized(int32_t curve_id, const uint8_t* bytes, uint64_t len, uint32_t flags, uint64_t commit_key, const mzk_comm* comm,
+                                     uint64_t* out_prover, uint64_t* out_commit_key, uint64_t* out_lagrange_key, uint64_t* out_bad) {
+    return create_serialized(curve_id, bytes, len, flags, commit_key, comm, out_prover, out_commit_key, out_lagrange_key, out_bad);
+}
+
 int32_t mzk_prover_destroy(uint64_t prover) {
     std::shared_ptr<ProverBase> p;
     {
@@ -533,6 +636,18 @@ int32_t mzk_prover_vk_commitments(uint64_t prover, uint64_t* out_xy_mont, uint64
     PROVER(prover);
     if (!out_xy_mont) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
     return guarded(*p_, [&] { p_->vk_commitments(out_xy_mont, out_plookup_xy_mont); });
+}
+int32_t mzk_prover_serialize_key(uint64_t prover, uint32_t flags, uint64_t num_inputs, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, int32_t is_merged,
+                                 uint8_t* out_bytes, uint64_t capacity, uint64_t* out_len) {
+    PROVER(prover);
+    if ((flags & ~MZK_SER_COMPRESSED) || (!out_bytes && !out_len)) { set_error("bad argument (flags: MZK_SER_COMPRESSED or 0)"); return MZK_ERR_INVALID_ARG; }
+    return guarded(*p_, [&] { p_->serialize(false, flags, num_inputs, h_bytes, beta_h_bytes, is_merged != 0, out_bytes, capacity, out_len); });
+}
+int32_t mzk_prover_serialize_vk(uint64_t prover, uint32_t flags, uint64_t num_inputs, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, int32_t is_merged,
+                                uint8_t* out_bytes, uint64_t capacity, uint64_t* out_len) {
+    PROVER(prover);
+    if ((flags & ~MZK_SER_COMPRESSED) || (!out_bytes && !out_len)) { set_error("bad argument (flags: MZK_SER_COMPRESSED or 0)"); return MZK_ERR_INVALID_ARG; }
+    return guarded(*p_, [&] { p_->serialize(true, flags, num_inputs, h_bytes, beta_h_bytes, is_merged != 0, out_bytes, capacity, out_len); });
 }
 int32_t mzk_prover_set_wire_variables(uint64_t prover, const uint32_t* wire_variables, uint64_t n_vars) {
     PROVER(prover);

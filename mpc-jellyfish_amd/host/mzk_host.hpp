@@ -67,6 +67,25 @@ struct SrsFile {
     const uint8_t* points() const { return bytes.data() + 8; }
 };
 
+// ---- a serialized proving key: CanonicalSerialize of jf-plonk's ProvingKey<E> (include/mzk.h, mzk_key_layout) --------------------
+// Read whole; the library parses the container (mzk_key_layout), decodes the polynomials and k on the device and checks what `flags`
+// ask for (MZK_SER_COMPRESSED: the image's mode; MZK_KEY_CHECK_COMMITMENTS): mzk_prover_create_serialized.
+struct KeyFile {
+    std::vector<uint8_t> bytes;
+    uint32_t flags = 0;
+    static KeyFile read(const char* path, uint32_t flags) {
+        KeyFile f;
+        f.flags = flags;
+        FILE* fp = std::fopen(path, "rb");
+        if (!fp) throw std::runtime_error(std::string("--pk: cannot open ") + path);
+        uint8_t chunk[1 << 16];
+        size_t got;
+        while ((got = std::fread(chunk, 1, sizeof chunk, fp)) > 0) f.bytes.insert(f.bytes.end(), chunk, chunk + got);
+        std::fclose(fp);
+        return f;
+    }
+};
+
 // ---- rand_chacha ChaCha{8,12,20}Rng and ark-ff's Fp::rand ------------------------------------------------
 struct ChaChaRng {
     uint32_t key[8];

@@ -9,6 +9,12 @@
 // sigma polynomials, so that --check-witness checks the copy constraints of a prover that came from coefficient forms (a circuit file
 // holds sigma values, not variables); when the first failing family is not the copy family, the first failing copy cell follows the counts.
 // Not with --host-witness-vars: that witness vector is in the circuit's numbering, the derived table in the canonical one.
+// --save-pk FILE (turbo, ultra, file; with --device-preprocess too): after the set-up the key is written as the CanonicalSerialize image of
+// the reference's `ProvingKey` (mzk_prover_serialize_key; compressed unless --pk-uncompressed; h and beta_h of the open key are zero bytes:
+// this host's testing setup has no G2 side).  --pk FILE (file): the proving key is read from such an image in place of the circuit file's
+// selector and sigma values (mzk_prover_create_serialized, the commit key being this host's: the embedded points are skipped); the witness
+// and the public input still come from the circuit file.  --pk-check: MZK_KEY_CHECK_COMMITMENTS.  --pk combines with --check-witness
+// --derive-variables.  The JSON line carries pk_bytes: the size of the image written or read (0: neither).
 // --srs FILE (turbo, ultra, file): commit over the powers of a setup file -- CanonicalSerialize of UnivariateUniversalParams, compressed --
 // decoded and validated on every device, instead of the testing SRS [beta^i] G.  The trapdoor is still drawn (and discarded) from the rng,
 // so the blinders are those of a run without --srs.  A file with fewer than n + 3 powers is an error.
@@ -48,6 +54,11 @@ struct Options {
                                   // sigma values on the device (mzk_prover_create_from_circuit_dev) -- same key, same bytes; bench circuits only
     bool derive_variables = false;  // --derive-variables: the wire-variable table from the key's sigma polynomials (mzk_prover_derive_wire_variables)
     bool check_witness = false;   // --check-witness: say where the witness fails before proving; exit status 3 if it does
+    const char* pk_path = nullptr;   // --pk FILE (file): the proving key from the reference's serialized ProvingKey in place of the circuit file's selector
+                                  // and sigma values; the witness and the public input still come from the circuit file
+    const char* save_pk_path = nullptr;  // --save-pk FILE: the key as that image, after any preprocess (h and beta_h of the open key: zero bytes)
+    bool pk_uncompressed = false; // --pk-uncompressed: the mode of both
+    bool pk_check = false;        // --pk-check: MZK_KEY_CHECK_COMMITMENTS on load
     int lagrange = -1;            // round 1 commits the wires from their VALUES over the Lagrange-basis key derived from the SRS (same proof
                                   // bytes): -1 = from 2^18 gates on (below, the heavy-bucket paths of small scalars cost more than they save: 2^15 gates 3.93 against 3.73 ms) when a sample of the witness
                                   // shows small values (a dense witness gains nothing from the key), --lagrange = always,
@@ -74,8 +85,18 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     double circuit_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     t0 = std::chrono::steady_clock::now();
     const bool lagrange = opt.lagrange < 0 ? (host.log_n >= 18 && host.witness_is_small()) : opt.lagrange != 0;
-    sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr, opt.device_preprocess);    // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
+    const KeyFile key_file = opt.pk_path ? KeyFile::read(opt.pk_path, (opt.pk_uncompressed ? 0u : MZK_SER_COMPRESSED) | (opt.pk_check ? MZK_KEY_CHECK_COMMITMENTS : 0u)) : KeyFile();
+    sp.setup(host, beta_c, opt.host_witness, lagrange, opt.slice_srs, opt.srs_path ? &srs_file : nullptr, opt.device_preprocess, opt.pk_path ? &key_file : nullptr);    // SRS, circuit upload and PlonkKzgSnark::preprocess on every device
     const double preprocess_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    size_t pk_bytes = key_file.bytes.size();
+    if (opt.save_pk_path) {
+        if (opt.gpus > 1 && opt.slice_srs) throw std::runtime_error("--save-pk: with --gpus G every rank holds a slice of the commit key; add --no-slice");
+        const std::vector<uint8_t> image = sp.prover[0]->serialize_key(!opt.pk_uncompressed, host.pub_input.size());
+        FILE* fp = std::fopen(opt.save_pk_path, "wb");
+        if (!fp || std::fwrite(image.data(), 1, image.size(), fp) != image.size()) throw std::runtime_error(std::string("--save-pk: cannot write ") + opt.save_pk_path);
+        std::fclose(fp);
+        pk_bytes = image.size();
+    }
     if (opt.derive_variables) sp.derive_wire_variables();
     if (opt.check_witness) {
         const mzk_witness_report rep = sp.check_witness();
@@ -137,7 +158,7 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
         for (const auto& cm : *v) { uint8_t b[48]; Encoding<C>::g1_bytes(cm, b); vk_bytes.insert(vk_bytes.end(), b, b + C::G1_BYTES); }
     std::string vk_hex;
     for (uint8_t b : vk_bytes) { vk_hex.push_back(d[b >> 4]); vk_hex.push_back(d[b & 15]); }
-    std::printf("}, \"vk_hex\": \"%s\", \"proof_hex\": \"%s\"}\n", vk_hex.c_str(), hex.c_str());
+    std::printf("}, \"pk_bytes\": %zu, \"vk_hex\": \"%s\", \"proof_hex\": \"%s\"}\n", pk_bytes, vk_hex.c_str(), hex.c_str());
     return 0;
 }
 
@@ -285,6 +306,10 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--check-witness") opt.check_witness = true;
         else if (a == "--derive-variables") opt.derive_variables = true;
         else if (a == "--device-preprocess") opt.device_preprocess = true;
+        else if (a == "--pk" && i + 1 < argc_in) opt.pk_path = argv_in[++i];
+        else if (a == "--save-pk" && i + 1 < argc_in) opt.save_pk_path = argv_in[++i];
+        else if (a == "--pk-uncompressed") opt.pk_uncompressed = true;
+        else if (a == "--pk-check") opt.pk_check = true;
         else if (a == "--lagrange") opt.lagrange = 1;
         else if (a == "--no-lagrange") opt.lagrange = 0;
         else if (a == "--no-slice") opt.slice_srs = false;
@@ -294,7 +319,7 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     if (opt.gpus < 1 || opt.gpus > 16) { std::fprintf(stderr, "mzk_prove: --gpus 1..16\n"); return 2; }
-    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--derive-variables] [--device-preprocess] [--no-lagrange] [--srs FILE]\n", argv[0]); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--derive-variables] [--device-preprocess] [--no-lagrange] [--srs FILE] [--save-pk FILE] [--pk FILE (file)] [--pk-uncompressed] [--pk-check]\n", argv[0]); return 2; }
     const int curve = std::atoi(argv[1]);
     if (opt.device_preprocess && (std::string(argv[2]) == "file" || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
         std::fprintf(stderr, "mzk_prove: --device-preprocess needs the circuit's variable table: a circuit file holds sigma values, not variables "
@@ -304,6 +329,14 @@ int main(int argc_in, char** argv_in) {
     if (opt.derive_variables && (opt.host_witness == 2 || opt.slots || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
         std::fprintf(stderr, "mzk_prove: --derive-variables goes with turbo, ultra and file, and not with --host-witness-vars (a witness vector in the circuit's "
                              "numbering) or --slots\n");
+        return 2;
+    }
+    if (opt.pk_path && std::string(argv[2]) != "file") {
+        std::fprintf(stderr, "mzk_prove: --pk goes with `file`: the key replaces the circuit file's selector and sigma values, its witness and public input stay\n");
+        return 2;
+    }
+    if ((opt.pk_path || opt.save_pk_path) && (opt.slots || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
+        std::fprintf(stderr, "mzk_prove: --pk / --save-pk go with turbo, ultra and file\n");
         return 2;
     }
     if (std::string(argv[2]) == "link") {

@@ -355,11 +355,7 @@ struct Prover {
         for (int i = 0; i < W; i++) std::memcpy(&kk[4 * i], k[i].l, 32);
         if (cs.device_preprocess) create_from_structure(cs, kk, lagrange_key, comm);
         else create_from_values(cs, kk, lagrange_key, comm);
-        std::vector<uint64_t> xy((size_t)(nsel + W) * 2 * QL);
-        check(mzk_prover_vk_commitments(handle, xy.data(), nullptr), "mzk_prover_vk_commitments");
-        auto pt = [&](size_t i) { Affine a; std::memcpy(a.data(), &xy[i * 2 * QL], sizeof(Affine)); return a; };
-        for (int i = 0; i < nsel; i++) selector_comms.push_back(pt(i));
-        for (int i = 0; i < W; i++) sigma_comms.push_back(pt(nsel + i));
+        read_vk_commitments();
         if (cs.host_witness == 2 && !cs.device_preprocess)
             check(mzk_prover_set_wire_variables(handle, cs.host_wire_variables.data(), cs.n_vars), "mzk_prover_set_wire_variables");
     }
@@ -380,6 +376,45 @@ struct Prover {
         const uint64_t* sel = host.data();
         const uint64_t* sig = sel + (size_t)nsel * n * 4;
         check(mzk_prover_create(C::ID, log_n, W, sel, sig, ultra ? sig + (size_t)W * n * 4 : nullptr, n, kk.data(), srs, lagrange_key, comm, &handle), "mzk_prover_create");
+    }
+    // The prover of a circuit whose proving key comes as the reference's serialized `ProvingKey` (mzk_prover_create_serialized): the
+    // circuit supplies the witness and the public input, the key everything else -- its k included.  The commit key is the caller's handle
+    // (the embedded points are skipped); out_lagrange_key non-null: the Lagrange-basis key is derived by the load and handed back.
+    Prover(uint64_t srs_handle, const BenchCircuit<C>& cs, const KeyFile& key, uint64_t* out_lagrange_key)
+        : ultra(cs.ultra), log_n(cs.log_n), W(cs.W), nsel(cs.nsel), n(cs.n), srs(srs_handle) {
+        mzk_key_layout_t lay;
+        check(mzk_key_layout(C::ID, key.bytes.data(), key.bytes.size(), key.flags & MZK_SER_COMPRESSED, &lay), "mzk_key_layout");
+        if (lay.domain_size != n || (int)lay.num_wire_types != W)
+            throw std::runtime_error("--pk: the key is for domain size " + std::to_string(lay.domain_size) + " and " + std::to_string(lay.num_wire_types) +
+                                     " wire types, the circuit has " + std::to_string(n) + " and " + std::to_string(W));
+        Fr r2;
+        for (int j = 0; j < 4; j++) r2.l[j] = Fr::c64(FrP::R2, j);
+        for (int i = 0; i < W; i++) {
+            Fr c;
+            std::memcpy(c.l, key.bytes.data() + lay.k_off + 32 * i, 32);
+            k.push_back(c * r2);
+        }
+        check(mzk_prover_create_serialized(C::ID, key.bytes.data(), key.bytes.size(), key.flags, srs, nullptr, &handle, nullptr, out_lagrange_key, nullptr),
+              "mzk_prover_create_serialized");
+        read_vk_commitments();
+    }
+    void read_vk_commitments() {
+        std::vector<uint64_t> xy((size_t)(nsel + W) * 2 * QL);
+        check(mzk_prover_vk_commitments(handle, xy.data(), nullptr), "mzk_prover_vk_commitments");
+        auto pt = [&](size_t i) { Affine a; std::memcpy(a.data(), &xy[i * 2 * QL], sizeof(Affine)); return a; };
+        for (int i = 0; i < nsel; i++) selector_comms.push_back(pt(i));
+        for (int i = 0; i < W; i++) sigma_comms.push_back(pt(nsel + i));
+    }
+    // the `ProvingKey` image of this prover (mzk_prover_serialize_key).  h, beta_h: the open key's G2 elements as bytes of the mode, which
+    // the library does not hold (nullptr: zero bytes -- the testing setup of this host has no G2 side)
+    std::vector<uint8_t> serialize_key(bool compressed, uint64_t num_inputs, const uint8_t* h = nullptr, const uint8_t* beta_h = nullptr) const {
+        const std::vector<uint8_t> zero((size_t)(C::ID == MZK_CURVE_BLS12_381 ? 96 : 64) * (compressed ? 1 : 2), 0);
+        const uint32_t flags = compressed ? MZK_SER_COMPRESSED : 0u;
+        uint64_t len = 0;
+        check(mzk_prover_serialize_key(handle, flags, num_inputs, nullptr, nullptr, 0, nullptr, 0, &len), "mzk_prover_serialize_key");
+        std::vector<uint8_t> out(len);
+        check(mzk_prover_serialize_key(handle, flags, num_inputs, h ? h : zero.data(), beta_h ? beta_h : zero.data(), 0, out.data(), len, &len), "mzk_prover_serialize_key");
+        return out;
     }
     // the wire-variable table from the key's own sigma polynomials (mzk_prover_derive_wire_variables): a prover from coefficient forms can
     // then check copy constraints; variables come in canonical numbering, so a witness VECTOR in the circuit's own numbering no longer fits
@@ -709,7 +744,8 @@ struct ShardedProver {
     // its fixed-base table, built with the window that suits the slice (2^17-point shards at G = 8: window 16 and fused small batches)
     // srs_file (nullable): the commit key is the file's first n + 3 powers, decoded and validated on every device, instead of [beta^i] G
     void setup(const BenchCircuitHost<C>& host, const std::array<uint64_t, 4>& beta_canonical, int host_witness = 0, bool lagrange = true, bool slice_srs = true,
-               const SrsFile* srs_file = nullptr, bool device_preprocess = false) {
+               const SrsFile* srs_file = nullptr, bool device_preprocess = false, const KeyFile* key_file = nullptr) {
+        if (key_file && G > 1) throw std::runtime_error("--pk: a serialized proving key is loaded on one device (sharded loading is not supported)");
         if (srs_file && srs_file->count < host.n + 3)
             throw std::runtime_error("--srs: the file holds " + std::to_string(srs_file->count) + " powers, the circuit needs n + 3 = " + std::to_string(host.n + 3));
         each([&](int r) {
@@ -718,7 +754,7 @@ struct ShardedProver {
                       "mzk_srs_register_serialized");
             else
                 check(mzk_srs_generate_for_testing(C::ID, beta_canonical.data(), host.n + 3, &srs[r]), "mzk_srs_generate_for_testing");
-            if (lagrange) {                                               // from the SRS's points alone (no trapdoor): an inverse NTT over the group
+            if (lagrange && !key_file) {                                  // from the SRS's points alone (no trapdoor): an inverse NTT over the group
                 const auto t0 = std::chrono::steady_clock::now();
                 check(mzk_srs_lagrange_from_srs(srs[r], (uint32_t)host.log_n, 3, &srs_lagrange[r]), "mzk_srs_lagrange_from_srs");
                 if (r == 0) lagrange_key_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -735,7 +771,8 @@ struct ShardedProver {
             }
             circuit[r] = std::make_unique<BenchCircuit<C>>(BenchCircuit<C>::upload(host, host_witness, device_preprocess));
             mzk_comm cm{&rank_ctx[r], r, G, &cb_all_gather, &cb_barrier, nullptr};
-            prover[r] = std::make_unique<P>(srs[r], *circuit[r], srs_lagrange[r], G > 1 ? &cm : nullptr);
+            if (key_file) prover[r] = std::make_unique<P>(srs[r], *circuit[r], *key_file, lagrange ? &srs_lagrange[r] : nullptr);   // (the load derives the Lagrange key)
+            else prover[r] = std::make_unique<P>(srs[r], *circuit[r], srs_lagrange[r], G > 1 ? &cm : nullptr);
         });
         if (G > 1) {                                                      // where every rank receives the class remainders of the others
             std::vector<void*> rem(G);

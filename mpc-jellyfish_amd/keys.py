@@ -1,0 +1,150 @@
+"""ProvingKey / VerifyingKey as their CanonicalSerialize images (ark-serialize 0.4, derive order; include/mzk.h, mzk_key_layout):
+
+    ProvingKey<E>    plonk/src/proof_system/structs.rs:575-590  -> ProvingKey.deserialize: a TurboPlonkProver on the GPU
+    VerifyingKey<E>  structs.rs:682-707                          -> VerifyingKey: fields, records as bytes, serialize / deserialize
+
+The container is parsed on the host (mzk_key_layout: no GPU); the polynomials, k and the commit key are decoded and checked on the
+device (mzk_prover_create_serialized).  G1 / G2 records of the verifying key are kept as the bytes they were read as.  The image names
+neither its curve nor its mode: the caller states both, as for the SRS (kzg.UnivariateProverParam.deserialize).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import re
+
+import numpy as np
+
+from . import kzg
+from . import lib as _lib
+from .kzg import SerializationError
+from .params import curve as _curve
+
+_SER_COMPRESSED, _SER_VALIDATE, _KEY_CHECK_COMMITMENTS, _KEY_VK_ONLY = 1, 2, 4, 8
+_ERR_ENCODING = -11
+_FIELD = re.compile(r"^([A-Za-z_.]+(?:\[\d+\])?(?:\.len)?)")
+
+
+class KeySerializationError(SerializationError):
+    """A serialized key that ark-serialize would refuse (MZK_ERR_ENCODING).  .field: the field of the image the error is in
+    ("sigmas[2]", "commit_key", "vk.selector_comms[3]", ..); .index: the index within it (coefficient, point; None for container
+    errors); .reason: the library's text."""
+
+    def __init__(self, reason: str, field: str | None, index: int | None = None):
+        ValueError.__init__(self, reason)
+        self.field, self.index, self.reason = field, index, reason
+
+
+def _raise_encoding(L, bad: int | None):
+    msg = L.mzk_last_error().decode()
+    m = _FIELD.match(msg[len("truncated in "):] if msg.startswith("truncated in ") else msg)
+    raise KeySerializationError(msg, m.group(1) if m else None, None if bad is None or bad == 2**64 - 1 else bad)
+
+
+def key_layout(curve, data, compress: bool = True, vk_only: bool = False) -> _lib.KeyLayout:
+    """mzk_key_layout: offsets and counts of every field of a ProvingKey (or, vk_only, a bare VerifyingKey) image.  Host-only."""
+    c = _curve(curve)
+    buf = kzg._as_bytes(data)
+    L = _lib.load()
+    out = _lib.KeyLayout()
+    rc = L.mzk_key_layout(c.curve_id, C.c_void_p(buf.ctypes.data) if buf.shape[0] else None, buf.shape[0],
+                          (_SER_COMPRESSED if compress else 0) | (_KEY_VK_ONLY if vk_only else 0), C.byref(out))
+    if rc == _ERR_ENCODING:
+        _raise_encoding(L, None)
+    _lib.check(rc, "mzk_key_layout")
+    return out
+
+
+class VerifyingKey:
+    """structs.rs:682-707.  domain_size, num_inputs, is_merged; k as canonical integers; sigma_comms / selector_comms / plookup_comms
+    (None for TurboPlonk) as lists of G1 records and g, h, beta_h as records, all bytes of the mode `compressed`."""
+
+    def __init__(self, curve, domain_size, num_inputs, sigma_comms, selector_comms, k, g, h, beta_h, is_merged=False, plookup_comms=None, compressed=True):
+        self.curve = _curve(curve)
+        self.domain_size, self.num_inputs, self.is_merged, self.compressed = domain_size, num_inputs, bool(is_merged), compressed
+        self.sigma_comms, self.selector_comms, self.k = [bytes(b) for b in sigma_comms], [bytes(b) for b in selector_comms], [int(x) for x in k]
+        self.g, self.h, self.beta_h = bytes(g), bytes(h), bytes(beta_h)
+        self.plookup_comms = None if plookup_comms is None else [bytes(b) for b in plookup_comms]
+
+    @classmethod
+    def _from_layout(cls, c, buf, lay, compress) -> "VerifyingKey":
+        g1, g2, W, nsel = lay.g1_record_bytes, lay.g2_record_bytes, lay.num_wire_types, lay.num_selectors
+        cut = lambda off, size: bytes(buf[off:off + size])
+        recs = lambda off, cnt: [cut(off + i * g1, g1) for i in range(cnt)]
+        return cls(c, lay.domain_size, lay.num_inputs, recs(lay.sigma_comms_off, W), recs(lay.selector_comms_off, nsel),
+                   [int.from_bytes(cut(lay.k_off + 32 * i, 32), "little") for i in range(W)], cut(lay.g_off, g1), cut(lay.h_off, g2), cut(lay.beta_h_off, g2),
+                   lay.is_merged, recs(lay.plookup_comms_off, 4) if lay.has_plookup_vk else None, compress)
+
+    @classmethod
+    def deserialize(cls, curve, data, compress: bool = True) -> "VerifyingKey":
+        """A bare VerifyingKey image (mzk_key_layout with MZK_KEY_VK_ONLY); raises KeySerializationError naming the field."""
+        c = _curve(curve)
+        buf = kzg._as_bytes(data)
+        return cls._from_layout(c, buf, key_layout(c, buf, compress, vk_only=True), compress)
+
+    def serialize(self) -> bytes:
+        u64 = lambda v: int(v).to_bytes(8, "little")
+        vec = lambda items: u64(len(items)) + b"".join(items)
+        out = u64(self.domain_size) + u64(self.num_inputs) + vec(self.sigma_comms) + vec(self.selector_comms)
+        out += vec([x.to_bytes(32, "little") for x in self.k]) + self.g + self.h + self.beta_h + bytes([int(self.is_merged)])
+        return out + (b"\x00" if self.plookup_comms is None else b"\x01" + b"".join(self.plookup_comms))
+
+
+class ProvingKey:
+    """A loaded `ProvingKey<E>`: .prover (a TurboPlonkProver whose coefficient forms were decoded on the device), .vk (VerifyingKey) and
+    the SRS handles this object owns (.commit_key unless one was passed in, .lagrange_key when asked for).  release() frees the prover,
+    then the keys it owns."""
+
+    def __init__(self, prover, vk: VerifyingKey, owned):
+        self.prover, self.vk, self._owned = prover, vk, list(owned)
+
+    @classmethod
+    def deserialize(cls, curve, data, compress: bool = True, validate: bool = True, check_commitments: bool = False,
+                    commit_key: kzg.UnivariateProverParam | None = None, lagrange: bool = False) -> "ProvingKey":
+        """mzk_prover_create_serialized.  compress / validate as for the SRS (they select ark's deserialize_* variant; validate applies
+        to the commit key's points); check_commitments: the commitments in vk must commit the key's polynomials and vk.open_key.g must
+        be commit-key point 0.  commit_key: an SRS already on the device -- the embedded points are then skipped, not compared, and one
+        SRS with its fixed-base table serves many keys.  lagrange: also derive the Lagrange-basis key (round 1 commits wire values).
+        Raises KeySerializationError with .field and .index."""
+        from .prover import TurboPlonkProver
+        c = _curve(curve)
+        buf = kzg._as_bytes(data)
+        if kzg._is_torch(buf):
+            raise ValueError("a key image is read from host memory")
+        lay = key_layout(c, buf, compress)
+        L = _lib.ensure_init()
+        flags = (_SER_COMPRESSED if compress else 0) | (_SER_VALIDATE if validate else 0) | (_KEY_CHECK_COMMITMENTS if check_commitments else 0)
+        assert commit_key is None or commit_key.offset == 0
+        h, ck, lk, bad = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = L.mzk_prover_create_serialized(c.curve_id, C.c_void_p(buf.ctypes.data), buf.shape[0], flags, commit_key.handle if commit_key is not None else 0, None,
+                                            C.byref(h), C.byref(ck), C.byref(lk) if lagrange else None, C.byref(bad))
+        if rc == _ERR_ENCODING:
+            _raise_encoding(L, bad.value)
+        _lib.check(rc, "mzk_prover_create_serialized")
+        n, W = lay.domain_size, lay.num_wire_types
+        vk = VerifyingKey._from_layout(c, buf, lay, compress)
+        own_ck = kzg.UnivariateProverParam(c, ck.value, lay.commit_key_count) if commit_key is None else None
+        own_lk = kzg.UnivariateProverParam(c, lk.value, n + 3) if lagrange else None
+        p = TurboPlonkProver.__new__(TurboPlonkProver)
+        p._describe(c, n, vk.k, own_ck if commit_key is None else commit_key, own_lk, W, lay.num_selectors)
+        p._adopt(h.value, None)
+        return cls(p, vk, [k for k in (own_lk, own_ck) if k is not None])
+
+    @property
+    def commit_key(self):
+        return self.prover.ck
+
+    @property
+    def lagrange_key(self):
+        return self.prover.lagrange_ck
+
+    def serialize(self, compress: bool | None = None) -> bytes:
+        """The image again, from the resident key (TurboPlonkProver.serialize_key with this key's vk fields)."""
+        compress = self.vk.compressed if compress is None else compress
+        assert compress == self.vk.compressed, "the G2 elements are held as bytes of the mode they were read in"
+        return self.prover.serialize_key(self.vk.num_inputs, self.vk.h, self.vk.beta_h, self.vk.is_merged, compress)
+
+    def release(self):
+        self.prover.release()
+        for k in self._owned:
+            k.release()
+        self._owned = []

@@ -26,6 +26,17 @@ class WitnessReport(C.Structure):
                 ("copy_rep_cell", C.c_uint64), ("row_wires", C.c_uint64 * 24), ("gate_residual", C.c_uint64 * 4)]
 
 
+class KeyLayout(C.Structure):
+    """mzk_key_layout_t (include/mzk.h)"""
+    _fields_ = [("num_wire_types", C.c_uint32), ("num_selectors", C.c_uint32), ("has_plookup", C.c_uint32), ("has_plookup_vk", C.c_uint32),
+                ("is_merged", C.c_uint32), ("reserved", C.c_uint32), ("domain_size", C.c_uint64), ("num_inputs", C.c_uint64),
+                ("g1_record_bytes", C.c_uint64), ("g2_record_bytes", C.c_uint64), ("sigma_off", C.c_uint64 * 6), ("sigma_len", C.c_uint64 * 6),
+                ("selector_off", C.c_uint64 * 14), ("selector_len", C.c_uint64 * 14), ("table_off", C.c_uint64 * 4), ("table_len", C.c_uint64 * 4),
+                ("commit_key_off", C.c_uint64), ("commit_key_count", C.c_uint64), ("vk_off", C.c_uint64), ("vk_len", C.c_uint64),
+                ("sigma_comms_off", C.c_uint64), ("selector_comms_off", C.c_uint64), ("k_off", C.c_uint64), ("g_off", C.c_uint64), ("h_off", C.c_uint64),
+                ("beta_h_off", C.c_uint64), ("plookup_comms_off", C.c_uint64), ("total_len", C.c_uint64)]
+
+
 _SIGS = {
     "mzk_init": [C.c_int32],
     "mzk_set_device": [C.c_int32],
@@ -43,6 +54,10 @@ _SIGS = {
     "mzk_srs_slice": [C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_srs_download": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p],
     "mzk_srs_len": [C.c_uint64, C.POINTER(C.c_uint64)],
+    "mzk_key_layout": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(KeyLayout)],
+    "mzk_fr_decode_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p],
+    "mzk_fr_encode_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_srs_register_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_srs_register_serialized_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_srs_serialize": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p],
@@ -129,6 +144,10 @@ _SIGS = {
                                        C.c_void_p, C.POINTER(C.c_uint64)],
     "mzk_prover_create_from_circuit_dev": [C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                            C.c_void_p, C.POINTER(C.c_uint64)],
+    "mzk_prover_create_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "mzk_prover_serialize_key": [C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
+    "mzk_prover_serialize_vk": [C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_prover_destroy": [C.c_uint64],
     "mzk_prover_fork": [C.c_uint64, C.POINTER(C.c_uint64)],
     "mzk_prover_vk_commitments": [C.c_uint64, C.c_void_p, C.c_void_p],

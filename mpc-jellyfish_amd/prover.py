@@ -330,6 +330,26 @@ class TurboPlonkProver:
         assert self.ultra
         return self._commitments()[1]
 
+    def _serialize(self, fn: str, num_inputs: int, h: bytes, beta_h: bytes, is_merged: bool, compress: bool) -> bytes:
+        g2 = kzg.g2_record_bytes(self.curve, compress)
+        if len(h) != g2 or len(beta_h) != g2:
+            raise kzg.SerializationError(f"G2 elements are {g2} bytes in this mode")
+        f, flags, size = getattr(_lib.load(), fn), 1 if compress else 0, C.c_uint64()
+        _check(f(self.handle, flags, num_inputs, h, beta_h, int(is_merged), None, 0, C.byref(size)), fn)
+        out = np.empty(size.value, dtype=np.uint8)
+        _check(f(self.handle, flags, num_inputs, h, beta_h, int(is_merged), _ptr(out), size.value, C.byref(size)), fn)
+        return out.tobytes()
+
+    def serialize_key(self, num_inputs: int, h: bytes, beta_h: bytes, is_merged: bool = False, compress: bool = True) -> bytes:
+        """The CanonicalSerialize image of the reference's `ProvingKey` for this prover, however it was created (mzk_prover_serialize_key):
+        what the library does not hold -- num_inputs, is_merged and the open key's G2 elements h, beta_h as bytes of the same mode -- is
+        the caller's.  keys.ProvingKey.deserialize reads it back."""
+        return self._serialize("mzk_prover_serialize_key", num_inputs, h, beta_h, is_merged, compress)
+
+    def serialize_vk(self, num_inputs: int, h: bytes, beta_h: bytes, is_merged: bool = False, compress: bool = True) -> bytes:
+        """The `VerifyingKey` image alone (mzk_prover_serialize_vk): the vk slice of serialize_key's."""
+        return self._serialize("mzk_prover_serialize_vk", num_inputs, h, beta_h, is_merged, compress)
+
     def set_wire_variables(self, wire_variables, n_vars: int):
         """wire_variables: (W, n) uint32 (host); witness kinds HOST_VECTOR / DEV_VECTOR gather through it on the device"""
         v = np.ascontiguousarray(wire_variables, dtype=np.uint32).reshape(self.W, self.n)
