@@ -153,6 +153,7 @@ __device__ __forceinline__ bool lookup_keys_equal(const LookupKey& x, const Look
     for (int e = 0; e < 5; e++) eq = eq && fr_words_equal(x.w[2 * e], x.w[2 * e + 1], y.w[2 * e], y.w[2 * e + 1]);
     return eq;
 }
+// restated in tests/plookup_cases.py, which aims keys at one probe chain: change both together
 __device__ __forceinline__ uint32_t lookup_key_hash(const LookupKey& k) {
     uint32_t h = 0;
 #pragma unroll

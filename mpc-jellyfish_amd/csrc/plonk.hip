@@ -1053,7 +1053,7 @@ int32_t plookup_sorted_vec_dev(uint64_t handle, const uint32_t* d_wires, const u
                                hipStream_t st) {
     const PlonkPk* pk = find_pk(handle);
     if (!pk) return MZK_ERR_BAD_HANDLE;
-    if (!pk->ultra || !d_wires || !tau || !d_table || !d_lookup || !d_sorted || pk->log_n < 2) {
+    if (!pk->ultra || !d_wires || !tau || !d_table || !d_lookup || !d_sorted) {
         set_error("bad argument (needs an UltraPlonk proving key)");
         return MZK_ERR_INVALID_ARG;
     }
@@ -1064,7 +1064,7 @@ int32_t plookup_product_dev(uint64_t handle, const uint32_t* d_table, const uint
                             const uint32_t* gamma, uint32_t* d_out, hipStream_t st) {
     const PlonkPk* pk = find_pk(handle);
     if (!pk) return MZK_ERR_BAD_HANDLE;
-    if (!pk->ultra || !d_table || !d_lookup || !d_sorted || !beta || !gamma || !d_out || pk->log_n < 2) {
+    if (!pk->ultra || !d_table || !d_lookup || !d_sorted || !beta || !gamma || !d_out) {
         set_error("bad argument (needs an UltraPlonk proving key)");
         return MZK_ERR_INVALID_ARG;
     }

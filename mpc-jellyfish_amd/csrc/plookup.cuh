@@ -56,6 +56,7 @@ __global__ __launch_bounds__(PLK_THREADS) void plookup_merge_kernel(MergeArgs a)
 __device__ __forceinline__ bool fr_words_equal(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
     return ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) == 0;
 }
+// restated in tests/plookup_cases.py, which aims values at one probe chain: change both together
 __device__ __forceinline__ uint32_t fr_words_hash(const uint4& a0, const uint4& a1) {
     uint32_t h = a0.x * 0x9E3779B1u;
     h = (h ^ (h >> 15)) + a0.y * 0x85EBCA77u;
