@@ -199,6 +199,84 @@ MZK_API int32_t mzk_fr_decode_dev(int32_t curve_id, const void* d_image, uint64_
                                   uint32_t* out_bad_segment, uint64_t* out_bad_index, void* stream);
 MZK_API int32_t mzk_fr_encode_dev(int32_t curve_id, const void* d_in, uint64_t count, void* d_out, void* stream);
 
+/* ---- host pairing (csrc/hostpairing.hpp): G2 and the optimal ate pairing of both curves, for the verifier's final
+ * check multi_pairing([A, -B], [beta_h, h]) == 1 (plonk/src/proof_system/verifier.rs:226-250) and for the G2 half of an OpenKey.
+ * Every entry point of this block is host-only like mzk_key_layout: no GPU, no mzk_init, nothing kept between calls.
+ *
+ * G2 records (ark-serialize 0.4; Fq2 = c0 + c1 u; "y is the larger" = y > -y with c1 compared first, then c0, on canonical integers):
+ *   BLS12-381  compressed    96 B  x.c1 || x.c0, each 48 B big-endian; byte 0: 0x80 compressed (must be set), 0x40 infinity, 0x20 y is the larger
+ *              uncompressed 192 B  x.c1 || x.c0 || y.c1 || y.c0; byte 0: 0x80 and 0x20 must be clear, 0x40 infinity
+ *   BN254      compressed    64 B  x.c0 || x.c1, each 32 B little-endian; last byte: 0x80 y is the larger, 0x40 infinity, both = invalid
+ *              uncompressed 128 B  x.c0 || x.c1 || y.c0 || y.c1; the same flags in the last byte (written; 0x80 ignored on read)
+ * mzk_g2_decode: one record (flags: MZK_SER_COMPRESSED states its mode) -> out_xy_mont = x.c0, x.c1, y.c0, y.c1, Montgomery Fq (4 x 6 resp.
+ * 4 x 4 limbs).  The checks of mzk_srs_register_serialized in its order -- flag bits, infinity (always refused: an OpenKey has none), every
+ * coordinate below q, x^3 + b' a square in Fq2 (compressed) or, with MZK_SER_VALIDATE, on the twist (uncompressed) -- and with
+ * MZK_SER_VALIDATE [r]Q = O on BOTH curves (BN254's twist has a cofactor too).  MZK_ERR_ENCODING: mzk_last_error() = "G2: <reason>", the
+ * reasons those of the G1 decoder.
+ * mzk_g2_mul: [k]Q as a record of the same mode, k a canonical integer of 4 limbs (any value below 2^256), Q = q_bytes decoded as above
+ * or, NULL, the standard generator; [k]Q = O is written as the infinity record.  beta_h = [beta]h of a testing OpenKey (srs.rs:118-153).
+ * mzk_pairing_product_is_one: *out = 1 when prod_{i<n} e(P_i, Q_i) = 1, else 0: n Miller loops, ONE final exponentiation.  g1_xy_mont: n x
+ * (x, y) Montgomery Fq, the boundary form of every G1 point of this ABI, (0, 0) = infinity (contributes 1); g2_xy_mont: n x the output of
+ * mzk_g2_decode.  n = 0: 1.  The points are taken as members of G1 and G2 (what mzk_g2_decode checks under MZK_SER_VALIDATE); nothing is
+ * checked here.
+ * mzk_pairing_gt: e(P, Q) as 12 canonical Fq integers (12 x 6 resp. 12 x 4 limbs), the coefficients of 1, w, .., w^11 in
+ * Fq[w] / (w^12 - 2 xi0 w^6 + xi0^2 + 1), xi0 = 1 (BLS12-381) / 9 (BN254): the tower's w with u = w^6 - xi0, the representation of
+ * oracle/pyref_pairing.ExtField.  The value is f_{ate,Q}(P)^((q^12 - 1) / r) with the Miller value conjugated for BLS12-381's negative x, as
+ * ark-ec does: on BN254 it EQUALS pyref_pairing's PairingCurve.pairing(Q, P), on BLS12-381 it is that value's INVERSE (pyref_pairing ignores
+ * the sign of x).  Products compared with 1 do not see the difference.
+ * mzk_batch_verify_challenge: r of batch_verify_opening_proofs (verifier.rs:203-215) from the K challenges u of the proofs (Montgomery Fr,
+ * caller's order): 1 for K = 1; else a Merlin transcript "batch verify", K appends of u under "u" (32 B little-endian), 64 challenge
+ * bytes under "r" reduced mod r (csrc/merlin.cuh, the transcript code of the device compiled for the host).  K = 0: MZK_ERR_INVALID_ARG. */
+MZK_API int32_t mzk_g2_decode(int32_t curve_id, const uint8_t* bytes, uint32_t flags, uint64_t* out_xy_mont);
+MZK_API int32_t mzk_g2_mul(int32_t curve_id, const uint8_t* q_bytes, const uint64_t* k_canonical, uint32_t flags, uint8_t* out_bytes);
+MZK_API int32_t mzk_pairing_product_is_one(int32_t curve_id, const uint64_t* g1_xy_mont, const uint64_t* g2_xy_mont, uint64_t n, int32_t* out);
+MZK_API int32_t mzk_pairing_gt(int32_t curve_id, const uint64_t* g1_xy_mont, const uint64_t* g2_xy_mont, uint64_t* out);
+MZK_API int32_t mzk_batch_verify_challenge(int32_t curve_id, const uint64_t* u_mont, uint64_t K, uint64_t* out_r_mont);
+
+/* ---- verifier: PlonkKzgSnark::batch_verify / verify (snark.rs:141-190, 653-671; verifier.rs:68-251) for single-instance `Proof`s of
+ * TurboPlonk and UltraPlonk (csrc/verifier.cuh).  K >= 1 proofs under ONE verifying key go through the device in one
+ * pass -- per proof 13 | 18 G1 decodings, one Merlin transcript, the linearisation scalars -- and end in two MSMs; groups under different
+ * keys with the same open key are summed before ONE check of two pairings (host).  verify is K = 1 with r = 1.  Needs mzk_init.
+ *
+ * mzk_verifier_create: a bare VerifyingKey image (mzk_key_layout with MZK_KEY_VK_ONLY; flags: MZK_SER_COMPRESSED states the mode of the key
+ * AND of every proof verified under it, MZK_SER_VALIDATE adds the subgroup checks to the key's points).  is_merged: MZK_ERR_UNSUPPORTED.
+ * Kept on the device: the decoded commitments (selectors, sigmas, Ultra: the 4 Plookup commitments, open_key.g), k, and the byte script of
+ * append_vk_and_pub_input (transcript/mod.rs:45-104); h and beta_h are decoded on the host.  A key commitment at infinity is normal (an
+ * unused selector commits to nothing): it is flagged, not refused.  MZK_ERR_ENCODING: "vk.<field>: <reason>".
+ * mzk_verifier_shape: points per proof (13 | 18), bases of the key (nsel + W + 4 (Ultra) + 1), the length of a proof image under this key
+ * and mode, num_inputs (each nullable).
+ *
+ * A batch runs in two phases, because r depends on every proof's u.
+ * mzk_verifier_batch_begin: K images of proof_len bytes each, back to back; public_inputs_canonical: K x num_inputs canonical integers of 4
+ * limbs; extra_ranges (nullable: no proof has an extra transcript message): K pairs (begin, end) of byte offsets into extra_msgs, begin =
+ * UINT64_MAX for a proof without one; challenges_mont (nullable): K x 7 Montgomery Fr (tau, beta, gamma, alpha, zeta, v, u) that REPLACE
+ * the Merlin transcript -- for callers with another transcript (Solidity, Rescue); flags: MZK_SER_VALIDATE (subgroup checks of the proofs'
+ * points).  On the host: proof_len, the Vec counts and the Option tag against the key's type.  On the device: A decode, B Fiat-Shamir, C
+ * scalars (one per base: repeated bases are summed).  *out_u_mont (nullable): the K challenges u, for mzk_batch_verify_challenge.
+ * Any malformed proof: MZK_ERR_ENCODING, *out_bad_index (nullable) the LOWEST bad proof -- one 64-bit atomicMin, the same answer on every
+ * run -- and mzk_last_error() "proof <i>: <field>: <reason>": a bad length, count or tag, a point (reasons of mzk_srs_register_serialized;
+ * infinity is flagged, not refused), an evaluation or public input "not below the modulus".  No batch is left open then.
+ * mzk_verifier_batch_challenges: K x 7 Montgomery Fr.  mzk_verifier_batch_scalars (each nullable): K x NKEY scalars for the key's bases
+ * (selectors, sigmas, Ultra: range, key, table_dom_sep, q_dom_sep; open_key.g last and zero: its scalar is the finish's), K x NP for the proof's
+ * own points in image order (wires, prod_perm, split_quot, opening = zeta, shifted_opening = u zeta w, Ultra: h_1, h_2, prod_lookup), K
+ * aggregated evaluations; Montgomery Fr, unweighted.
+ * mzk_verifier_batch_finish: weights proof i by r_weights_mont[i] (r^i of mzk_batch_verify_challenge, in the caller's order across groups),
+ * column-sums the key rows and the evaluations by a fixed tree (no atomics on field elements), zeroes the scalar of every flagged base and runs
+ * the two MSMs of verifier.rs:217-247 through the variable-base path: A = sum r^i (W_i + u_i W'_i), B over the key's bases, the K x NP proof
+ * points and -(sum r^i eval_i) g; Jacobian (x, y, z) Montgomery Fq.  The batch handle is consumed, also on failure; with all three pointers
+ * NULL the batch is only discarded.
+ * mzk_verifier_check: sums n_groups results (same open key), normalises, *out_accept = [ e(A, beta_h) e(-B, h) == 1 ]. */
+MZK_API int32_t mzk_verifier_create(int32_t curve_id, const uint8_t* vk_bytes, uint64_t len, uint32_t flags, uint64_t* out_handle);
+MZK_API int32_t mzk_verifier_destroy(uint64_t verifier);
+MZK_API int32_t mzk_verifier_shape(uint64_t verifier, uint32_t* out_n_proof_points, uint32_t* out_n_key_bases, uint64_t* out_proof_len, uint64_t* out_num_inputs);
+MZK_API int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* public_inputs_canonical,
+                                         const uint8_t* extra_msgs, const uint64_t* extra_ranges, const uint64_t* challenges_mont, uint32_t flags,
+                                         uint64_t* out_batch, uint64_t* out_u_mont, uint64_t* out_bad_index);
+MZK_API int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out);
+MZK_API int32_t mzk_verifier_batch_scalars(uint64_t batch, uint64_t* out_key_rows, uint64_t* out_proof_rows, uint64_t* out_evals);
+MZK_API int32_t mzk_verifier_batch_finish(uint64_t batch, const uint64_t* r_weights_mont, uint64_t* out_A_xyz, uint64_t* out_B_xyz);
+MZK_API int32_t mzk_verifier_check(uint64_t verifier, const uint64_t* A_xyz, const uint64_t* B_xyz, uint64_t n_groups, int32_t* out_accept);
+
 /* ---- MSM: replaces <E::G1 as VariableBaseMSM>::msm_bigint(bases, bigints)
  *      at univariate_kzg/mod.rs:109-111 (commit) and :151-155 (open).
  * Computes sum_{i<n} scalars[i] * srs[base_offset + i]; base_offset = num_leading_zeros of

@@ -148,7 +148,10 @@ MZK_HD bool g1_in_subgroup_endo(const AffineX<X>& p) {
 }
 
 // One record -> the boundary form (x*R, y*R: X::N words each) in out[0 .. 2 X::N).  Returns -1, or the first SrsBad that applies.
-template <class X, bool COMPRESSED, bool VALIDATE>
+// ALLOW_INF (the commitments of a proof or of a verifying key, where infinity is a normal value: verifier.cuh): a point at infinity is
+// not refused but FLAGGED -- SRS_INFINITY_FLAGGED is returned and out is left untouched; the SRS path keeps refusing it.
+constexpr int SRS_INFINITY_FLAGGED = -2;
+template <class X, bool COMPRESSED, bool VALIDATE, bool ALLOW_INF = false>
 MZK_HD int srs_decode_point(const uint8_t* rec, uint32_t* out) {
     constexpr int B = SerFmt<X>::BYTES;
     constexpr bool BLS = SerFmt<X>::BE;
@@ -170,7 +173,7 @@ MZK_HD int srs_decode_point(const uint8_t* rec, uint32_t* out) {
         if (COMPRESSED) xw[X::N - 1] &= 0x3FFFFFFFu;
         else yw[X::N - 1] &= 0x3FFFFFFFu;
     }
-    if (inf) return SRS_BAD_INFINITY;                             // (its coordinates are not read: nothing else applies)
+    if (inf) return ALLOW_INF ? SRS_INFINITY_FLAGGED : (int)SRS_BAD_INFINITY;   // (its coordinates are not read: nothing else applies)
     if (!ser_below_modulus<X>(xw)) return SRS_BAD_RANGE;
     if (!COMPRESSED && !ser_below_modulus<X>(yw)) return SRS_BAD_RANGE;
     const Fx<X> r2 = Fx<X>::from_const(X::XR2);
@@ -193,7 +196,7 @@ MZK_HD int srs_decode_point(const uint8_t* rec, uint32_t* out) {
         uint32_t z = 0;
 #pragma unroll
         for (int j = 0; j < X::N; j++) z |= xw[j] | yw[j];
-        if (z == 0) return SRS_BAD_INFINITY;
+        if (z == 0) return ALLOW_INF ? SRS_INFINITY_FLAGGED : (int)SRS_BAD_INFINITY;
     }
     const Fp<X> bx = fx_to_boundary<X>(p.x), by = fx_to_boundary<X>(p.y);
 #pragma unroll

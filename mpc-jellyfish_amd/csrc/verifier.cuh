@@ -1,0 +1,383 @@
+// verifier.cuh -- the per-proof work of PlonkKzgSnark::batch_verify on the device: K single-instance proofs under
+// ONE verifying key, staged as K images of proof_len bytes.
+//   A  vfy_decode_kernel      one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array
+//   B  vfy_transcript_kernel  one thread per proof: the Merlin transcript of compute_challenges (verifier.rs:274-319) -> 7 challenges
+//   C  vfy_scalars_kernel     one thread per proof: prepare_pcs_info for one instance (verifier.rs:122-184, 340-733) -> one scalar per base
+//   finish                    vfy_weight_kernel / vfy_colsum_kernel: rows weighted by r^i, the key's columns summed by a fixed tree
+// Base array (boundary form, what mzk_srs_register_dev takes): [ key bases | proof 0's points | proof 1's points | .. ]
+//   key bases    selectors (13 | 14), sigmas (W), Ultra: range, key, table_dom_sep, q_dom_sep; open_key.g last        (NKEY = nsel + W + 4 ultra + 1)
+//   proof points wires (W), prod_perm, split_quot (W), opening, shifted_opening, Ultra: h_1, h_2, prod_lookup       (NP = 13 | 18: image order)
+// A base at infinity holds the curve's generator and is FLAGGED; the finish zeroes its scalar.
+// Errors: one 64-bit atomicMin over (proof << 32 | field << 8 | reason): the lowest proof, then its first field, on every run.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "fp.cuh"
+#include "fp_inv.cuh"
+#include "key_io.cuh"                                              // fr_read_record
+#include "merlin.cuh"
+#include "srs_io.cuh"
+
+namespace mzk {
+
+#define VFY_LBL(s) s, (uint32_t)(sizeof(s) - 1)                  // a transcript label and its length
+constexpr int VFY_THREADS = 64;                                  // one wave; stage B keeps 25 lanes x 64 transcripts = 12.5 KB of LDS
+constexpr int VFY_MAX_POINTS = 25;                               // records of one image that stage A decodes (a key: 25, a proof: 18)
+constexpr uint32_t VFY_REASON_NOT_BELOW_R = 6;                   // after SrsBad's six
+constexpr uint32_t VFY_FIELD_EVAL = 32, VFY_FIELD_PUB_INPUT = 64;  // fields: 0..24 point j, 32 + e evaluation e, 64 + i public input i
+
+struct VfyPoints {                                               // the G1 records of one image
+    uint32_t n, stride;                                          // records per image; bytes from one image to the next
+    uint32_t off[VFY_MAX_POINTS];                                // byte offset in the image
+    int32_t open_idx;                                            // >= 0: records open_idx, open_idx + 1 also go to a_bases (the MSM A)
+};
+struct VfyShape {                                                // one key's proofs
+    uint32_t W, nsel, ultra, np, nkey, log_n, num_inputs, compressed, g1_bytes, proof_len;
+    uint32_t pt_off[18];
+    uint32_t wires_evals_off, sigma_evals_off, perm_next_off, plookup_evals_off;
+    unsigned long long n;
+};
+
+MZK_D void vfy_report(unsigned long long* err, unsigned long long proof, uint32_t field, uint32_t reason) {
+    atomicMin(err, (proof << 32) | ((unsigned long long)field << 8) | reason);
+}
+
+// ---- A -------------------------------------------------------------------------------------------------------------------------------
+template <class X, bool COMPRESSED, bool VALIDATE>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_decode_kernel(const uint8_t* __restrict__ images, unsigned long long n_images, VfyPoints pts,
+                                                                 uint32_t* __restrict__ bases, uint32_t* __restrict__ inf_flags, uint32_t* __restrict__ a_bases,
+                                                                 uint32_t* __restrict__ a_inf, unsigned long long* __restrict__ err) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_images * pts.n) return;
+    const unsigned long long i = t / pts.n;
+    const uint32_t j = (uint32_t)(t % pts.n);
+    uint32_t xy[2 * X::N];
+    const int rc = srs_decode_point<X, COMPRESSED, VALIDATE, true>(images + i * pts.stride + pts.off[j], xy);
+    if (rc >= 0) vfy_report(err, i, j, (uint32_t)rc);
+    const bool inf = rc != -1;                                    // (a refused record gets the generator too: the batch is refused anyway)
+    if (inf) {
+#pragma unroll
+        for (int k = 0; k < X::N; k++) { xy[k] = X::GEN_X[k]; xy[X::N + k] = X::GEN_Y[k]; }
+    }
+    uint32_t* out = bases + t * 2 * X::N;
+#pragma unroll
+    for (int k = 0; k < 2 * X::N; k++) out[k] = xy[k];
+    inf_flags[t] = inf;
+    if (pts.open_idx >= 0 && (j == (uint32_t)pts.open_idx || j == (uint32_t)pts.open_idx + 1)) {
+        const unsigned long long a = 2 * i + (j - (uint32_t)pts.open_idx);
+#pragma unroll
+        for (int k = 0; k < 2 * X::N; k++) a_bases[a * 2 * X::N + k] = xy[k];
+        a_inf[a] = inf;
+    }
+}
+
+// ---- B -------------------------------------------------------------------------------------------------------------------------------
+// 64 challenge bytes (little-endian) mod r, Montgomery: lo + 2^256 hi, each half brought below r by subtraction (2^256 < 6 r)
+template <class P>
+MZK_D Fp<P> vfy_reduce_challenge(const uint8_t* ch) {
+    Fp<P> lo = Fp<P>::zero(), hi = Fp<P>::zero();
+#pragma unroll
+    for (int s = 0; s < 32; s++) { lo.l[s >> 2] |= (uint32_t)ch[s] << (8 * (s & 3)); hi.l[s >> 2] |= (uint32_t)ch[32 + s] << (8 * (s & 3)); }
+    while (!ser_below_modulus<P>(lo.l)) sub_limbs<P::N>(lo.l, lo.l, P::MOD);
+    while (!ser_below_modulus<P>(hi.l)) sub_limbs<P::N>(hi.l, hi.l, P::MOD);
+    return to_mont(lo) + to_mont(to_mont(hi));
+}
+MZK_D void vfy_absorb_global(merlin::Transcript& t, const uint8_t* __restrict__ p, uint32_t n) {
+    for (uint32_t i = 0; i < n; i++) t.absorb_byte(p[i]);
+}
+MZK_D void vfy_absorb_words(merlin::Transcript& t, const uint32_t (&w)[8]) {      // 32 bytes, little-endian (an Fr record)
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        for (int b = 0; b < 32; b += 8) t.absorb_byte(w[k] >> b);
+}
+// a G1 record of the image enters the transcript in its COMPRESSED form: as it stands, or rebuilt from an uncompressed record (x's bytes,
+// the infinity flag, and "y is the larger" = y > (q - 1) / 2)
+template <class X>
+MZK_D void vfy_append_g1(merlin::Transcript& t, const char* label, uint32_t label_len, const uint8_t* __restrict__ rec, bool compressed) {
+    constexpr int B = SerFmt<X>::BYTES;
+    constexpr bool BLS = SerFmt<X>::BE;
+    t.append_begin(label, label_len, B);
+    if (compressed) { vfy_absorb_global(t, rec, B); return; }
+    uint32_t yw[X::N];
+    ser_read<X>(rec + B, yw);
+    const uint32_t f = BLS ? rec[0] : rec[2 * B - 1];
+    const bool inf = f & 0x40u;
+    yw[X::N - 1] &= BLS ? 0x1FFFFFFFu : 0x3FFFFFFFu;
+    bool larger = false, decided = false;
+#pragma unroll
+    for (int k = X::N - 1; k >= 0; k--) {                        // y > q >> 1
+        const uint32_t h = (X::MOD[k] >> 1) | (k + 1 < X::N ? X::MOD[k + 1] << 31 : 0u);
+        if (!decided && yw[k] != h) { larger = yw[k] > h; decided = true; }
+    }
+    larger = larger && !inf;
+    for (int s = 0; s < B; s++) {
+        uint32_t b = rec[s];
+        if (BLS && s == 0) b = (b & 0x1Fu) | 0x80u | (inf ? 0x40u : 0u) | (larger ? 0x20u : 0u);
+        if (!BLS && s == B - 1) b = (b & 0x3Fu) | (inf ? 0x40u : 0u) | (larger ? 0x80u : 0u);
+        t.absorb_byte(b);
+    }
+}
+template <class P>
+MZK_D Fp<P> vfy_challenge(merlin::Transcript& t, const char* label, uint32_t label_len) {
+    uint8_t ch[64];
+    t.challenge_bytes(label, label_len, ch, 64);
+    const Fp<P> c = vfy_reduce_challenge<P>(ch);
+    const Fp<P> v = from_mont(c);
+    t.append_begin(label, label_len, 32);
+    vfy_absorb_words(t, v.l);
+    return c;
+}
+
+// script: the appends of append_vk_and_pub_input up to the public inputs, as items { label_len u8, msg_len u8, label, msg }, n_items of them
+template <class P, class X>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_transcript_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyShape sh,
+                                                                     const uint8_t* __restrict__ script, uint32_t n_items,
+                                                                     const uint32_t* __restrict__ pub_inputs /* K x num_inputs canonical */,
+                                                                     const uint8_t* __restrict__ extra, const unsigned long long* __restrict__ extra_range,
+                                                                     uint32_t* __restrict__ challenges, unsigned long long* __restrict__ err) {
+    __shared__ uint64_t lanes[25 * VFY_THREADS];
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const uint8_t* img = images + i * sh.proof_len;
+    const uint32_t G = sh.g1_bytes;
+    const bool cmp = sh.compressed;
+    merlin::Transcript t;
+    t.init(lanes + threadIdx.x, VFY_THREADS, VFY_LBL("PlonkProof"));
+    if (extra_range && extra_range[2 * i] != ~0ull) {
+        const unsigned long long b = extra_range[2 * i], e = extra_range[2 * i + 1];
+        t.append_begin(VFY_LBL("extra info"), (uint32_t)(e - b));
+        vfy_absorb_global(t, extra + b, (uint32_t)(e - b));
+    }
+    const uint8_t* s = script;
+    for (uint32_t k = 0; k < n_items; k++) {
+        const uint32_t ll = s[0], ml = s[1];
+        t.begin_op(merlin::F_M | merlin::F_A);
+        vfy_absorb_global(t, s + 2, ll);
+        t.absorb_u32le(ml);
+        t.begin_op(merlin::F_A);
+        vfy_absorb_global(t, s + 2 + ll, ml);
+        s += 2 + ll + ml;
+    }
+    for (uint32_t k = 0; k < sh.num_inputs; k++) {
+        const uint32_t* w = pub_inputs + (i * sh.num_inputs + k) * 8ull;
+        uint32_t v[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = w[j];
+        if (!ser_below_modulus<P>(v)) vfy_report(err, i, VFY_FIELD_PUB_INPUT + k, VFY_REASON_NOT_BELOW_R);
+        t.append_begin(VFY_LBL("public input"), 32);
+        vfy_absorb_words(t, v);
+    }
+    const uint32_t W = sh.W;
+    Fp<P> ch[7];
+    for (uint32_t k = 0; k < W; k++) vfy_append_g1<X>(t, VFY_LBL("witness_poly_comms"), img + sh.pt_off[k], cmp);
+    ch[0] = vfy_challenge<P>(t, VFY_LBL("tau"));
+    if (sh.ultra)
+        for (uint32_t k = 0; k < 2; k++) vfy_append_g1<X>(t, VFY_LBL("h_poly_comms"), img + sh.pt_off[2 * W + 3 + k], cmp);
+    ch[1] = vfy_challenge<P>(t, VFY_LBL("beta"));
+    ch[2] = vfy_challenge<P>(t, VFY_LBL("gamma"));
+    vfy_append_g1<X>(t, VFY_LBL("perm_poly_comms"), img + sh.pt_off[W], cmp);
+    if (sh.ultra) vfy_append_g1<X>(t, VFY_LBL("plookup_poly_comms"), img + sh.pt_off[2 * W + 5], cmp);
+    ch[3] = vfy_challenge<P>(t, VFY_LBL("alpha"));
+    for (uint32_t k = 0; k < W; k++) vfy_append_g1<X>(t, VFY_LBL("quot_poly_comms"), img + sh.pt_off[W + 1 + k], cmp);
+    ch[4] = vfy_challenge<P>(t, VFY_LBL("zeta"));
+    for (uint32_t k = 0; k < W; k++) { t.append_begin(VFY_LBL("wire_evals"), 32); vfy_absorb_global(t, img + sh.wires_evals_off + 32 * k, 32); }
+    for (uint32_t k = 0; k + 1 < W; k++) { t.append_begin(VFY_LBL("wire_sigma_evals"), 32); vfy_absorb_global(t, img + sh.sigma_evals_off + 32 * k, 32); }
+    t.append_begin(VFY_LBL("perm_next_eval"), 32);
+    vfy_absorb_global(t, img + sh.perm_next_off, 32);
+    if (sh.ultra) {                                               // transcript/mod.rs:165-202: six of the fifteen, under these labels
+        const uint8_t* pe = img + sh.plookup_evals_off;
+        t.append_begin(VFY_LBL("lookup_table_eval"), 32);      vfy_absorb_global(t, pe + 32 * 0, 32);
+        t.append_begin(VFY_LBL("h_1_eval"), 32);                vfy_absorb_global(t, pe + 32 * 4, 32);
+        t.append_begin(VFY_LBL("prod_next_eval"), 32);         vfy_absorb_global(t, pe + 32 * 6, 32);
+        t.append_begin(VFY_LBL("lookup_table_next_eval"), 32); vfy_absorb_global(t, pe + 32 * 7, 32);
+        t.append_begin(VFY_LBL("h_1_next_eval"), 32);          vfy_absorb_global(t, pe + 32 * 10, 32);
+        t.append_begin(VFY_LBL("h_2_next_eval"), 32);          vfy_absorb_global(t, pe + 32 * 11, 32);
+    }
+    ch[5] = vfy_challenge<P>(t, VFY_LBL("v"));
+    vfy_append_g1<X>(t, VFY_LBL("open_proof"), img + sh.pt_off[2 * W + 1], cmp);
+    vfy_append_g1<X>(t, VFY_LBL("shifted_open_proof"), img + sh.pt_off[2 * W + 2], cmp);
+    ch[6] = vfy_challenge<P>(t, VFY_LBL("u"));
+#pragma unroll
+    for (int k = 0; k < 7; k++) store_fp<P>(challenges + (i * 7 + k) * 8ull, ch[k]);
+}
+
+// ---- C -------------------------------------------------------------------------------------------------------------------------------
+template <class P>
+MZK_D Fp<P> vfy_read_eval(const uint8_t* __restrict__ p, unsigned long long* err, unsigned long long proof, uint32_t index) {
+    Fp<P> a;
+    fr_read_record(p, a.l);
+    if (!ser_below_modulus<P>(a.l)) vfy_report(err, proof, VFY_FIELD_EVAL + index, VFY_REASON_NOT_BELOW_R);
+    return to_mont(a);
+}
+
+// key_rows: K x nkey; proof_rows: K x np (the tail of the MSM's scalar array); evals: K.  k_mont: the key's W separators.
+template <class P>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_scalars_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyShape sh,
+                                                                  const uint32_t* __restrict__ k_mont, const uint32_t* __restrict__ pub_inputs,
+                                                                  const uint32_t* __restrict__ challenges, uint32_t* __restrict__ key_rows,
+                                                                  uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ evals, unsigned long long* __restrict__ err) {
+    using F = Fp<P>;
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const uint8_t* img = images + i * sh.proof_len;
+    const uint32_t W = sh.W;
+    const bool ultra = sh.ultra;
+    const F tau = load_fp<P>(challenges + (i * 7 + 0) * 8ull), beta = load_fp<P>(challenges + (i * 7 + 1) * 8ull),
+            gamma = load_fp<P>(challenges + (i * 7 + 2) * 8ull), alpha = load_fp<P>(challenges + (i * 7 + 3) * 8ull),
+            zeta = load_fp<P>(challenges + (i * 7 + 4) * 8ull), v = load_fp<P>(challenges + (i * 7 + 5) * 8ull),
+            u = load_fp<P>(challenges + (i * 7 + 6) * 8ull);
+    F we[6], se[5], pe[15];
+    for (uint32_t k = 0; k < W; k++) we[k] = vfy_read_eval<P>(img + sh.wires_evals_off + 32 * k, err, i, k);
+    for (uint32_t k = 0; k + 1 < W; k++) se[k] = vfy_read_eval<P>(img + sh.sigma_evals_off + 32 * k, err, i, W + k);
+    const F zn = vfy_read_eval<P>(img + sh.perm_next_off, err, i, 2 * W - 1);
+    if (ultra)
+        for (uint32_t k = 0; k < 15; k++) pe[k] = vfy_read_eval<P>(img + sh.plookup_evals_off + 32 * k, err, i, 2 * W + k);
+    // structs.rs:496-541
+    const F &rng_e = pe[0], &key_e = pe[1], &dom_e = pe[2], &qdom_e = pe[3], &h1_e = pe[4], &ql_e = pe[5], &prodn_e = pe[6], &rngn_e = pe[7], &keyn_e = pe[8],
+            &domn_e = pe[9], &h1n_e = pe[10], &h2n_e = pe[11], &qln_e = pe[12], &w3n_e = pe[13], &w4n_e = pe[14];
+
+    // the domain: w, 1 / w, zeta^n, the vanishing and the two Lagrange evaluations (verifier.rs:776-788)
+    F w = F::from_const(P::ROOT);
+    for (int k = (int)sh.log_n; k < P::TWO_ADICITY; k++) w = sqr(w);
+    const F w_inv = inv_safegcd<P>(w), one = F::one(), n_f = from_u64<P>(sh.n);
+    F zeta_n = zeta;
+    for (uint32_t k = 0; k < sh.log_n; k++) zeta_n = sqr(zeta_n);
+    const F vanish = zeta_n - one;
+    const F l1 = vanish * inv_safegcd<P>(n_f * (zeta - one));
+    const F ln = vanish * w_inv * inv_safegcd<P>(n_f * (zeta - w_inv));
+    // PI(zeta) over num_inputs (verifier.rs:845-880, unmerged)
+    F pi = F::zero();
+    if (!vanish.is_zero()) {
+        const F vn = vanish * inv_safegcd<P>(n_f);
+        F g = one;
+        for (uint32_t k = 0; k < sh.num_inputs; k++) {
+            F val = load_fp<P>(pub_inputs + (i * sh.num_inputs + k) * 8ull);
+            if (!ser_below_modulus<P>(val.l)) vfy_report(err, i, VFY_FIELD_PUB_INPUT + k, VFY_REASON_NOT_BELOW_R);
+            val = to_mont(val);
+            pi = pi + vn * g * inv_safegcd<P>(zeta - g) * val;
+            g = g * w;
+        }
+    }
+    const F a2 = sqr(alpha), a3 = a2 * alpha, a4 = sqr(a2), a5 = a4 * alpha, a6 = a4 * a2;
+    const F b1 = one + beta, g_b1 = gamma * b1;
+    // the constant term of the linearisation polynomial (:340-414)
+    F lin = pi - a2 * l1;
+    F acc = alpha * zn * (gamma + we[W - 1]);
+    for (uint32_t k = 0; k + 1 < W; k++) acc = acc * (gamma + we[k] + beta * se[k]);
+    lin = lin - acc;
+    if (ultra) {
+        const F pc = ln * (h1_e - h2n_e - a2) - alpha * l1 - a3 * (zeta - w_inv) * prodn_e * (g_b1 + h1_e + beta * h1n_e) * (g_b1 + beta * h2n_e);
+        lin = lin + a3 * pc;
+    }
+    // scalars: one per base
+    F key[VFY_MAX_POINTS], own[18];
+    for (uint32_t k = 0; k < sh.nkey; k++) key[k] = F::zero();
+    for (uint32_t k = 0; k < sh.np; k++) own[k] = F::zero();
+    const uint32_t SIG = sh.nsel, PLK = sh.nsel + W;                                   // key columns
+    const uint32_t PROD = W, QUOT = W + 1, OPEN = 2 * W + 1, SHIFT = 2 * W + 2, H = 2 * W + 3, PLOOK = 2 * W + 5;   // proof columns
+    // [D]_1 (:513-652)
+    F coeff = alpha;
+    for (uint32_t k = 0; k < W; k++) coeff = coeff * (beta * load_fp<P>(k_mont + 8 * k) * zeta + gamma + we[k]);
+    own[PROD] = coeff + a2 * l1;
+    coeff = alpha * beta * zn;
+    for (uint32_t k = 0; k + 1 < W; k++) coeff = coeff * (beta * se[k] + gamma + we[k]);
+    key[SIG + W - 1] = neg(coeff);
+    {
+        const F w01 = we[0] * we[1], w23 = we[2] * we[3];
+        const auto p5 = [](const F& a) { const F s = sqr(a); return sqr(s) * a; };
+        key[0] = we[0]; key[1] = we[1]; key[2] = we[2]; key[3] = we[3]; key[4] = w01; key[5] = w23;
+        key[6] = p5(we[0]); key[7] = p5(we[1]); key[8] = p5(we[2]); key[9] = p5(we[3]);
+        key[10] = neg(we[4]); key[11] = one; key[12] = w01 * w23 * we[4];
+    }
+    if (ultra) {
+        const F merged_lookup_x = we[5] + ql_e * tau * (qdom_e + tau * (we[0] + tau * (we[1] + tau * we[2])));
+        const F table_x = rng_e + ql_e * tau * (dom_e + tau * (key_e + tau * (we[3] + tau * we[4])));
+        const F table_xw = rngn_e + qln_e * tau * (domn_e + tau * (keyn_e + tau * (w3n_e + tau * w4n_e)));
+        own[PLOOK] = a4 * l1 + a5 * ln + a6 * (zeta - w_inv) * b1 * (gamma + merged_lookup_x) * (g_b1 + table_x + beta * table_xw);
+        own[H + 1] = a6 * (w_inv - zeta) * prodn_e * (g_b1 + h1_e + beta * h1n_e);
+    }
+    // the split quotient (:654-665)
+    {
+        const F zeta_n2 = zeta_n * sqr(zeta);
+        F c = neg(vanish);
+        for (uint32_t k = 0; k < W; k++) { own[QUOT + k] = c; c = c * zeta_n2; }
+    }
+    // powers of v at zeta and of u v at zeta w, with the matching evaluations (:453-506, :673-733)
+    F eval = neg(lin), vb = v, uvb = u;
+    const auto at_zeta = [&](F& slot, const F& e) { slot = slot + vb; eval = eval + e * vb; vb = vb * v; };
+    const auto at_zeta_omega = [&](F& slot, const F& e) { slot = slot + uvb; eval = eval + e * uvb; uvb = uvb * v; };
+    for (uint32_t k = 0; k < W; k++) at_zeta(own[k], we[k]);
+    for (uint32_t k = 0; k + 1 < W; k++) at_zeta(key[SIG + k], se[k]);
+    at_zeta_omega(own[PROD], zn);
+    if (ultra) {
+        at_zeta(key[PLK + 0], rng_e); at_zeta(key[PLK + 1], key_e); at_zeta(own[H], h1_e); at_zeta(key[13], ql_e);
+        at_zeta(key[PLK + 2], dom_e); at_zeta(key[PLK + 3], qdom_e);
+        at_zeta_omega(own[PLOOK], prodn_e); at_zeta_omega(key[PLK + 0], rngn_e); at_zeta_omega(key[PLK + 1], keyn_e);
+        at_zeta_omega(own[H], h1n_e); at_zeta_omega(own[H + 1], h2n_e); at_zeta_omega(key[13], qln_e);
+        at_zeta_omega(own[3], w3n_e); at_zeta_omega(own[4], w4n_e); at_zeta_omega(key[PLK + 2], domn_e);
+    }
+    // the opening proofs' scalars in B (verifier.rs:236-240); open_key.g gets -sum r^i eval_i in the finish
+    own[OPEN] = zeta;
+    own[SHIFT] = u * zeta * w;
+    for (uint32_t k = 0; k < sh.nkey; k++) store_fp<P>(key_rows + (i * sh.nkey + k) * 8ull, key[k]);
+    for (uint32_t k = 0; k < sh.np; k++) store_fp<P>(proof_rows + (i * sh.np + k) * 8ull, own[k]);
+    store_fp<P>(evals + i * 8ull, eval);
+}
+
+// ---- finish --------------------------------------------------------------------------------------------------------------------------
+// proof rows *= r_i (0 at a flagged base); A's scalars (r_i, r_i u_i)
+template <class P>
+__global__ __launch_bounds__(256) void vfy_weight_kernel(unsigned long long K, uint32_t np, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ challenges,
+                                                         const uint32_t* __restrict__ inf_flags /* K x np */, const uint32_t* __restrict__ a_inf,
+                                                         uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ a_scalars) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= K * (np + 2)) return;
+    const unsigned long long i = t / (np + 2);
+    const uint32_t j = (uint32_t)(t % (np + 2));
+    const Fp<P> r = load_fp<P>(weights + i * 8ull);
+    if (j < np) {
+        const Fp<P> s = inf_flags[i * np + j] ? Fp<P>::zero() : r * load_fp<P>(proof_rows + (i * np + j) * 8ull);
+        store_fp<P>(proof_rows + (i * np + j) * 8ull, s);
+    } else {
+        const unsigned long long a = 2 * i + (j - np);
+        Fp<P> s = j == np ? r : r * load_fp<P>(challenges + (i * 7 + 6) * 8ull);
+        if (a_inf[a]) s = Fp<P>::zero();
+        store_fp<P>(a_scalars + a * 8ull, s);
+    }
+}
+// column c < nkey - 1: sum_i r_i key_rows[i][c]; the last column (open_key.g): -sum_i r_i evals[i].  One block per column; thread t adds
+// rows t, t + 256, .. in order and the 256 partial sums meet in a fixed tree: the same sum on every run, no atomics.
+template <class P>
+__global__ __launch_bounds__(256) void vfy_colsum_kernel(unsigned long long K, uint32_t nkey, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ key_rows,
+                                                         const uint32_t* __restrict__ evals, const uint32_t* __restrict__ key_inf, uint32_t* __restrict__ out) {
+    __shared__ uint32_t part[256 * 8];
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    const bool last = c == nkey - 1;
+    Fp<P> acc = Fp<P>::zero();
+    for (unsigned long long i = tid; i < K; i += 256)
+        acc = acc + load_fp<P>(weights + i * 8ull) * (last ? load_fp<P>(evals + i * 8ull) : load_fp<P>(key_rows + (i * nkey + c) * 8ull));
+#pragma unroll
+    for (int k = 0; k < 8; k++) part[tid * 8 + k] = acc.l[k];
+    __syncthreads();
+    for (uint32_t half = 128; half; half >>= 1) {
+        if (tid < half) {
+            Fp<P> a, b;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { a.l[k] = part[tid * 8 + k]; b.l[k] = part[(tid + half) * 8 + k]; }
+            a = a + b;
+#pragma unroll
+            for (int k = 0; k < 8; k++) part[tid * 8 + k] = a.l[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        Fp<P> s;
+#pragma unroll
+        for (int k = 0; k < 8; k++) s.l[k] = part[k];
+        if (last) s = neg(s);
+        if (key_inf[c]) s = Fp<P>::zero();
+        store_fp<P>(out + c * 8ull, s);
+    }
+}
+
+}  // namespace mzk

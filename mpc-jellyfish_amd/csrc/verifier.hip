@@ -1,0 +1,506 @@
+// verifier.hip -- mzk_verifier_*: PlonkKzgSnark::batch_verify for single-instance proofs (snark.rs:141-190, verifier.rs:68-251).  The per-proof
+// work runs on the device (verifier.cuh: decode, Fiat-Shamir, linearisation scalars), the two MSMs through the variable-base path over a base
+// array registered per batch, the two pairings on the host (hostpairing.hpp behind mzk_pairing_product_is_one).
+#include "internal.hpp"
+#include "hostfp.hpp"
+#include "verifier.cuh"
+
+#include <memory>
+
+namespace mzk {
+namespace {
+
+struct DevMem {                                                   // one allocation, freed with its owner
+    void* p = nullptr;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    int32_t alloc(size_t bytes) { return hip_status(hipMalloc(&p, bytes ? bytes : 4), "hipMalloc (verifier)"); }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+struct Verifier {
+    int curve = 0;
+    uint32_t flags = 0;                                           // MZK_SER_COMPRESSED: the mode of the key image and of every proof under it
+    VfyShape sh{};
+    DevMem key_xy, key_inf, k_mont, script;
+    uint32_t n_items = 0;
+    std::vector<uint64_t> h, beta_h;                              // mzk_g2_decode's output
+};
+struct Batch {
+    Verifier* v = nullptr;
+    uint64_t verifier = 0, K = 0;
+    DevMem images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
+};
+
+std::mutex g_vfy_lock;
+std::map<uint64_t, std::unique_ptr<Verifier>> g_verifiers;
+std::map<uint64_t, std::unique_ptr<Batch>> g_batches;
+uint64_t g_next_verifier = 1, g_next_batch = 1;
+
+int32_t bind_device() {                                           // the calling thread's context (MZK_ERR_NOT_INIT without one): binds its HIP device
+    int32_t d;
+    return mzk_get_device(&d);
+}
+uint32_t g1_bytes(int curve, bool compressed) { return (uint32_t)srs_record_bytes(curve, compressed); }
+
+// the layout of a `Proof` image (structs.rs:59-84) under this key's type and mode
+void proof_shape(VfyShape& sh) {
+    const uint32_t W = sh.W, G = sh.g1_bytes;
+    uint32_t o = 8, p = 0;
+    for (uint32_t k = 0; k < W; k++, o += G) sh.pt_off[p++] = o;                  // wires_poly_comms
+    sh.pt_off[p++] = o; o += G;                                                  // prod_perm_poly_comm
+    o += 8;
+    for (uint32_t k = 0; k < W; k++, o += G) sh.pt_off[p++] = o;                  // split_quot_poly_comms
+    sh.pt_off[p++] = o; o += G;                                                  // opening_proof
+    sh.pt_off[p++] = o; o += G;                                                  // shifted_opening_proof
+    sh.wires_evals_off = o + 8; o += 8 + 32 * W;
+    sh.sigma_evals_off = o + 8; o += 8 + 32 * (W - 1);
+    sh.perm_next_off = o; o += 32;
+    o += 1;                                                                      // Option<PlookupProof> tag
+    if (sh.ultra) {
+        o += 8;
+        sh.pt_off[p++] = o; o += G;                                              // h_poly_comms
+        sh.pt_off[p++] = o; o += G;
+        sh.pt_off[p++] = o; o += G;                                              // prod_lookup_poly_comm
+        sh.plookup_evals_off = o; o += 32 * 15;
+    }
+    sh.np = p;
+    sh.proof_len = o;
+}
+const char* proof_point_name(const VfyShape& sh, uint32_t j, std::string& buf) {
+    const uint32_t W = sh.W;
+    if (j < W) buf = "wires_poly_comms[" + std::to_string(j) + "]";
+    else if (j == W) buf = "prod_perm_poly_comm";
+    else if (j < 2 * W + 1) buf = "split_quot_poly_comms[" + std::to_string(j - W - 1) + "]";
+    else if (j == 2 * W + 1) buf = "opening_proof";
+    else if (j == 2 * W + 2) buf = "shifted_opening_proof";
+    else if (j < 2 * W + 5) buf = "plookup_proof.h_poly_comms[" + std::to_string(j - 2 * W - 3) + "]";
+    else buf = "plookup_proof.prod_lookup_poly_comm";
+    return buf.c_str();
+}
+const char* proof_eval_name(const VfyShape& sh, uint32_t e, std::string& buf) {
+    static const char* const PLOOKUP[15] = {"range_table_eval", "key_table_eval", "table_dom_sep_eval", "q_dom_sep_eval", "h_1_eval", "q_lookup_eval",
+                                            "prod_next_eval", "range_table_next_eval", "key_table_next_eval", "table_dom_sep_next_eval", "h_1_next_eval",
+                                            "h_2_next_eval", "q_lookup_next_eval", "w_3_next_eval", "w_4_next_eval"};
+    const uint32_t W = sh.W;
+    if (e < W) buf = "wires_evals[" + std::to_string(e) + "]";
+    else if (e < 2 * W - 1) buf = "wire_sigma_evals[" + std::to_string(e - W) + "]";
+    else if (e == 2 * W - 1) buf = "perm_next_eval";
+    else buf = std::string("plookup_proof.") + PLOOKUP[(e - 2 * W) % 15];
+    return buf.c_str();
+}
+const char* reason_text(uint32_t reason) { return reason == VFY_REASON_NOT_BELOW_R ? "not below the modulus" : srs_bad_reason((int)reason); }
+
+template <class X>
+void launch_decode(bool compressed, bool validate, const uint8_t* images, uint64_t n_images, const VfyPoints& pts, uint32_t* bases, uint32_t* inf, uint32_t* a_bases,
+                   uint32_t* a_inf, unsigned long long* err) {
+    const dim3 grid((unsigned)((n_images * pts.n + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+    if (compressed) {
+        if (validate) hipLaunchKernelGGL((vfy_decode_kernel<X, true, true>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
+        else hipLaunchKernelGGL((vfy_decode_kernel<X, true, false>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
+    } else {
+        if (validate) hipLaunchKernelGGL((vfy_decode_kernel<X, false, true>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
+        else hipLaunchKernelGGL((vfy_decode_kernel<X, false, false>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
+    }
+}
+void decode_points(int curve, bool compressed, bool validate, const uint8_t* images, uint64_t n_images, const VfyPoints& pts, uint32_t* bases, uint32_t* inf,
+                   uint32_t* a_bases, uint32_t* a_inf, unsigned long long* err) {
+    if (curve == MZK_CURVE_BLS12_381) launch_decode<BlsFqX>(compressed, validate, images, n_images, pts, bases, inf, a_bases, a_inf, err);
+    else launch_decode<BnFqX>(compressed, validate, images, n_images, pts, bases, inf, a_bases, a_inf, err);
+}
+
+void script_item(std::vector<uint8_t>& s, uint32_t& n_items, const char* label, const uint8_t* msg, size_t len) {
+    const size_t ll = std::strlen(label);
+    s.push_back((uint8_t)ll);
+    s.push_back((uint8_t)len);
+    s.insert(s.end(), label, label + ll);
+    s.insert(s.end(), msg, msg + len);
+    n_items++;
+}
+template <class FrP>
+bool fr_to_mont_host(const uint8_t* rec32, uint64_t* out) {      // false: not below r
+    Fp64<FrP> a, r2;
+    std::memcpy(a.l, rec32, 32);
+    if (Fp64<FrP>::geq_mod(a.l)) return false;
+    for (int i = 0; i < 4; i++) r2.l[i] = Fp64<FrP>::c64(FrP::R2, i);
+    a = a * r2;
+    std::memcpy(out, a.l, 32);
+    return true;
+}
+template <class FqP>
+void fq_negate_host(uint64_t* y) {
+    Fp64<FqP> a;
+    std::memcpy(a.l, y, sizeof a.l);
+    a = neg(a);
+    std::memcpy(y, a.l, sizeof a.l);
+}
+
+Verifier* find_verifier(uint64_t h) {
+    auto it = g_verifiers.find(h);
+    if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return nullptr; }
+    return it->second.get();
+}
+Batch* find_batch(uint64_t h) {
+    auto it = g_batches.find(h);
+    if (it == g_batches.end()) { set_error("unknown batch handle"); return nullptr; }
+    return it->second.get();
+}
+
+int32_t verifier_create(int32_t curve, const uint8_t* vk, uint64_t len, uint32_t flags, uint64_t* out_handle) {
+    const bool compressed = flags & MZK_SER_COMPRESSED, validate = flags & MZK_SER_VALIDATE;
+    mzk_key_layout_t lay;
+    MZK_TRY(mzk_key_layout(curve, vk, len, (flags & MZK_SER_COMPRESSED) | MZK_KEY_VK_ONLY, &lay));
+    if (lay.is_merged) { set_error("merged verifying keys are not supported"); return MZK_ERR_UNSUPPORTED; }
+    if (len >= (1ull << 31)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    auto v = std::make_unique<Verifier>();
+    v->curve = curve;
+    v->flags = flags & MZK_SER_COMPRESSED;
+    VfyShape& sh = v->sh;
+    sh.W = lay.num_wire_types, sh.nsel = lay.num_selectors, sh.ultra = lay.has_plookup_vk, sh.n = lay.domain_size, sh.num_inputs = (uint32_t)lay.num_inputs;
+    if (lay.num_inputs > lay.domain_size) { set_error("num_inputs: larger than the domain"); return MZK_ERR_ENCODING; }
+    for (sh.log_n = 0; (1ull << sh.log_n) < sh.n; sh.log_n++) {}
+    sh.compressed = compressed, sh.g1_bytes = g1_bytes(curve, compressed);
+    sh.nkey = sh.nsel + sh.W + (sh.ultra ? 4 : 0) + 1;
+    proof_shape(sh);
+    const uint32_t G = sh.g1_bytes, nkey = sh.nkey, fqw = fq_words(curve);
+    // the key's commitments, decoded on the device; infinity is a normal value here (an unused selector commits to nothing)
+    VfyPoints pts{};
+    pts.n = nkey, pts.stride = (uint32_t)len, pts.open_idx = -1;
+    uint32_t p = 0;
+    std::vector<std::string> names;
+    for (uint32_t j = 0; j < sh.nsel; j++) { pts.off[p++] = (uint32_t)(lay.selector_comms_off + j * G); names.push_back("selector_comms[" + std::to_string(j) + "]"); }
+    for (uint32_t j = 0; j < sh.W; j++) { pts.off[p++] = (uint32_t)(lay.sigma_comms_off + j * G); names.push_back("sigma_comms[" + std::to_string(j) + "]"); }
+    static const char* const PLK[4] = {"range_table_comm", "key_table_comm", "table_dom_sep_comm", "q_dom_sep_comm"};
+    if (sh.ultra)
+        for (uint32_t j = 0; j < 4; j++) { pts.off[p++] = (uint32_t)(lay.plookup_comms_off + j * G); names.push_back(std::string("plookup_vk.") + PLK[j]); }
+    pts.off[p++] = (uint32_t)lay.g_off;
+    names.push_back("open_key.g");
+    DevMem image, err;
+    MZK_TRY(image.alloc(len));
+    MZK_TRY(err.alloc(8));
+    MZK_TRY(v->key_xy.alloc((size_t)nkey * 2 * fqw * 4));
+    MZK_TRY(v->key_inf.alloc((size_t)nkey * 4));
+    HIP_TRY(hipMemcpy(image.p, vk, len, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(err.p, 0xFF, 8));
+    decode_points(curve, compressed, validate, image.as<uint8_t>(), 1, pts, v->key_xy.as<uint32_t>(), v->key_inf.as<uint32_t>(), nullptr, nullptr,
+                  err.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpy(&bad, err.p, 8, hipMemcpyDeviceToHost));
+    if (bad != ~0ull) {
+        set_error("vk." + names[(bad >> 8) & 0xFFFFFF] + ": " + reason_text((uint32_t)(bad & 0xFF)));
+        return MZK_ERR_ENCODING;
+    }
+    // the byte script of append_vk_and_pub_input (transcript/mod.rs:45-104), commitments in their compressed form
+    std::vector<uint64_t> xy((size_t)nkey * 2 * fqw / 2);
+    std::vector<uint32_t> inf(nkey);
+    HIP_TRY(hipMemcpy(xy.data(), v->key_xy.p, (size_t)nkey * 2 * fqw * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(inf.data(), v->key_inf.p, (size_t)nkey * 4, hipMemcpyDeviceToHost));
+    for (uint32_t j = 0; j < nkey; j++)
+        if (inf[j]) std::memset(xy.data() + (size_t)j * fqw, 0, (size_t)fqw * 8);       // (0, 0): the encoder's infinity
+    const uint32_t GC = g1_bytes(curve, true);
+    std::vector<uint8_t> recs((size_t)nkey * GC), script;
+    MZK_TRY(mzk_ctx_g1_encode(curve, xy.data(), nkey, MZK_SER_COMPRESSED, recs.data()));
+    const uint32_t bits = curve == MZK_CURVE_BLS12_381 ? BlsFr::BITS : BnFr::BITS;
+    const uint64_t n64 = sh.n, ni64 = lay.num_inputs;
+    script_item(script, v->n_items, "field size in bits", reinterpret_cast<const uint8_t*>(&bits), 4);
+    script_item(script, v->n_items, "domain size", reinterpret_cast<const uint8_t*>(&n64), 8);
+    script_item(script, v->n_items, "input size", reinterpret_cast<const uint8_t*>(&ni64), 8);
+    std::vector<uint64_t> k_mont(4 * sh.W);
+    for (uint32_t j = 0; j < sh.W; j++) {
+        const uint8_t* rec = vk + lay.k_off + 32 * j;
+        const bool ok = curve == MZK_CURVE_BLS12_381 ? fr_to_mont_host<BlsFr>(rec, &k_mont[4 * j]) : fr_to_mont_host<BnFr>(rec, &k_mont[4 * j]);
+        if (!ok) { set_error("vk.k[" + std::to_string(j) + "]: not below the modulus"); return MZK_ERR_ENCODING; }
+        script_item(script, v->n_items, "wire subsets separators", rec, 32);
+    }
+    for (uint32_t j = 0; j < sh.nsel; j++) script_item(script, v->n_items, "selector commitments", &recs[(size_t)j * GC], GC);
+    for (uint32_t j = 0; j < sh.W; j++) script_item(script, v->n_items, "sigma commitments", &recs[(size_t)(sh.nsel + j) * GC], GC);
+    MZK_TRY(v->script.alloc(script.size()));
+    MZK_TRY(v->k_mont.alloc(k_mont.size() * 8));
+    HIP_TRY(hipMemcpy(v->script.p, script.data(), script.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v->k_mont.p, k_mont.data(), k_mont.size() * 8, hipMemcpyHostToDevice));
+    // h, beta_h: decoded on the host, where the pairing runs
+    v->h.resize(4 * fqw / 2);
+    v->beta_h.resize(4 * fqw / 2);
+    if (mzk_g2_decode(curve, vk + lay.h_off, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->h.data()) != MZK_OK) {
+        set_error(std::string("vk.open_key.h: ") + mzk_last_error());
+        return MZK_ERR_ENCODING;
+    }
+    if (mzk_g2_decode(curve, vk + lay.beta_h_off, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->beta_h.data()) != MZK_OK) {
+        set_error(std::string("vk.open_key.beta_h: ") + mzk_last_error());
+        return MZK_ERR_ENCODING;
+    }
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    *out_handle = g_next_verifier++;
+    g_verifiers[*out_handle] = std::move(v);
+    return MZK_OK;
+}
+
+// the container of proof i on the host: Vec counts and the Option tag against the key's type
+bool proof_container_ok(const VfyShape& sh, const uint8_t* img, std::string& why) {
+    const auto count = [&](uint32_t off) { uint64_t c; std::memcpy(&c, img + off, 8); return c; };
+    const auto expect = [&](const char* field, uint32_t off, uint64_t want) {
+        if (count(off) == want) return true;
+        why = std::string(field) + ".len: " + std::to_string(count(off)) + ", expected " + std::to_string(want);
+        return false;
+    };
+    const uint32_t W = sh.W, G = sh.g1_bytes;
+    if (!expect("wires_poly_comms", 0, W) || !expect("split_quot_poly_comms", sh.pt_off[W] + G, W) || !expect("wires_evals", sh.wires_evals_off - 8, W) ||
+        !expect("wire_sigma_evals", sh.sigma_evals_off - 8, W - 1))
+        return false;
+    const uint8_t tag = img[sh.perm_next_off + 32];
+    if (tag != (sh.ultra ? 1 : 0)) {
+        why = tag > 1 ? "plookup_proof: invalid Option tag" : sh.ultra ? "plookup_proof: absent under an UltraPlonk key" : "plookup_proof: present under a TurboPlonk key";
+        return false;
+    }
+    return !sh.ultra || expect("plookup_proof.h_poly_comms", sh.perm_next_off + 33, 2);
+}
+
+int32_t batch_begin(Verifier& v, uint64_t vh, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub, const uint8_t* extra,
+                    const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags, uint64_t* out_batch, uint64_t* out_u, uint64_t* out_bad) {
+    const VfyShape& sh = v.sh;
+    if (out_bad) *out_bad = ~0ull;
+    if (proof_len != sh.proof_len) {
+        if (out_bad) *out_bad = 0;
+        set_error("proof 0: length: " + std::to_string(proof_len) + " bytes, expected " + std::to_string(sh.proof_len) + " under this key");
+        return MZK_ERR_ENCODING;
+    }
+    for (uint64_t i = 0; i < K; i++) {
+        std::string why;
+        if (!proof_container_ok(sh, proofs + i * proof_len, why)) {
+            if (out_bad) *out_bad = i;
+            set_error("proof " + std::to_string(i) + ": " + why);
+            return MZK_ERR_ENCODING;
+        }
+    }
+    uint64_t extra_len = 0;
+    if (extra_ranges)
+        for (uint64_t i = 0; i < K; i++) {
+            const uint64_t b = extra_ranges[2 * i], e = extra_ranges[2 * i + 1];
+            if (b == ~0ull) continue;
+            if (e < b || e - b >= (1ull << 31) || !extra) { set_error("bad extra message range"); return MZK_ERR_INVALID_ARG; }
+            extra_len = std::max(extra_len, e);
+        }
+    const int curve = v.curve;
+    const uint32_t np = sh.np, nkey = sh.nkey, fqw = fq_words(curve);
+    const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
+    auto b = std::make_unique<Batch>();
+    b->v = &v, b->verifier = vh, b->K = K;
+    MZK_TRY(b->images.alloc(K * proof_len));
+    MZK_TRY(b->pub.alloc(K * sh.num_inputs * 32));
+    MZK_TRY(b->extra.alloc(extra_len));
+    MZK_TRY(b->extra_range.alloc(K * 16));
+    MZK_TRY(b->bases.alloc(n_bases * pt_bytes));
+    MZK_TRY(b->inf.alloc(n_bases * 4));
+    MZK_TRY(b->a_bases.alloc(2 * K * pt_bytes));
+    MZK_TRY(b->a_inf.alloc(2 * K * 4));
+    MZK_TRY(b->chal.alloc(K * 7 * 32));
+    MZK_TRY(b->key_rows.alloc(K * nkey * 32));
+    MZK_TRY(b->b_scal.alloc(n_bases * 32));
+    MZK_TRY(b->evals.alloc(K * 32));
+    MZK_TRY(b->a_scal.alloc(2 * K * 32));
+    MZK_TRY(b->weights.alloc(K * 32));
+    MZK_TRY(b->err.alloc(8));
+    HIP_TRY(hipMemcpy(b->images.p, proofs, K * proof_len, hipMemcpyHostToDevice));           // the K images in one copy
+    if (sh.num_inputs) HIP_TRY(hipMemcpy(b->pub.p, pub, K * sh.num_inputs * 32, hipMemcpyHostToDevice));
+    if (extra_len) HIP_TRY(hipMemcpy(b->extra.p, extra, extra_len, hipMemcpyHostToDevice));
+    if (extra_ranges) HIP_TRY(hipMemcpy(b->extra_range.p, extra_ranges, K * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b->err.p, 0xFF, 8));
+    HIP_TRY(hipMemcpy(b->bases.p, v.key_xy.p, nkey * pt_bytes, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(b->inf.p, v.key_inf.p, nkey * 4, hipMemcpyDeviceToDevice));
+    unsigned long long* err = b->err.as<unsigned long long>();
+    // A
+    VfyPoints pts{};
+    pts.n = np, pts.stride = sh.proof_len, pts.open_idx = (int32_t)(2 * sh.W + 1);
+    for (uint32_t j = 0; j < np; j++) pts.off[j] = sh.pt_off[j];
+    decode_points(curve, sh.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, pts, b->bases.as<uint32_t>() + (size_t)nkey * 2 * fqw,
+                  b->inf.as<uint32_t>() + nkey, b->a_bases.as<uint32_t>(), b->a_inf.as<uint32_t>(), err);
+    HIP_TRY(hipGetLastError());
+    // B, or the caller's challenges
+    const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+    if (challenges) {
+        HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
+    } else {
+        const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
+        if (curve == MZK_CURVE_BLS12_381)
+            hipLaunchKernelGGL((vfy_transcript_kernel<BlsFr, BlsFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.script.as<uint8_t>(),
+                               v.n_items, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), err);
+        else
+            hipLaunchKernelGGL((vfy_transcript_kernel<BnFr, BnFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.script.as<uint8_t>(),
+                               v.n_items, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), err);
+        HIP_TRY(hipGetLastError());
+    }
+    // C
+    uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
+    if (curve == MZK_CURVE_BLS12_381)
+        hipLaunchKernelGGL((vfy_scalars_kernel<BlsFr>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.k_mont.as<uint32_t>(),
+                           b->pub.as<uint32_t>(), b->chal.as<uint32_t>(), b->key_rows.as<uint32_t>(), proof_rows, b->evals.as<uint32_t>(), err);
+    else
+        hipLaunchKernelGGL((vfy_scalars_kernel<BnFr>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.k_mont.as<uint32_t>(),
+                           b->pub.as<uint32_t>(), b->chal.as<uint32_t>(), b->key_rows.as<uint32_t>(), proof_rows, b->evals.as<uint32_t>(), err);
+    HIP_TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));                             // (synchronises the three stages)
+    if (bad != ~0ull) {
+        const uint64_t i = bad >> 32;
+        const uint32_t field = (uint32_t)(bad >> 8) & 0xFFFFFF, reason = (uint32_t)bad & 0xFF;
+        std::string buf;
+        const std::string name = field >= VFY_FIELD_PUB_INPUT ? "public_input[" + std::to_string(field - VFY_FIELD_PUB_INPUT) + "]"
+                                 : field >= VFY_FIELD_EVAL    ? proof_eval_name(sh, field - VFY_FIELD_EVAL, buf)
+                                                              : proof_point_name(sh, field, buf);
+        if (out_bad) *out_bad = i;
+        set_error("proof " + std::to_string(i) + ": " + name + ": " + reason_text(reason));
+        return MZK_ERR_ENCODING;
+    }
+    if (out_u) HIP_TRY(hipMemcpy2D(out_u, 32, b->chal.as<uint8_t>() + 6 * 32, 7 * 32, 32, K, hipMemcpyDeviceToHost));
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    *out_batch = g_next_batch++;
+    g_batches[*out_batch] = std::move(b);
+    return MZK_OK;
+}
+
+int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_t* out_B) {
+    const Verifier& v = *b.v;
+    const VfyShape& sh = v.sh;
+    const uint64_t K = b.K;
+    const uint32_t np = sh.np, nkey = sh.nkey;
+    HIP_TRY(hipMemcpy(b.weights.p, weights, K * 32, hipMemcpyHostToDevice));
+    uint32_t* proof_rows = b.b_scal.as<uint32_t>() + (size_t)nkey * 8;
+    const dim3 wgrid((unsigned)((K * (np + 2) + 255) / 256));
+    if (v.curve == MZK_CURVE_BLS12_381) {
+        hipLaunchKernelGGL((vfy_weight_kernel<BlsFr>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
+                           b.inf.as<uint32_t>() + nkey, b.a_inf.as<uint32_t>(), proof_rows, b.a_scal.as<uint32_t>());
+        hipLaunchKernelGGL((vfy_colsum_kernel<BlsFr>), dim3(nkey), dim3(256), 0, nullptr, (unsigned long long)K, nkey, b.weights.as<uint32_t>(), b.key_rows.as<uint32_t>(),
+                           b.evals.as<uint32_t>(), b.inf.as<uint32_t>(), b.b_scal.as<uint32_t>());
+    } else {
+        hipLaunchKernelGGL((vfy_weight_kernel<BnFr>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
+                           b.inf.as<uint32_t>() + nkey, b.a_inf.as<uint32_t>(), proof_rows, b.a_scal.as<uint32_t>());
+        hipLaunchKernelGGL((vfy_colsum_kernel<BnFr>), dim3(nkey), dim3(256), 0, nullptr, (unsigned long long)K, nkey, b.weights.as<uint32_t>(), b.key_rows.as<uint32_t>(),
+                           b.evals.as<uint32_t>(), b.inf.as<uint32_t>(), b.b_scal.as<uint32_t>());
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    // the two MSMs of verifier.rs:217-247 through the variable-base path
+    const struct { void* bases; void* scalars; uint64_t n; uint64_t* out; } jobs[2] = {{b.a_bases.p, b.a_scal.p, 2 * K, out_A},
+                                                                                      {b.bases.p, b.b_scal.p, nkey + K * np, out_B}};
+    for (const auto& j : jobs) {
+        uint64_t srs = 0;
+        MZK_TRY(mzk_srs_register_dev(v.curve, j.bases, j.n, &srs, nullptr));
+        const int32_t rc = mzk_msm_dev(srs, 0, j.scalars, j.n, 1, j.out, nullptr);
+        (void)hipDeviceSynchronize();
+        (void)mzk_srs_release(srs);
+        MZK_TRY(rc);
+    }
+    return MZK_OK;
+}
+
+}  // namespace
+}  // namespace mzk
+
+using namespace mzk;
+
+extern "C" int32_t mzk_verifier_create(int32_t curve_id, const uint8_t* vk_bytes, uint64_t len, uint32_t flags, uint64_t* out_handle) {
+    if (!valid_curve(curve_id) || !vk_bytes || !out_handle || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    MZK_TRY(bind_device());
+    return verifier_create(curve_id, vk_bytes, len, flags, out_handle);
+}
+
+extern "C" int32_t mzk_verifier_destroy(uint64_t verifier) {
+    std::unique_ptr<Verifier> v;
+    {
+        std::lock_guard<std::mutex> lk(g_vfy_lock);
+        auto it = g_verifiers.find(verifier);
+        if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
+        for (const auto& kv : g_batches)
+            if (kv.second->verifier == verifier) { set_error("the verifier has an open batch"); return MZK_ERR_INVALID_ARG; }
+        v = std::move(it->second);
+        g_verifiers.erase(it);
+    }
+    MZK_TRY(bind_device());
+    return MZK_OK;                                                    // (v's buffers go with it)
+}
+
+extern "C" int32_t mzk_verifier_shape(uint64_t verifier, uint32_t* out_n_proof_points, uint32_t* out_n_key_bases, uint64_t* out_proof_len, uint64_t* out_num_inputs) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    Verifier* v = find_verifier(verifier);
+    if (!v) return MZK_ERR_BAD_HANDLE;
+    if (out_n_proof_points) *out_n_proof_points = v->sh.np;
+    if (out_n_key_bases) *out_n_key_bases = v->sh.nkey;
+    if (out_proof_len) *out_proof_len = v->sh.proof_len;
+    if (out_num_inputs) *out_num_inputs = v->sh.num_inputs;
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* public_inputs_canonical,
+                                            const uint8_t* extra_msgs, const uint64_t* extra_ranges, const uint64_t* challenges_mont, uint32_t flags,
+                                            uint64_t* out_batch, uint64_t* out_u_mont, uint64_t* out_bad_index) {
+    Verifier* v;
+    {
+        std::lock_guard<std::mutex> lk(g_vfy_lock);
+        v = find_verifier(verifier);
+    }
+    if (!v) return MZK_ERR_BAD_HANDLE;
+    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->sh.num_inputs && !public_inputs_canonical) || (flags & ~MZK_SER_VALIDATE)) {
+        set_error("bad argument");
+        return MZK_ERR_INVALID_ARG;
+    }
+    MZK_TRY(bind_device());
+    return batch_begin(*v, verifier, proofs, proof_len, K, public_inputs_canonical, extra_msgs, extra_ranges, challenges_mont, flags, out_batch, out_u_mont,
+                       out_bad_index);
+}
+
+extern "C" int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    Batch* b = find_batch(batch);
+    if (!b) return MZK_ERR_BAD_HANDLE;
+    if (!out) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    MZK_TRY(bind_device());
+    return hip_status(hipMemcpy(out, b->chal.p, b->K * 7 * 32, hipMemcpyDeviceToHost), "hipMemcpy of the challenges");
+}
+
+extern "C" int32_t mzk_verifier_batch_scalars(uint64_t batch, uint64_t* out_key_rows, uint64_t* out_proof_rows, uint64_t* out_evals) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    Batch* b = find_batch(batch);
+    if (!b) return MZK_ERR_BAD_HANDLE;
+    MZK_TRY(bind_device());
+    const VfyShape& sh = b->v->sh;
+    if (out_key_rows) HIP_TRY(hipMemcpy(out_key_rows, b->key_rows.p, b->K * sh.nkey * 32, hipMemcpyDeviceToHost));
+    if (out_proof_rows) HIP_TRY(hipMemcpy(out_proof_rows, b->b_scal.as<uint8_t>() + (size_t)sh.nkey * 32, b->K * sh.np * 32, hipMemcpyDeviceToHost));
+    if (out_evals) HIP_TRY(hipMemcpy(out_evals, b->evals.p, b->K * 32, hipMemcpyDeviceToHost));
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_verifier_batch_finish(uint64_t batch, const uint64_t* r_weights_mont, uint64_t* out_A_xyz, uint64_t* out_B_xyz) {
+    std::unique_ptr<Batch> b;
+    {
+        std::lock_guard<std::mutex> lk(g_vfy_lock);
+        auto it = g_batches.find(batch);
+        if (it == g_batches.end()) { set_error("unknown batch handle"); return MZK_ERR_BAD_HANDLE; }
+        b = std::move(it->second);                                    // consumed, whatever follows
+        g_batches.erase(it);
+    }
+    MZK_TRY(bind_device());
+    if (!r_weights_mont && !out_A_xyz && !out_B_xyz) return MZK_OK;   // discarded
+    if (!r_weights_mont || !out_A_xyz || !out_B_xyz) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    return batch_finish(*b, r_weights_mont, out_A_xyz, out_B_xyz);
+}
+
+extern "C" int32_t mzk_verifier_check(uint64_t verifier, const uint64_t* A_xyz, const uint64_t* B_xyz, uint64_t n_groups, int32_t* out_accept) {
+    Verifier* v;
+    {
+        std::lock_guard<std::mutex> lk(g_vfy_lock);
+        v = find_verifier(verifier);
+    }
+    if (!v) return MZK_ERR_BAD_HANDLE;
+    if (!A_xyz || !B_xyz || !n_groups || !out_accept) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    const int curve = v->curve;
+    const size_t L = fq_words(curve) / 2;                             // 64-bit limbs of Fq
+    std::vector<uint64_t> sum(2 * 3 * L), g1(2 * 2 * L), g2(2 * 4 * L);
+    MZK_TRY(mzk_g1_sum_jacobian(curve, A_xyz, n_groups, &sum[0]));
+    MZK_TRY(mzk_g1_sum_jacobian(curve, B_xyz, n_groups, &sum[3 * L]));
+    MZK_TRY(mzk_g1_jacobian_to_affine(curve, sum.data(), 2, g1.data()));
+    if (curve == MZK_CURVE_BLS12_381) fq_negate_host<BlsFq>(&g1[3 * L]);   // -B
+    else fq_negate_host<BnFq>(&g1[3 * L]);
+    std::memcpy(&g2[0], v->beta_h.data(), 4 * L * 8);
+    std::memcpy(&g2[4 * L], v->h.data(), 4 * L * 8);
+    return mzk_pairing_product_is_one(curve, g1.data(), g2.data(), 2, out_accept);   // e(A, beta_h) e(-B, h) = 1
+}

@@ -88,6 +88,135 @@ class VerifyingKey:
         out += vec([x.to_bytes(32, "little") for x in self.k]) + self.g + self.h + self.beta_h + bytes([int(self.is_merged)])
         return out + (b"\x00" if self.plookup_comms is None else b"\x01" + b"".join(self.plookup_comms))
 
+    def verifier(self, validate: bool = True) -> "Verifier":
+        """The device verifier of this key (mzk_verifier_create), created once and cached; release_verifier() frees it."""
+        v = getattr(self, "_verifier", None)
+        if v is None:
+            v = self._verifier = Verifier(self, validate)
+        return v
+
+    def release_verifier(self):
+        v = getattr(self, "_verifier", None)
+        if v is not None:
+            v.release()
+            self._verifier = None
+
+
+class ProofEncodingError(SerializationError):
+    """A proof that ark-serialize or the verifier's range checks would refuse (MZK_ERR_ENCODING).  .index: the lowest bad proof of the batch;
+    .field: the field of the `Proof` ("wires_poly_comms[2]", "wires_evals[0]", "length", ..); .reason: the library's text."""
+
+    def __init__(self, reason: str, index: int, field: str | None):
+        ValueError.__init__(self, reason)
+        self.index, self.field, self.reason = index, field, reason
+
+
+_PROOF_MSG = re.compile(r"^proof (\d+): ([^:]+): ")
+
+
+class Verifier:
+    """mzk_verifier_*: the decoded commitments, k and the transcript script of one VerifyingKey on the device, h and beta_h on the host.
+    begin() runs the per-proof stages of a group of proofs under this key and returns a VerifierBatch."""
+
+    def __init__(self, vk: VerifyingKey, validate: bool = True):
+        L = _lib.ensure_init()
+        self.vk, self.curve = vk, vk.curve
+        img = np.frombuffer(vk.serialize(), dtype=np.uint8)
+        h = C.c_uint64()
+        rc = L.mzk_verifier_create(vk.curve.curve_id, C.c_void_p(img.ctypes.data), img.shape[0],
+                                   (_SER_COMPRESSED if vk.compressed else 0) | (_SER_VALIDATE if validate else 0), C.byref(h))
+        if rc == _ERR_ENCODING:
+            _raise_encoding(L, None)
+        _lib.check(rc, "mzk_verifier_create")
+        self.handle = h.value
+        np_, nkey, plen, nin = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _lib.check(L.mzk_verifier_shape(self.handle, C.byref(np_), C.byref(nkey), C.byref(plen), C.byref(nin)), "mzk_verifier_shape")
+        self.n_proof_points, self.n_key_bases, self.proof_len, self.num_inputs = np_.value, nkey.value, plen.value, nin.value
+
+    def begin(self, proofs, public_inputs, extra_msgs=None, challenges=None, validate: bool = True) -> "VerifierBatch":
+        """mzk_verifier_batch_begin.  proofs: K images (bytes); public_inputs: K lists of num_inputs canonical integers; extra_msgs: None or
+        K entries, each bytes or None; challenges: None or (K, 7, 4) uint64 Montgomery (tau, beta, gamma, alpha, zeta, v, u) replacing the
+        transcript.  Raises ProofEncodingError naming the lowest bad proof."""
+        L = _lib.load()
+        K = len(proofs)
+        if K == 0 or len(public_inputs) != K or (extra_msgs is not None and len(extra_msgs) != K):
+            raise ValueError("the number of proofs / public inputs / extra messages differ, or no proof")
+        for i, p in enumerate(proofs):                                 # (the ABI takes one length for the batch)
+            if len(p) != self.proof_len:
+                raise ProofEncodingError(f"proof {i}: length: {len(p)} bytes, expected {self.proof_len} under this key", i, "length")
+        for pi in public_inputs:
+            if len(pi) != self.num_inputs:
+                raise ValueError("the circuit public input length != the verification key public input length")   # verifier.rs:99-108
+        images = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8)
+        pub = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for pi in public_inputs for x in pi), dtype=np.uint64) if self.num_inputs else None
+        extra = ranges = None
+        if extra_msgs is not None and any(m is not None for m in extra_msgs):
+            blob, r = b"", []
+            for m in extra_msgs:
+                r += [2**64 - 1, 0] if m is None else [len(blob), len(blob) + len(m)]
+                blob += b"" if m is None else bytes(m)
+            extra, ranges = np.frombuffer(blob + b"\0", dtype=np.uint8), np.array(r, dtype=np.uint64)
+        ch = None if challenges is None else np.ascontiguousarray(challenges, dtype=np.uint64).reshape(K, 7, 4)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        batch, bad = C.c_uint64(), C.c_uint64()
+        u = np.zeros((K, 4), dtype=np.uint64)
+        rc = L.mzk_verifier_batch_begin(self.handle, ptr(images), self.proof_len, K, ptr(pub), ptr(extra), ptr(ranges), ptr(ch), _SER_VALIDATE if validate else 0,
+                                        C.byref(batch), ptr(u), C.byref(bad))
+        if rc == _ERR_ENCODING:
+            msg = L.mzk_last_error().decode()
+            m = _PROOF_MSG.match(msg)
+            raise ProofEncodingError(msg, bad.value, m.group(2) if m else None)
+        _lib.check(rc, "mzk_verifier_batch_begin")
+        return VerifierBatch(self, batch.value, K, u)
+
+    def check(self, A_xyz, B_xyz) -> bool:
+        """mzk_verifier_check over the (A, B) of one or more groups with this key's open key: e(sum A, beta_h) e(-sum B, h) == 1."""
+        A = np.ascontiguousarray(A_xyz, dtype=np.uint64).reshape(-1, 3, self.curve.fq_limbs)
+        B = np.ascontiguousarray(B_xyz, dtype=np.uint64).reshape(-1, 3, self.curve.fq_limbs)
+        assert A.shape == B.shape and A.shape[0] >= 1
+        ok = C.c_int32()
+        _lib.check(_lib.load().mzk_verifier_check(self.handle, C.c_void_p(A.ctypes.data), C.c_void_p(B.ctypes.data), A.shape[0], C.byref(ok)), "mzk_verifier_check")
+        return bool(ok.value)
+
+    def release(self):
+        if self.handle:
+            _lib.check(_lib.load().mzk_verifier_destroy(self.handle), "mzk_verifier_destroy")
+            self.handle = 0
+
+
+class VerifierBatch:
+    """An open batch: .u (K, 4) Montgomery, challenges() / scalars() the stage outputs, finish(r_weights) -> (A, B) Jacobian; finish or
+    discard consumes it."""
+
+    def __init__(self, verifier: Verifier, handle: int, K: int, u: np.ndarray):
+        self.verifier, self.handle, self.K, self.u = verifier, handle, K, u
+
+    def challenges(self) -> np.ndarray:
+        out = np.zeros((self.K, 7, 4), dtype=np.uint64)
+        _lib.check(_lib.load().mzk_verifier_batch_challenges(self.handle, C.c_void_p(out.ctypes.data)), "mzk_verifier_batch_challenges")
+        return out
+
+    def scalars(self):
+        """(key_rows (K, NKEY, 4), proof_rows (K, NP, 4), evals (K, 4)), Montgomery, unweighted"""
+        v = self.verifier
+        kr, pr, ev = np.zeros((self.K, v.n_key_bases, 4), np.uint64), np.zeros((self.K, v.n_proof_points, 4), np.uint64), np.zeros((self.K, 4), np.uint64)
+        _lib.check(_lib.load().mzk_verifier_batch_scalars(self.handle, C.c_void_p(kr.ctypes.data), C.c_void_p(pr.ctypes.data), C.c_void_p(ev.ctypes.data)),
+                   "mzk_verifier_batch_scalars")
+        return kr, pr, ev
+
+    def finish(self, r_weights_mont):
+        L = self.verifier.curve.fq_limbs
+        w = np.ascontiguousarray(r_weights_mont, dtype=np.uint64).reshape(self.K, 4)
+        A, B = np.zeros((3, L), np.uint64), np.zeros((3, L), np.uint64)
+        h, self.handle = self.handle, 0
+        _lib.check(_lib.load().mzk_verifier_batch_finish(h, C.c_void_p(w.ctypes.data), C.c_void_p(A.ctypes.data), C.c_void_p(B.ctypes.data)), "mzk_verifier_batch_finish")
+        return A, B
+
+    def discard(self):
+        if self.handle:
+            h, self.handle = self.handle, 0
+            _lib.check(_lib.load().mzk_verifier_batch_finish(h, None, None, None), "mzk_verifier_batch_finish")
+
 
 class ProvingKey:
     """A loaded `ProvingKey<E>`: .prover (a TurboPlonkProver whose coefficient forms were decoded on the device), .vk (VerifyingKey) and

@@ -405,3 +405,22 @@ def msm_bigint_batch(pp: UnivariateProverParam, scalar_sets, base_offsets=None, 
         ptrs[i] = a.ctypes.data if a.size else None
     _lib.check(L.mzk_msm_batch(pp.handle, k, ptrs, lens, offa, int(scalars_are_mont), C.c_void_p(out.ctypes.data)), "mzk_msm_batch")
     return out
+
+
+def open_key_for_testing(curve, beta: int, h: bytes | None = None, compress: bool = True):
+    """(g, h, beta_h) of `gen_srs_for_testing` (srs.rs:118-153) as records of the mode `compress`: g the curve's G1 generator, h the G2
+    generator (or the record given), beta_h = [beta]h through the host G2 arithmetic (mzk_g2_mul; no GPU)."""
+    from . import transcript as _transcript
+    c = _curve(curve)
+    L = _lib.load()
+    flags, n = (1 if compress else 0), g2_record_bytes(c, compress)
+    one, k = (C.c_uint64 * 4)(1, 0, 0, 0), (C.c_uint64 * 4)(*[(beta % c.r >> (64 * i)) & (2**64 - 1) for i in range(4)])
+    h_buf = None if h is None else (C.c_uint8 * n).from_buffer_copy(bytes(h))
+    h_out, bh_out = (C.c_uint8 * n)(), (C.c_uint8 * n)()
+    _lib.check(L.mzk_g2_mul(c.curve_id, h_buf, one, flags | 2, h_out), "mzk_g2_mul")
+    _lib.check(L.mzk_g2_mul(c.curve_id, h_buf, k, flags | 2, bh_out), "mzk_g2_mul")
+    g = _transcript.g1_bytes(c, (c.gx, c.gy))
+    if not compress:                                      # x || y, no flag set: y's sign flag belongs to BN254's last byte and is ignored on read
+        size = len(g)
+        g = c.gx.to_bytes(size, "big") + c.gy.to_bytes(size, "big") if c.curve_id == 0 else c.gx.to_bytes(size, "little") + c.gy.to_bytes(size, "little")
+    return g, bytes(h_out), bytes(bh_out)

@@ -58,6 +58,20 @@ _SIGS = {
     "mzk_fr_decode_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_fr_encode_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    "mzk_g2_decode": [C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p],
+    "mzk_g2_mul": [C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p],
+    "mzk_pairing_product_is_one": [C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)],
+    "mzk_pairing_gt": [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_batch_verify_challenge": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p],
+    "mzk_verifier_create": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)],
+    "mzk_verifier_destroy": [C.c_uint64],
+    "mzk_verifier_shape": [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "mzk_verifier_batch_begin": [C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                 C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)],
+    "mzk_verifier_batch_challenges": [C.c_uint64, C.c_void_p],
+    "mzk_verifier_batch_scalars": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_verifier_batch_finish": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_verifier_check": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)],
     "mzk_srs_register_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_srs_register_serialized_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_srs_serialize": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p],

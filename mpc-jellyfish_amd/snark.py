@@ -327,3 +327,49 @@ def batch_prove(rng: _rng.ChaChaRng, circuits: list, pks: list, extra_transcript
     blinds, quot = draw_batch_blinders(circuits[0].curve, rng, W, [pk.ultra for pk in pks])
     core = _batch.batch_prove(pks, [cs.wire_values for cs in circuits], [list(cs.public_input) for cs in circuits], blinds, quot, extra_transcript_init_msg)
     return core, _batch.serialize_batch_proof(circuits[0].curve, core)
+
+
+def batch_verify(vks, public_inputs, proofs, extra_msgs) -> bool:
+    """PlonkKzgSnark::batch_verify (snark.rs:141-190) for single-instance proofs: vks are keys.VerifyingKey, proofs their serialized `Proof`s
+    (the mode of each key), extra_msgs one Optional[bytes] per proof.  Proofs are grouped by key and each group goes through the device in
+    one pass (keys.Verifier.begin); r is drawn from every proof's u in the CALLER's order (verifier.rs:203-215), the groups' (A, B) are
+    summed and checked by one product of two pairings.  Raises ValueError on mismatched lengths, an empty batch or differing open keys,
+    keys.ProofEncodingError on a malformed proof."""
+    from . import lib as _lib
+    import ctypes as C
+    K = len(proofs)
+    if not (len(vks) == len(public_inputs) == K == len(extra_msgs)):
+        raise ValueError("the number of verification keys / public inputs / proofs / extra messages differ")       # snark.rs:150-158
+    if K == 0:
+        raise ValueError("no proof to verify")
+    open_key = (vks[0].g, vks[0].h, vks[0].beta_h, vks[0].compressed)
+    groups, order = {}, []
+    for i, vk in enumerate(vks):
+        if (vk.g, vk.h, vk.beta_h, vk.compressed) != open_key:
+            raise ValueError("the verification keys have different open keys")                                      # snark.rs:160-166
+        if id(vk) not in groups:
+            groups[id(vk)] = (vk, [])
+            order.append(id(vk))
+        groups[id(vk)][1].append(i)
+    c = vks[0].curve
+    batches, u = [], np.zeros((K, 4), dtype=np.uint64)
+    try:
+        for key in order:
+            vk, idx = groups[key]
+            b = vk.verifier().begin([proofs[i] for i in idx], [public_inputs[i] for i in idx], [extra_msgs[i] for i in idx])
+            batches.append((vk, idx, b))
+            u[idx] = b.u
+        r = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.load().mzk_batch_verify_challenge(c.curve_id, C.c_void_p(u.ctypes.data), K, C.c_void_p(r.ctypes.data)), "mzk_batch_verify_challenge")
+        r_int = fr_from_mont(c, r.reshape(1, 4))[0]
+        weights = fr_to_mont(c, [pow(r_int, i, c.r) for i in range(K)])
+        results = [b.finish(weights[idx]) for _, idx, b in batches]
+    finally:
+        for _, _, b in batches:
+            b.discard()
+    return vks[0].verifier().check(np.stack([a for a, _ in results]), np.stack([b for _, b in results]))
+
+
+def verify(vk, public_input, proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None) -> bool:
+    """PlonkKzgSnark::verify (snark.rs:653-671): batch_verify of one proof (r = 1)."""
+    return batch_verify([vk], [public_input], [proof_bytes], [extra_transcript_init_msg])
