@@ -265,7 +265,14 @@ MZK_API int32_t mzk_batch_verify_challenge(int32_t curve_id, const uint64_t* u_m
  * the two MSMs of verifier.rs:217-247 through the variable-base path: A = sum r^i (W_i + u_i W'_i), B over the key's bases, the K x NP proof
  * points and -(sum r^i eval_i) g; Jacobian (x, y, z) Montgomery Fq.  The batch handle is consumed, also on failure; with all three pointers
  * NULL the batch is only discarded.
- * mzk_verifier_check: sums n_groups results (same open key), normalises, *out_accept = [ e(A, beta_h) e(-B, h) == 1 ]. */
+ * mzk_verifier_check: sums n_groups results (same open key), normalises, *out_accept = [ e(A, beta_h) e(-B, h) == 1 ].
+ *
+ * Handles and threads.  A verifier lives on the device of the thread that created it (MZK_ERR_NOT_INIT without one) and its handle, like
+ * the handle of every batch begun under it, carries that device: any thread may call with them whatever device it is bound to, and finds
+ * its own binding unchanged on return.  mzk_verifier_destroy refuses a verifier that has an open batch (MZK_ERR_INVALID_ARG, "the verifier
+ * has an open batch"; the verifier stays usable).  A destroy that races a call in flight on another thread is safe: the handle is gone at
+ * once, the call completes on the object it found, and the memory is freed when that call returns.  mzk_shutdown releases every verifier
+ * and open batch; their handles are MZK_ERR_BAD_HANDLE afterwards. */
 MZK_API int32_t mzk_verifier_create(int32_t curve_id, const uint8_t* vk_bytes, uint64_t len, uint32_t flags, uint64_t* out_handle);
 MZK_API int32_t mzk_verifier_destroy(uint64_t verifier);
 MZK_API int32_t mzk_verifier_shape(uint64_t verifier, uint32_t* out_n_proof_points, uint32_t* out_n_key_bases, uint64_t* out_proof_len, uint64_t* out_num_inputs);

@@ -55,6 +55,18 @@ struct DevBuf {
     void release();
     template <class T> T* as() { return reinterpret_cast<T*>(p); }
 };
+// One device allocation that lives as long as a call or an object: move-only, allocated once, freed by the destructor.  The free
+// happens on the device that is CURRENT then, so an owner dies only where its device is bound: inside the entry point that made it
+// (ENTER_* in mzk.hip), under the DeviceGuard of the handle that owns it (verifier.hip), or in mzk_shutdown's per-context loop.
+struct DevOwned {
+    void* p = nullptr;
+    DevOwned() = default;
+    DevOwned(DevOwned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevOwned& operator=(DevOwned&&) = delete;
+    ~DevOwned() { if (p) (void)hipFree(p); }
+    int32_t alloc(size_t bytes) { return hip_status(hipMalloc(&p, bytes ? bytes : 4), "hipMalloc"); }   // (0 bytes: still a valid pointer)
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
 
 struct Workspace {
     DevBuf ntt_scratch, scalars, hist, offs, cursor, sorted, buckets, collect, io, misc, digits, long_desc, long_parts, plonk_polys, plonk_out, pre_cnt, pre_off, pre_ce, pre_cb, poly_tmp, split, link_tmp, occ;
@@ -160,6 +172,19 @@ class WsHold {
 };
 inline uint64_t handle_make(int logical, uint64_t counter) { return ((uint64_t)(logical + 1) << 48) | counter; }
 inline int handle_ctx(uint64_t h) { return (int)(h >> 48) - 1; }
+// the calling thread works on a handle's (logical) device for the duration of an entry point, for the translation units whose handles
+// live outside Ctx (prover.hip, verifier.hip); the caller's own binding is back on return
+struct DeviceGuard {
+    int32_t prev = -1, rc = MZK_OK;
+    bool switched = false;
+    explicit DeviceGuard(int device) {
+        if (mzk_get_device(&prev) != MZK_OK) prev = -1;
+        if (prev != device) { rc = mzk_set_device(device); switched = rc == MZK_OK && prev >= 0; }
+    }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+    ~DeviceGuard() { if (switched) (void)mzk_set_device(prev); }
+};
 
 // ntt.hip
 // scale: 0 = boundary form in and out; 1 = output left in the internal form x * R' (R' = 2^261 = 32 R) of the quotient kernels;
@@ -238,6 +263,7 @@ int32_t plonk_quotient_combine_dev(int curve, int log_n, const uint32_t* classes
                                    const uint32_t* d_top /* nullable */, uint32_t n_top, uint32_t* d_out, hipStream_t st);
 int32_t plonk_pk_release(uint64_t handle);
 void plonk_release_all();
+void verifier_release_all();                                  // verifier.hip: every verifier and open batch of the current context (mzk_shutdown)
 int32_t plonk_quotient_dev(uint64_t handle, uint32_t* d_polys, uint64_t in_len, const uint32_t* tau /* NULL: TurboPlonk */, const uint32_t* alpha,
                            const uint32_t* beta, const uint32_t* gamma, uint32_t* d_out, hipStream_t st);
 int32_t plookup_sorted_vec_dev(uint64_t handle, const uint32_t* d_wires, const uint32_t* tau, uint32_t* d_table, uint32_t* d_lookup, uint32_t* d_sorted,

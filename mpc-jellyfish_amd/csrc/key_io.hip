@@ -13,23 +13,16 @@ int32_t fr_decode_dispatch(int curve, const uint8_t* d_image, uint32_t n_seg, co
     if (!n_seg || !row_len) return MZK_OK;
     FrSegments segs{};
     for (uint32_t s = 0; s < n_seg; s++) { segs.src[s] = src[s]; segs.count[s] = count[s]; segs.row[s] = row[s]; }
-    unsigned long long* d_err = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_err, sizeof(unsigned long long)));
     unsigned long long err = ~0ull;
-    hipError_t e = hipMemsetAsync(d_err, 0xFF, sizeof(err), st);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)((row_len + KEY_IO_THREADS - 1) / KEY_IO_THREADS), n_seg), block(KEY_IO_THREADS);
-        if (curve == MZK_CURVE_BLS12_381) hipLaunchKernelGGL((fr_decode_kernel<BlsFr>), grid, block, 0, st, d_image, segs, d_out, (unsigned long long)row_len, d_err);
-        else hipLaunchKernelGGL((fr_decode_kernel<BnFr>), grid, block, 0, st, d_image, segs, d_out, (unsigned long long)row_len, d_err);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_err);
-    if (e != hipSuccess) {
-        set_error(std::string("Fr decode: ") + hipGetErrorString(e));
-        return MZK_ERR_HIP;
-    }
+    DevOwned d_err;
+    MZK_TRY(d_err.alloc(sizeof(err)));
+    HIP_TRY(hipMemsetAsync(d_err.p, 0xFF, sizeof(err), st));
+    const dim3 grid((unsigned)((row_len + KEY_IO_THREADS - 1) / KEY_IO_THREADS), n_seg), block(KEY_IO_THREADS);
+    if (curve == MZK_CURVE_BLS12_381) hipLaunchKernelGGL((fr_decode_kernel<BlsFr>), grid, block, 0, st, d_image, segs, d_out, (unsigned long long)row_len, d_err.as<unsigned long long>());
+    else hipLaunchKernelGGL((fr_decode_kernel<BnFr>), grid, block, 0, st, d_image, segs, d_out, (unsigned long long)row_len, d_err.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     if (err != ~0ull) {
         *out_bad_seg = (uint32_t)(err >> FR_ERR_INDEX_BITS);
         *out_bad_index = err & ((1ull << FR_ERR_INDEX_BITS) - 1);

@@ -168,11 +168,6 @@ struct SrsBuilder {
         return MZK_OK;
     }
 };
-// a device buffer that lives for one call (freed directly: the context lock is held and is not recursive)
-struct DevScratch {
-    uint8_t* p = nullptr;
-    ~DevScratch() { if (p) (void)hipFree(p); }
-};
 
 // ---- host-pointer I/O slots ------------------------------------------------------------------------
 // The host-pointer entry points (mzk_ntt, mzk_ntt_batch, mzk_msm, mzk_msm_batch: what a shim that swaps only the two
@@ -317,6 +312,7 @@ int32_t mzk_shutdown(void) {
         ntt_release_plans();
         msm_release_streams();
         plonk_release_all();
+        verifier_release_all();
         for (auto& r : cx.prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
         cx.prof_recs.clear();
         cx.ws.release();
@@ -406,13 +402,13 @@ int32_t mzk_srs_register_serialized(int32_t curve_id, const uint8_t* point_bytes
     }
     // whole staging: one copy of the records, then one decode launch (the copy / decode split)
     const size_t bytes = (size_t)n_points * srs_record_bytes(curve_id, flags & MZK_SER_COMPRESSED);
-    DevScratch d_bytes;
-    HIP_TRY(hipMalloc((void**)&d_bytes.p, bytes ? bytes : 4));
+    DevOwned d_bytes;                                               // (call-scoped: the context is bound until the return)
+    MZK_TRY(d_bytes.alloc(bytes));
     {
         ProfScope ps("srs_load.copy", nullptr);
         if (bytes) MZK_TRY(hip_status(hipMemcpy(d_bytes.p, point_bytes, bytes, hipMemcpyHostToDevice), "hipMemcpy of the SRS records"));
     }
-    return srs_register_decoded(curve_id, d_bytes.p, n_points, flags, out_handle, out_bad_index, nullptr);
+    return srs_register_decoded(curve_id, d_bytes.as<uint8_t>(), n_points, flags, out_handle, out_bad_index, nullptr);
 }
 int32_t mzk_srs_register_serialized_dev(int32_t curve_id, const void* d_point_bytes, uint64_t n_points, uint32_t flags, uint64_t* out_handle,
                                         uint64_t* out_bad_index, void* stream) {
@@ -430,12 +426,12 @@ int32_t mzk_srs_serialize(uint64_t handle, uint64_t first, uint64_t n_points, ui
     if (first > s->n || n_points > s->n - first || (flags & ~MZK_SER_COMPRESSED) || (!out_bytes && n_points)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     if (!n_points) return MZK_OK;
     const size_t bytes = (size_t)n_points * srs_record_bytes(s->curve, flags & MZK_SER_COMPRESSED);
-    DevScratch d_out;
-    HIP_TRY(hipMalloc((void**)&d_out.p, bytes));
+    DevOwned d_out;
+    MZK_TRY(d_out.alloc(bytes));
     HIP_TRY(hipDeviceSynchronize());
     {
         ProfScope ps("srs_save.encode", nullptr);
-        MZK_TRY(srs_encode_dispatch(s->curve, s->d_xy + first * 2 * fq_words(s->curve), n_points, flags & MZK_SER_COMPRESSED, d_out.p, nullptr));
+        MZK_TRY(srs_encode_dispatch(s->curve, s->d_xy + first * 2 * fq_words(s->curve), n_points, flags & MZK_SER_COMPRESSED, d_out.as<uint8_t>(), nullptr));
     }
     ProfScope ps("srs_save.copy", nullptr);
     return hip_status(hipMemcpy(out_bytes, d_out.p, bytes, hipMemcpyDeviceToHost), "hipMemcpy of the SRS records");
@@ -446,11 +442,11 @@ int32_t mzk_ctx_g1_encode(int32_t curve_id, const uint64_t* xy_mont, uint64_t n_
     ENTER_CUR();
     if (!valid_curve(curve_id) || !xy_mont || !out_bytes || !n_points) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     const size_t in_bytes = (size_t)n_points * srs_point_bytes(curve_id), out_len = (size_t)n_points * srs_record_bytes(curve_id, flags & MZK_SER_COMPRESSED);
-    DevScratch d_in, d_out;
-    HIP_TRY(hipMalloc((void**)&d_in.p, in_bytes));
-    HIP_TRY(hipMalloc((void**)&d_out.p, out_len));
+    DevOwned d_in, d_out;
+    MZK_TRY(d_in.alloc(in_bytes));
+    MZK_TRY(d_out.alloc(out_len));
     HIP_TRY(hipMemcpy(d_in.p, xy_mont, in_bytes, hipMemcpyHostToDevice));
-    MZK_TRY(srs_encode_dispatch(curve_id, reinterpret_cast<const uint32_t*>(d_in.p), n_points, flags & MZK_SER_COMPRESSED, d_out.p, nullptr));
+    MZK_TRY(srs_encode_dispatch(curve_id, d_in.as<uint32_t>(), n_points, flags & MZK_SER_COMPRESSED, d_out.as<uint8_t>(), nullptr));
     return hip_status(hipMemcpy(out_bytes, d_out.p, out_len, hipMemcpyDeviceToHost), "hipMemcpy of the G1 records");
 }
 // ---- Fr records of a serialized key (key_io.hip) ----

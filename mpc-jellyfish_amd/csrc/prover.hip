@@ -369,17 +369,7 @@ std::shared_ptr<ProverBase> find(uint64_t h) {
     return it->second;
 }
 
-// the calling thread works on the prover's device for the duration of an entry point
-struct DeviceGuard {
-    int32_t prev = -1, rc = MZK_OK;
-    bool switched = false;
-    explicit DeviceGuard(int device) {
-        if (mzk_get_device(&prev) != MZK_OK) prev = -1;
-        if (prev != device) { rc = mzk_set_device(device); switched = rc == MZK_OK && prev >= 0; }
-    }
-    ~DeviceGuard() { if (switched) (void)mzk_set_device(prev); }
-};
-
+// the calling thread works on the prover's device for the duration of an entry point (DeviceGuard, internal.hpp)
 template <class F>
 int32_t guarded(ProverBase& p, F&& f) {
     DeviceGuard g(p.device);

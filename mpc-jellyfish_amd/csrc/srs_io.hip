@@ -61,22 +61,15 @@ int32_t srs_decode_dispatch(int curve, const uint8_t* d_in, uint64_t n, bool com
     *out_bad = ~0ull;
     *out_reason = -1;
     if (!n) return MZK_OK;
-    unsigned long long* d_err = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_err, SRS_BAD_REASONS * sizeof(unsigned long long)));
     unsigned long long err[SRS_BAD_REASONS];
-    hipError_t e = hipMemsetAsync(d_err, 0xFF, sizeof(err), st);
-    if (e == hipSuccess) {
-        if (curve == MZK_CURVE_BLS12_381) launch_decode_x<BlsFqX>(compressed, validate, d_in, n, d_xy, d_err, st);
-        else launch_decode_x<BnFqX>(compressed, validate, d_in, n, d_xy, d_err, st);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(d_err);
-    if (e != hipSuccess) {
-        set_error(std::string("SRS decode: ") + hipGetErrorString(e));
-        return MZK_ERR_HIP;
-    }
+    DevOwned d_err;
+    MZK_TRY(d_err.alloc(sizeof(err)));
+    HIP_TRY(hipMemsetAsync(d_err.p, 0xFF, sizeof(err), st));
+    if (curve == MZK_CURVE_BLS12_381) launch_decode_x<BlsFqX>(compressed, validate, d_in, n, d_xy, d_err.as<unsigned long long>(), st);
+    else launch_decode_x<BnFqX>(compressed, validate, d_in, n, d_xy, d_err.as<unsigned long long>(), st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     for (int k = 0; k < SRS_BAD_REASONS; k++)                     // a thread records only its first failing check: one reason holds the minimum
         if (err[k] < *out_bad) { *out_bad = err[k]; *out_reason = k; }
     return MZK_OK;

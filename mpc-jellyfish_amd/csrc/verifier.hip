@@ -10,36 +10,26 @@
 namespace mzk {
 namespace {
 
-struct DevMem {                                                   // one allocation, freed with its owner
-    void* p = nullptr;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    int32_t alloc(size_t bytes) { return hip_status(hipMalloc(&p, bytes ? bytes : 4), "hipMalloc (verifier)"); }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
 struct Verifier {
-    int curve = 0;
-    uint32_t flags = 0;                                           // MZK_SER_COMPRESSED: the mode of the key image and of every proof under it
-    VfyShape sh{};
-    DevMem key_xy, key_inf, k_mont, script;
+    int curve = 0, device = -1;                                   // device: the logical device it was created on, where its memory lives
+    VfyShape sh{};                                                // (sh.compressed: the mode of the key image and of every proof under it)
+    DevOwned key_xy, key_inf, k_mont, script;
     uint32_t n_items = 0;
     std::vector<uint64_t> h, beta_h;                              // mzk_g2_decode's output
 };
 struct Batch {
-    Verifier* v = nullptr;
-    uint64_t verifier = 0, K = 0;
-    DevMem images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
+    std::shared_ptr<Verifier> v;                                  // an open batch keeps its verifier alive
+    uint64_t K = 0;
+    DevOwned images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
 };
 
+// Handles name the logical device of their object (a batch has its verifier's).  g_vfy_lock covers map operations only: a look-up hands out a
+// shared_ptr held until the entry point returns, so a destroy or shutdown on another thread takes the handle away and the object goes with its last holder.
 std::mutex g_vfy_lock;
-std::map<uint64_t, std::unique_ptr<Verifier>> g_verifiers;
-std::map<uint64_t, std::unique_ptr<Batch>> g_batches;
+std::map<uint64_t, std::shared_ptr<Verifier>> g_verifiers;
+std::map<uint64_t, std::shared_ptr<Batch>> g_batches;
 uint64_t g_next_verifier = 1, g_next_batch = 1;
 
-int32_t bind_device() {                                           // the calling thread's context (MZK_ERR_NOT_INIT without one): binds its HIP device
-    int32_t d;
-    return mzk_get_device(&d);
-}
 uint32_t g1_bytes(int curve, bool compressed) { return (uint32_t)srs_record_bytes(curve, compressed); }
 
 // the layout of a `Proof` image (structs.rs:59-84) under this key's type and mode
@@ -134,26 +124,40 @@ void fq_negate_host(uint64_t* y) {
     std::memcpy(y, a.l, sizeof a.l);
 }
 
-Verifier* find_verifier(uint64_t h) {
+std::shared_ptr<Verifier> find_verifier(uint64_t h) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
     auto it = g_verifiers.find(h);
     if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return nullptr; }
-    return it->second.get();
+    return it->second;
 }
-Batch* find_batch(uint64_t h) {
+std::shared_ptr<Batch> find_batch(uint64_t h, bool consume = false) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
     auto it = g_batches.find(h);
     if (it == g_batches.end()) { set_error("unknown batch handle"); return nullptr; }
-    return it->second.get();
+    std::shared_ptr<Batch> b = it->second;
+    if (consume) g_batches.erase(it);
+    return b;
 }
+// An entry point that touches the device runs on the device its handle names (context bits that name no initialised context: an unknown handle).
+// The guard is declared BEFORE the shared_ptr, so a last reference drops -- and frees device memory -- while that device is still bound.
+int32_t guard_status(const DeviceGuard& g) {
+    if (g.rc == MZK_ERR_NOT_INIT) { set_error("unknown handle"); return MZK_ERR_BAD_HANDLE; }
+    return g.rc;
+}
+#define ON_DEVICE_OF(h, obj, find)       \
+    DeviceGuard guard_(handle_ctx(h));   \
+    MZK_TRY(guard_status(guard_));       \
+    const auto obj = find(h);            \
+    if (!obj) return MZK_ERR_BAD_HANDLE
 
-int32_t verifier_create(int32_t curve, const uint8_t* vk, uint64_t len, uint32_t flags, uint64_t* out_handle) {
+int32_t verifier_create(int32_t curve, int device, const uint8_t* vk, uint64_t len, uint32_t flags, uint64_t* out_handle) {
     const bool compressed = flags & MZK_SER_COMPRESSED, validate = flags & MZK_SER_VALIDATE;
     mzk_key_layout_t lay;
     MZK_TRY(mzk_key_layout(curve, vk, len, (flags & MZK_SER_COMPRESSED) | MZK_KEY_VK_ONLY, &lay));
     if (lay.is_merged) { set_error("merged verifying keys are not supported"); return MZK_ERR_UNSUPPORTED; }
     if (len >= (1ull << 31)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    auto v = std::make_unique<Verifier>();
-    v->curve = curve;
-    v->flags = flags & MZK_SER_COMPRESSED;
+    auto v = std::make_shared<Verifier>();
+    v->curve = curve, v->device = device;
     VfyShape& sh = v->sh;
     sh.W = lay.num_wire_types, sh.nsel = lay.num_selectors, sh.ultra = lay.has_plookup_vk, sh.n = lay.domain_size, sh.num_inputs = (uint32_t)lay.num_inputs;
     if (lay.num_inputs > lay.domain_size) { set_error("num_inputs: larger than the domain"); return MZK_ERR_ENCODING; }
@@ -174,7 +178,7 @@ int32_t verifier_create(int32_t curve, const uint8_t* vk, uint64_t len, uint32_t
         for (uint32_t j = 0; j < 4; j++) { pts.off[p++] = (uint32_t)(lay.plookup_comms_off + j * G); names.push_back(std::string("plookup_vk.") + PLK[j]); }
     pts.off[p++] = (uint32_t)lay.g_off;
     names.push_back("open_key.g");
-    DevMem image, err;
+    DevOwned image, err;
     MZK_TRY(image.alloc(len));
     MZK_TRY(err.alloc(8));
     MZK_TRY(v->key_xy.alloc((size_t)nkey * 2 * fqw * 4));
@@ -230,7 +234,7 @@ int32_t verifier_create(int32_t curve, const uint8_t* vk, uint64_t len, uint32_t
         return MZK_ERR_ENCODING;
     }
     std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_handle = g_next_verifier++;
+    *out_handle = handle_make(device, g_next_verifier++);
     g_verifiers[*out_handle] = std::move(v);
     return MZK_OK;
 }
@@ -255,8 +259,9 @@ bool proof_container_ok(const VfyShape& sh, const uint8_t* img, std::string& why
     return !sh.ultra || expect("plookup_proof.h_poly_comms", sh.perm_next_off + 33, 2);
 }
 
-int32_t batch_begin(Verifier& v, uint64_t vh, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub, const uint8_t* extra,
+int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub, const uint8_t* extra,
                     const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags, uint64_t* out_batch, uint64_t* out_u, uint64_t* out_bad) {
+    const Verifier& v = *vp;
     const VfyShape& sh = v.sh;
     if (out_bad) *out_bad = ~0ull;
     if (proof_len != sh.proof_len) {
@@ -283,8 +288,8 @@ int32_t batch_begin(Verifier& v, uint64_t vh, const uint8_t* proofs, uint64_t pr
     const int curve = v.curve;
     const uint32_t np = sh.np, nkey = sh.nkey, fqw = fq_words(curve);
     const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
-    auto b = std::make_unique<Batch>();
-    b->v = &v, b->verifier = vh, b->K = K;
+    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
+    b->v = vp, b->K = K;
     MZK_TRY(b->images.alloc(K * proof_len));
     MZK_TRY(b->pub.alloc(K * sh.num_inputs * 32));
     MZK_TRY(b->extra.alloc(extra_len));
@@ -353,30 +358,27 @@ int32_t batch_begin(Verifier& v, uint64_t vh, const uint8_t* proofs, uint64_t pr
     }
     if (out_u) HIP_TRY(hipMemcpy2D(out_u, 32, b->chal.as<uint8_t>() + 6 * 32, 7 * 32, 32, K, hipMemcpyDeviceToHost));
     std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_batch = g_next_batch++;
+    *out_batch = handle_make(v.device, g_next_batch++);
     g_batches[*out_batch] = std::move(b);
     return MZK_OK;
 }
 
-int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_t* out_B) {
-    const Verifier& v = *b.v;
-    const VfyShape& sh = v.sh;
-    const uint64_t K = b.K;
-    const uint32_t np = sh.np, nkey = sh.nkey;
-    HIP_TRY(hipMemcpy(b.weights.p, weights, K * 32, hipMemcpyHostToDevice));
+template <class Fr>
+void launch_finish(const Batch& b, uint64_t K, uint32_t np, uint32_t nkey) {
     uint32_t* proof_rows = b.b_scal.as<uint32_t>() + (size_t)nkey * 8;
     const dim3 wgrid((unsigned)((K * (np + 2) + 255) / 256));
-    if (v.curve == MZK_CURVE_BLS12_381) {
-        hipLaunchKernelGGL((vfy_weight_kernel<BlsFr>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
-                           b.inf.as<uint32_t>() + nkey, b.a_inf.as<uint32_t>(), proof_rows, b.a_scal.as<uint32_t>());
-        hipLaunchKernelGGL((vfy_colsum_kernel<BlsFr>), dim3(nkey), dim3(256), 0, nullptr, (unsigned long long)K, nkey, b.weights.as<uint32_t>(), b.key_rows.as<uint32_t>(),
-                           b.evals.as<uint32_t>(), b.inf.as<uint32_t>(), b.b_scal.as<uint32_t>());
-    } else {
-        hipLaunchKernelGGL((vfy_weight_kernel<BnFr>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
-                           b.inf.as<uint32_t>() + nkey, b.a_inf.as<uint32_t>(), proof_rows, b.a_scal.as<uint32_t>());
-        hipLaunchKernelGGL((vfy_colsum_kernel<BnFr>), dim3(nkey), dim3(256), 0, nullptr, (unsigned long long)K, nkey, b.weights.as<uint32_t>(), b.key_rows.as<uint32_t>(),
-                           b.evals.as<uint32_t>(), b.inf.as<uint32_t>(), b.b_scal.as<uint32_t>());
-    }
+    hipLaunchKernelGGL((vfy_weight_kernel<Fr>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
+                       b.inf.as<uint32_t>() + nkey, b.a_inf.as<uint32_t>(), proof_rows, b.a_scal.as<uint32_t>());
+    hipLaunchKernelGGL((vfy_colsum_kernel<Fr>), dim3(nkey), dim3(256), 0, nullptr, (unsigned long long)K, nkey, b.weights.as<uint32_t>(), b.key_rows.as<uint32_t>(),
+                       b.evals.as<uint32_t>(), b.inf.as<uint32_t>(), b.b_scal.as<uint32_t>());
+}
+int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_t* out_B) {
+    const Verifier& v = *b.v;
+    const uint64_t K = b.K;
+    const uint32_t np = v.sh.np, nkey = v.sh.nkey;
+    HIP_TRY(hipMemcpy(b.weights.p, weights, K * 32, hipMemcpyHostToDevice));
+    if (v.curve == MZK_CURVE_BLS12_381) launch_finish<BlsFr>(b, K, np, nkey);
+    else launch_finish<BnFr>(b, K, np, nkey);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     // the two MSMs of verifier.rs:217-247 through the variable-base path
@@ -394,74 +396,70 @@ int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_
 }
 
 }  // namespace
+
+void verifier_release_all() {                                         // mzk_shutdown, per context (bound): its handles go; what a call in flight holds goes with that call
+    const int logical = cur().logical;
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    for (auto it = g_batches.begin(); it != g_batches.end();) it = handle_ctx(it->first) == logical ? g_batches.erase(it) : std::next(it);
+    for (auto it = g_verifiers.begin(); it != g_verifiers.end();) it = handle_ctx(it->first) == logical ? g_verifiers.erase(it) : std::next(it);
+}
+
 }  // namespace mzk
 
 using namespace mzk;
 
 extern "C" int32_t mzk_verifier_create(int32_t curve_id, const uint8_t* vk_bytes, uint64_t len, uint32_t flags, uint64_t* out_handle) {
     if (!valid_curve(curve_id) || !vk_bytes || !out_handle || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    MZK_TRY(bind_device());
-    return verifier_create(curve_id, vk_bytes, len, flags, out_handle);
+    int32_t device;                                                   // the calling thread's context: a key image names no device
+    MZK_TRY(mzk_get_device(&device));
+    return verifier_create(curve_id, device, vk_bytes, len, flags, out_handle);
 }
 
 extern "C" int32_t mzk_verifier_destroy(uint64_t verifier) {
-    std::unique_ptr<Verifier> v;
-    {
-        std::lock_guard<std::mutex> lk(g_vfy_lock);
-        auto it = g_verifiers.find(verifier);
-        if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
-        for (const auto& kv : g_batches)
-            if (kv.second->verifier == verifier) { set_error("the verifier has an open batch"); return MZK_ERR_INVALID_ARG; }
-        v = std::move(it->second);
-        g_verifiers.erase(it);
-    }
-    MZK_TRY(bind_device());
-    return MZK_OK;                                                    // (v's buffers go with it)
+    DeviceGuard guard(handle_ctx(verifier));
+    MZK_TRY(guard_status(guard));
+    std::shared_ptr<Verifier> v;                                      // (the last reference, unless a call in flight holds one: the buffers go with it)
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    auto it = g_verifiers.find(verifier);
+    if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
+    for (const auto& kv : g_batches)
+        if (kv.second->v == it->second) { set_error("the verifier has an open batch"); return MZK_ERR_INVALID_ARG; }
+    v = std::move(it->second);
+    g_verifiers.erase(it);
+    return MZK_OK;
 }
 
 extern "C" int32_t mzk_verifier_shape(uint64_t verifier, uint32_t* out_n_proof_points, uint32_t* out_n_key_bases, uint64_t* out_proof_len, uint64_t* out_num_inputs) {
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    Verifier* v = find_verifier(verifier);
-    if (!v) return MZK_ERR_BAD_HANDLE;
-    if (out_n_proof_points) *out_n_proof_points = v->sh.np;
-    if (out_n_key_bases) *out_n_key_bases = v->sh.nkey;
-    if (out_proof_len) *out_proof_len = v->sh.proof_len;
-    if (out_num_inputs) *out_num_inputs = v->sh.num_inputs;
+    std::lock_guard<std::mutex> lk(g_vfy_lock);                       // host-only, no device bound: reads under the lock and holds no reference,
+    auto it = g_verifiers.find(verifier);                             // so it is never the last holder (mzk_verifier_check likewise)
+    if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
+    const VfyShape& sh = it->second->sh;
+    if (out_n_proof_points) *out_n_proof_points = sh.np;
+    if (out_n_key_bases) *out_n_key_bases = sh.nkey;
+    if (out_proof_len) *out_proof_len = sh.proof_len;
+    if (out_num_inputs) *out_num_inputs = sh.num_inputs;
     return MZK_OK;
 }
 
 extern "C" int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* public_inputs_canonical,
                                             const uint8_t* extra_msgs, const uint64_t* extra_ranges, const uint64_t* challenges_mont, uint32_t flags,
                                             uint64_t* out_batch, uint64_t* out_u_mont, uint64_t* out_bad_index) {
-    Verifier* v;
-    {
-        std::lock_guard<std::mutex> lk(g_vfy_lock);
-        v = find_verifier(verifier);
-    }
-    if (!v) return MZK_ERR_BAD_HANDLE;
+    ON_DEVICE_OF(verifier, v, find_verifier);
     if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->sh.num_inputs && !public_inputs_canonical) || (flags & ~MZK_SER_VALIDATE)) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
     }
-    MZK_TRY(bind_device());
-    return batch_begin(*v, verifier, proofs, proof_len, K, public_inputs_canonical, extra_msgs, extra_ranges, challenges_mont, flags, out_batch, out_u_mont,
-                       out_bad_index);
+    return batch_begin(v, proofs, proof_len, K, public_inputs_canonical, extra_msgs, extra_ranges, challenges_mont, flags, out_batch, out_u_mont, out_bad_index);
 }
 
 extern "C" int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out) {
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    Batch* b = find_batch(batch);
-    if (!b) return MZK_ERR_BAD_HANDLE;
+    ON_DEVICE_OF(batch, b, find_batch);
     if (!out) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    MZK_TRY(bind_device());
     return hip_status(hipMemcpy(out, b->chal.p, b->K * 7 * 32, hipMemcpyDeviceToHost), "hipMemcpy of the challenges");
 }
 
 extern "C" int32_t mzk_verifier_batch_scalars(uint64_t batch, uint64_t* out_key_rows, uint64_t* out_proof_rows, uint64_t* out_evals) {
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    Batch* b = find_batch(batch);
-    if (!b) return MZK_ERR_BAD_HANDLE;
-    MZK_TRY(bind_device());
+    ON_DEVICE_OF(batch, b, find_batch);
     const VfyShape& sh = b->v->sh;
     if (out_key_rows) HIP_TRY(hipMemcpy(out_key_rows, b->key_rows.p, b->K * sh.nkey * 32, hipMemcpyDeviceToHost));
     if (out_proof_rows) HIP_TRY(hipMemcpy(out_proof_rows, b->b_scal.as<uint8_t>() + (size_t)sh.nkey * 32, b->K * sh.np * 32, hipMemcpyDeviceToHost));
@@ -470,37 +468,32 @@ extern "C" int32_t mzk_verifier_batch_scalars(uint64_t batch, uint64_t* out_key_
 }
 
 extern "C" int32_t mzk_verifier_batch_finish(uint64_t batch, const uint64_t* r_weights_mont, uint64_t* out_A_xyz, uint64_t* out_B_xyz) {
-    std::unique_ptr<Batch> b;
-    {
-        std::lock_guard<std::mutex> lk(g_vfy_lock);
-        auto it = g_batches.find(batch);
-        if (it == g_batches.end()) { set_error("unknown batch handle"); return MZK_ERR_BAD_HANDLE; }
-        b = std::move(it->second);                                    // consumed, whatever follows
-        g_batches.erase(it);
-    }
-    MZK_TRY(bind_device());
+    DeviceGuard guard(handle_ctx(batch));                             // (looked at below: the handle is consumed first, whatever follows)
+    const std::shared_ptr<Batch> b = find_batch(batch, true);
+    if (!b) return MZK_ERR_BAD_HANDLE;
+    MZK_TRY(guard_status(guard));
     if (!r_weights_mont && !out_A_xyz && !out_B_xyz) return MZK_OK;   // discarded
     if (!r_weights_mont || !out_A_xyz || !out_B_xyz) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     return batch_finish(*b, r_weights_mont, out_A_xyz, out_B_xyz);
 }
 
 extern "C" int32_t mzk_verifier_check(uint64_t verifier, const uint64_t* A_xyz, const uint64_t* B_xyz, uint64_t n_groups, int32_t* out_accept) {
-    Verifier* v;
+    int curve = 0;
+    std::vector<uint64_t> g2;                                         // (beta_h, h), 2 x 4 L limbs: copied under the lock, no reference held
     {
         std::lock_guard<std::mutex> lk(g_vfy_lock);
-        v = find_verifier(verifier);
+        auto it = g_verifiers.find(verifier);
+        if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
+        curve = it->second->curve, g2 = it->second->beta_h;
+        g2.insert(g2.end(), it->second->h.begin(), it->second->h.end());
     }
-    if (!v) return MZK_ERR_BAD_HANDLE;
     if (!A_xyz || !B_xyz || !n_groups || !out_accept) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    const int curve = v->curve;
     const size_t L = fq_words(curve) / 2;                             // 64-bit limbs of Fq
-    std::vector<uint64_t> sum(2 * 3 * L), g1(2 * 2 * L), g2(2 * 4 * L);
+    std::vector<uint64_t> sum(2 * 3 * L), g1(2 * 2 * L);
     MZK_TRY(mzk_g1_sum_jacobian(curve, A_xyz, n_groups, &sum[0]));
     MZK_TRY(mzk_g1_sum_jacobian(curve, B_xyz, n_groups, &sum[3 * L]));
     MZK_TRY(mzk_g1_jacobian_to_affine(curve, sum.data(), 2, g1.data()));
     if (curve == MZK_CURVE_BLS12_381) fq_negate_host<BlsFq>(&g1[3 * L]);   // -B
     else fq_negate_host<BnFq>(&g1[3 * L]);
-    std::memcpy(&g2[0], v->beta_h.data(), 4 * L * 8);
-    std::memcpy(&g2[4 * L], v->h.data(), 4 * L * 8);
     return mzk_pairing_product_is_one(curve, g1.data(), g2.data(), 2, out_accept);   // e(A, beta_h) e(-B, h) = 1
 }

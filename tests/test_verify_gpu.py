@@ -378,3 +378,104 @@ def test_uncompressed_key_and_proofs(world, mj, pyref, cid, j):
     flipped[(8 + W * g1) + g1 + (8 + W * g1) + 2 * g1 + 8] ^= 1          # wires_evals[0]
     assert not mj.snark.batch_verify([vk] * 3, [case.pub] * 3, proofs[:2] + [bytes(flipped)], [EXTRAS[i] for i in idx])
     vk.release_verifier()
+
+
+# ---- handles: ownership, device and release (csrc/verifier.hip; DESIGN.md section 4.14 "Handles") ----
+ERR_INVALID_ARG, ERR_BAD_HANDLE = -1, -4
+
+
+@pytest.mark.parametrize("cid", [0, 1])
+def test_handle_lifecycle(world, mj, cid):
+    """an open batch holds its verifier: destroy is refused and changes nothing; destroyed / consumed handles are unknown to every entry point"""
+    import ctypes as C
+    case, c = world[cid]["cases"][0], mj.params.CURVES[cid]
+    L = mj.load()
+    one = fr_mont_limbs(c, [1])
+    v = mj.keys.Verifier(case.vk)
+    vh = v.handle
+    b = v.begin([case.proofs[0]], [case.pub])
+    bh = b.handle
+    assert L.mzk_verifier_destroy(vh) == ERR_INVALID_ARG and b"open batch" in L.mzk_last_error()
+    A, B = b.finish(one)
+    A2, B2 = v.begin([case.proofs[0]], [case.pub]).finish(one)        # the same proof with no destroy attempt in between
+    assert np.array_equal(A, A2) and np.array_equal(B, B2)
+    assert v.check(A, B)
+    assert L.mzk_verifier_destroy(vh) == 0
+    v.handle = 0
+    image = np.frombuffer(case.proofs[0], dtype=np.uint8)
+    pub = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in case.pub) or bytes(32), dtype=np.uint64)
+    ptr = lambda a: C.c_void_p(a.ctypes.data)
+    out, ok, big = C.c_uint64(), C.c_int32(), np.zeros((64, 4), dtype=np.uint64)
+    assert L.mzk_verifier_shape(vh, None, None, C.byref(out), None) == ERR_BAD_HANDLE
+    assert L.mzk_verifier_batch_begin(vh, ptr(image), len(case.proofs[0]), 1, ptr(pub), None, None, None, 0, C.byref(out), None, None) == ERR_BAD_HANDLE
+    assert L.mzk_verifier_check(vh, ptr(A), ptr(B), 1, C.byref(ok)) == ERR_BAD_HANDLE
+    assert L.mzk_verifier_destroy(vh) == ERR_BAD_HANDLE
+    assert L.mzk_verifier_batch_challenges(bh, ptr(big)) == ERR_BAD_HANDLE
+    assert L.mzk_verifier_batch_scalars(bh, None, None, None) == ERR_BAD_HANDLE
+    assert L.mzk_verifier_batch_finish(bh, ptr(one), ptr(big), ptr(big[32:])) == ERR_BAD_HANDLE
+
+
+def test_a_failed_begin_leaves_no_batch_open(world, mj):
+    case, c = world[0]["cases"][0], mj.params.CURVES[0]
+    W = len(case.pr[0]["wires_poly_comms"])
+    evals_off = (8 + W * 48) + 48 + (8 + W * 48) + 2 * 48 + 8
+    eval_r = bytearray(case.proofs[0])                                # wires_evals[1] = r: the malformed proof of the test above
+    eval_r[evals_off + 32:evals_off + 64] = c.r.to_bytes(32, "little")
+    v = mj.keys.Verifier(case.vk)
+    with pytest.raises(mj.keys.ProofEncodingError) as e:
+        v.begin([case.proofs[0], bytes(eval_r)], [case.pub] * 2)
+    assert (e.value.index, e.value.field) == (1, "wires_evals[1]")
+    assert mj.load().mzk_verifier_destroy(v.handle) == 0              # at once: nothing was left registered
+    v.handle = 0
+
+
+def test_a_handle_finds_its_device(world, mj, tmp_path):
+    """Two contexts in a child process (MZK_VIRTUAL_DEVICES=2, read at mzk_init): a verifier created on device 1 is driven from a thread bound to
+    device 0.  Handles name device 1, the results are the parent's, the thread's binding is untouched, and mzk_shutdown releases the handle."""
+    import json
+    import os
+    import subprocess
+    case, c = world[0]["cases"][0], mj.params.CURVES[0]
+    one = fr_mont_limbs(c, [1])
+    A, B = case.vk.verifier().begin([case.proofs[0]], [case.pub]).finish(one)
+    assert case.vk.verifier().check(A, B)
+    np.savez(tmp_path / "want.npz", A=A, B=B, one=one)
+    (tmp_path / "key.bin").write_bytes(case.vk.serialize())
+    (tmp_path / "proof.bin").write_bytes(case.proofs[0])
+    (tmp_path / "pub.json").write_text(json.dumps([int(x) for x in case.pub]))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = r'''
+import ctypes as C, json, os, sys
+import numpy as np
+sys.path.insert(0, %r)
+d = %r
+import mpc_jellyfish_amd as mj
+from importlib import import_module
+lib = import_module("mpc-jellyfish_amd.lib")
+L = lib.init(0)
+lib.check(L.mzk_init(1), "init1"); lib.check(L.mzk_set_device(1), "set1")
+def bound():
+    dev = C.c_int32(-1)
+    lib.check(L.mzk_get_device(C.byref(dev)), "get")
+    return dev.value
+want = np.load(os.path.join(d, "want.npz"))
+pub = json.load(open(os.path.join(d, "pub.json")))
+proof = open(os.path.join(d, "proof.bin"), "rb").read()
+v = mj.keys.VerifyingKey.deserialize(0, open(os.path.join(d, "key.bin"), "rb").read()).verifier()
+assert v.handle >> 48 == 2 and bound() == 1                         # created on the calling thread's device, which the handle names
+lib.check(L.mzk_set_device(0), "set0")
+b = v.begin([proof], [pub])
+assert b.handle >> 48 == 2 and bound() == 0
+ch = b.challenges()
+assert ch.any() and bound() == 0
+A, B = b.finish(want["one"])
+assert bound() == 0
+assert np.array_equal(A, want["A"]) and np.array_equal(B, want["B"])
+assert v.check(A, B) and bound() == 0
+lib.check(L.mzk_shutdown(), "shutdown")
+lib.check(L.mzk_init(0), "init0 again")
+assert L.mzk_verifier_shape(v.handle, None, None, None, None) == -4  # MZK_ERR_BAD_HANDLE: the shutdown released it
+print("ok")
+''' % (root, str(tmp_path))
+    out = subprocess.run([os.sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ, MZK_VIRTUAL_DEVICES="2"))
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-3000:]
