@@ -284,6 +284,56 @@ MZK_API int32_t mzk_verifier_batch_scalars(uint64_t batch, uint64_t* out_key_row
 MZK_API int32_t mzk_verifier_batch_finish(uint64_t batch, const uint64_t* r_weights_mont, uint64_t* out_A_xyz, uint64_t* out_B_xyz);
 MZK_API int32_t mzk_verifier_check(uint64_t verifier, const uint64_t* A_xyz, const uint64_t* B_xyz, uint64_t n_groups, int32_t* out_accept);
 
+/* ---- aggregated proofs: PlonkKzgSnark::verify_batch_proof (snark.rs:117-138; verifier.rs:68-184, 256-321) for `BatchProof`s of m >= 1
+ * instances under a TUPLE of m verifiers ("Aggregated proofs").  K BatchProofs under one tuple go through the device in
+ * one pass and leave an ordinary batch handle: mzk_verifier_batch_challenges / _scalars / _finish (discard too) and mzk_verifier_check take
+ * it as they take a single-proof batch, so the (A, B) of aggregated and of single-proof groups with one open key sum into one check.
+ *
+ * A BatchProof image (ark-serialize, derive order; structs.rs:266-291), every Vec a u64 count and its items:
+ *   wires_poly_comms_vec: Vec<Vec<G1>> (m x W)   prod_perm_poly_comms_vec: Vec<G1> (m)
+ *   poly_evals_vec: Vec<{ wires_evals: Vec<Fr> (W), wire_sigma_evals: Vec<Fr> (W - 1), perm_next_eval: Fr }> (m)
+ *   plookup_proofs_vec: Vec<Option<{ h_poly_comms: Vec<G1> (2), prod_lookup_poly_comm: G1, 15 Fr }>> (m)
+ *   split_quot_poly_comms: Vec<G1> (W)   opening_proof: G1   shifted_opening_proof: G1
+ * mzk_batch_proof_layout: host-only like mzk_key_layout (no GPU, no mzk_init).  The length of an image of m instances of one type (ultra: 0 |
+ * 1) on this curve and in this mode (flags: MZK_SER_COMPRESSED) and the offset of every record; offsets of a Vec point at its first item.
+ * With `image` (nullable) the container of that image of `len` bytes is checked as mzk_verifier_aggregate_begin checks it before anything is
+ * staged -- the length, every Vec count and every Option tag, in image order -- MZK_ERR_ENCODING with mzk_last_error() "instance <j>: <field>:
+ * <reason>", j = m for what belongs to the whole proof (the length, the outer counts, split_quot_poly_comms).  m = 0: MZK_ERR_INVALID_ARG;
+ * m > MZK_VERIFIER_MAX_INSTANCES: MZK_ERR_UNSUPPORTED.
+ *
+ * The tuple: every verifier of the same curve, device, image mode, domain size, open key (MZK_ERR_INVALID_ARG otherwise: "the verification
+ * keys have different open keys", "the domain size of the <j>-th verification key is different", ..) and Plonk type (a mixed tuple:
+ * MZK_ERR_UNSUPPORTED -- batch_prove makes no such proof).  One handle may stand at several positions (a key and its forks); everything is
+ * laid out per POSITION.
+ * mzk_verifier_aggregate_shape (host-only): points per BatchProof NP(m) = m (W + 1) + W + 2 + 3 m ultra; key bases NKEY(m) = m (NKEY_1 - 1)
+ * + 1; the image length; the public inputs per proof, sum_j num_inputs_j (each nullable).
+ * mzk_verifier_aggregate_begin: the contract of mzk_verifier_batch_begin with K BatchProof images and, per proof, the m instances' public
+ * inputs back to back in tuple order.  Column order, which mzk_verifier_batch_scalars reports and the MSM B follows:
+ *   key columns    position 0's block (selectors, sigmas, Ultra: range, key, table_dom_sep, q_dom_sep), position 1's, .., open_key.g last
+ *   proof columns  j < m: wires_j (W), prod_perm_j; then split_quot (W), opening, shifted_opening; then, Ultra, j < m: h_1, h_2, prod_lookup
+ * (m = 1: exactly the single-proof orders).  Any malformed proof: MZK_ERR_ENCODING, *out_bad_index the LOWEST bad proof and mzk_last_error()
+ * "proof <i>: instance <j>: <field>: <reason>" -- the lowest proof, then its lowest instance, then its first field, on every run (one 64-bit
+ * atomicMin over proof << 40 | instance << 33 | field << 4 | reason); no batch is left open.  An open aggregate batch holds every verifier
+ * of its tuple: mzk_verifier_destroy of any of them is refused until the batch is finished or discarded. */
+#define MZK_VERIFIER_MAX_INSTANCES 64u
+typedef struct mzk_batch_proof_layout {
+    uint32_t m, num_wire_types, ultra, g1_record_bytes;
+    uint64_t total_len;
+    uint64_t wires_off[MZK_VERIFIER_MAX_INSTANCES], prod_perm_off[MZK_VERIFIER_MAX_INSTANCES];          /* instance j: its W wire commitments; its permutation product */
+    uint64_t wires_evals_off[MZK_VERIFIER_MAX_INSTANCES], sigma_evals_off[MZK_VERIFIER_MAX_INSTANCES], perm_next_off[MZK_VERIFIER_MAX_INSTANCES];
+    uint64_t plookup_tag_off[MZK_VERIFIER_MAX_INSTANCES];                                               /* the Option tag; the next three: Ultra only, else 0 */
+    uint64_t h_off[MZK_VERIFIER_MAX_INSTANCES], prod_lookup_off[MZK_VERIFIER_MAX_INSTANCES], plookup_evals_off[MZK_VERIFIER_MAX_INSTANCES];
+    uint64_t split_quot_off, opening_off, shifted_opening_off;
+} mzk_batch_proof_layout_t;
+MZK_API int32_t mzk_batch_proof_layout(int32_t curve_id, uint32_t ultra, uint32_t m, uint32_t flags, const uint8_t* image, uint64_t len,
+                                       mzk_batch_proof_layout_t* out);
+MZK_API int32_t mzk_verifier_aggregate_shape(const uint64_t* verifiers, uint32_t m, uint32_t* out_n_proof_points, uint32_t* out_n_key_bases,
+                                             uint64_t* out_proof_len, uint64_t* out_num_inputs);
+MZK_API int32_t mzk_verifier_aggregate_begin(const uint64_t* verifiers, uint32_t m, const uint8_t* proofs, uint64_t proof_len, uint64_t K,
+                                             const uint64_t* public_inputs_canonical, const uint8_t* extra_msgs, const uint64_t* extra_ranges,
+                                             const uint64_t* challenges_mont, uint32_t flags, uint64_t* out_batch, uint64_t* out_u_mont,
+                                             uint64_t* out_bad_index);
+
 /* ---- MSM: replaces <E::G1 as VariableBaseMSM>::msm_bigint(bases, bigints)
  *      at univariate_kzg/mod.rs:109-111 (commit) and :151-155 (open).
  * Computes sum_{i<n} scalars[i] * srs[base_offset + i]; base_offset = num_leading_zeros of

@@ -1,5 +1,5 @@
 // verifier.cuh -- the per-proof work of PlonkKzgSnark::batch_verify on the device: K single-instance proofs under
-// ONE verifying key, staged as K images of proof_len bytes.
+// ONE verifying key, staged as K images of proof_len bytes.  Aggregated BatchProofs under a tuple of keys: the second half of this file.
 //   A  vfy_decode_kernel      one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array
 //   B  vfy_transcript_kernel  one thread per proof: the Merlin transcript of compute_challenges (verifier.rs:274-319) -> 7 challenges
 //   C  vfy_scalars_kernel     one thread per proof: prepare_pcs_info for one instance (verifier.rs:122-184, 340-733) -> one scalar per base
@@ -378,6 +378,328 @@ __global__ __launch_bounds__(256) void vfy_colsum_kernel(unsigned long long K, u
         if (key_inf[c]) s = Fp<P>::zero();
         store_fp<P>(out + c * 8ull, s);
     }
+}
+
+// ---- aggregated BatchProofs ----------------------------------------------------------------------------------------------------------
+// K BatchProof images (structs.rs:266-291) of m instances each under a tuple of m keys of one type, domain and open key.  Every instance
+// has the same W and type, so its records sit at base + j * stride; the decoder alone takes a table, in COLUMN order:
+//   key columns    position 0's block (selectors, sigmas, Ultra: range, key, table_dom_sep, q_dom_sep), position 1's, .., then open_key.g
+//   proof columns  j < m: wires_j (W), prod_perm_j | split_quot (W), opening, shifted_opening | Ultra, j < m: h_1, h_2, prod_lookup
+//   Aa vfy_agg_decode_kernel      one thread per G1 record, offsets and field names from device memory
+//   Ba vfy_agg_transcript_kernel  one thread per BatchProof: compute_challenges over m keys (verifier.rs:256-321)
+//   Ca vfy_agg_scalars_kernel     one thread per (proof, instance): that instance's share of prepare_pcs_info (verifier.rs:68-184)
+//   Fa vfy_agg_fold_kernel        one thread per proof: the m shares summed in instance order, the scalars that belong to the whole proof
+// Errors: atomicMin over (proof << 40 | instance << 33 | field << 4 | reason); what belongs to the whole proof counts as instance m.
+constexpr uint32_t VFY_MAX_INSTANCES = 64;                       // MZK_VERIFIER_MAX_INSTANCES
+struct VfyAggShape {
+    uint32_t m, W, nsel, ultra, np, nkey, nkey1, log_n, compressed, g1_bytes, proof_len, total_inputs;   // nkey1: one position's block
+    uint32_t wires_off, wires_stride;                            // instance j's first wire commitment
+    uint32_t prod_off;                                           // prod_perm_poly_comms_vec[0]; stride g1_bytes
+    uint32_t evals_off, evals_stride;                            // instance j's ProofEvaluations, at the count of wires_evals
+    uint32_t plk_off, plk_stride;                                // instance j's Option<PlookupProof>, at its tag
+    uint32_t quot_off;                                           // split_quot_poly_comms[0]; opening_proof and shifted_opening_proof follow the W records
+    unsigned long long n;
+};
+// pos_tab, 3 (m + 1) words: per position { byte offset of its script, items of its script, first public input }, then the totals
+
+MZK_D void vfy_agg_report(unsigned long long* err, unsigned long long proof, uint32_t inst, uint32_t field, uint32_t reason) {
+    atomicMin(err, (proof << 40) | ((unsigned long long)inst << 33) | ((unsigned long long)field << 4) | reason);
+}
+
+template <class X, bool COMPRESSED, bool VALIDATE>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_agg_decode_kernel(const uint8_t* __restrict__ images, unsigned long long n_images, uint32_t np, uint32_t stride,
+                                                                     const uint32_t* __restrict__ off, const uint32_t* __restrict__ fld /* instance << 8 | field */,
+                                                                     uint32_t open_idx, uint32_t* __restrict__ bases, uint32_t* __restrict__ inf_flags,
+                                                                     uint32_t* __restrict__ a_bases, uint32_t* __restrict__ a_inf, unsigned long long* __restrict__ err) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_images * np) return;
+    const unsigned long long i = t / np;
+    const uint32_t j = (uint32_t)(t % np);
+    uint32_t xy[2 * X::N];
+    const int rc = srs_decode_point<X, COMPRESSED, VALIDATE, true>(images + i * stride + off[j], xy);
+    if (rc >= 0) vfy_agg_report(err, i, fld[j] >> 8, fld[j] & 0xFFu, (uint32_t)rc);
+    const bool inf = rc != -1;
+    if (inf) {
+#pragma unroll
+        for (int k = 0; k < X::N; k++) { xy[k] = X::GEN_X[k]; xy[X::N + k] = X::GEN_Y[k]; }
+    }
+    uint32_t* out = bases + t * 2 * X::N;
+#pragma unroll
+    for (int k = 0; k < 2 * X::N; k++) out[k] = xy[k];
+    inf_flags[t] = inf;
+    if (j == open_idx || j == open_idx + 1) {                     // the two opening columns also go to the MSM A
+        const unsigned long long a = 2 * i + (j - open_idx);
+#pragma unroll
+        for (int k = 0; k < 2 * X::N; k++) a_bases[a * 2 * X::N + k] = xy[k];
+        a_inf[a] = inf;
+    }
+}
+
+template <class P, class X>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_agg_transcript_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyAggShape sh,
+                                                                         const uint8_t* __restrict__ script, const uint32_t* __restrict__ pos_tab,
+                                                                         const uint32_t* __restrict__ pub_inputs /* K x total_inputs canonical */,
+                                                                         const uint8_t* __restrict__ extra, const unsigned long long* __restrict__ extra_range,
+                                                                         uint32_t* __restrict__ challenges) {
+    __shared__ uint64_t lanes[25 * VFY_THREADS];
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const uint8_t* img = images + i * sh.proof_len;
+    const uint32_t G = sh.g1_bytes, W = sh.W, m = sh.m;
+    const bool cmp = sh.compressed;
+    merlin::Transcript t;
+    t.init(lanes + threadIdx.x, VFY_THREADS, VFY_LBL("PlonkProof"));
+    if (extra_range && extra_range[2 * i] != ~0ull) {
+        const unsigned long long b = extra_range[2 * i], e = extra_range[2 * i + 1];
+        t.append_begin(VFY_LBL("extra info"), (uint32_t)(e - b));
+        vfy_absorb_global(t, extra + b, (uint32_t)(e - b));
+    }
+    for (uint32_t j = 0; j < m; j++) {                            // append_vk_and_pub_input, position by position
+        const uint8_t* s = script + pos_tab[3 * j];
+        const uint32_t n_items = pos_tab[3 * j + 1], p0 = pos_tab[3 * j + 2], p1 = pos_tab[3 * j + 5];
+        for (uint32_t k = 0; k < n_items; k++) {
+            const uint32_t ll = s[0], ml = s[1];
+            t.begin_op(merlin::F_M | merlin::F_A);
+            vfy_absorb_global(t, s + 2, ll);
+            t.absorb_u32le(ml);
+            t.begin_op(merlin::F_A);
+            vfy_absorb_global(t, s + 2 + ll, ml);
+            s += 2 + ll + ml;
+        }
+        for (uint32_t k = p0; k < p1; k++) {
+            const uint32_t* w = pub_inputs + (i * sh.total_inputs + k) * 8ull;
+            uint32_t v[8];
+#pragma unroll
+            for (int l = 0; l < 8; l++) v[l] = w[l];
+            t.append_begin(VFY_LBL("public input"), 32);
+            vfy_absorb_words(t, v);
+        }
+    }
+    Fp<P> ch[7];
+    for (uint32_t j = 0; j < m; j++)
+        for (uint32_t k = 0; k < W; k++) vfy_append_g1<X>(t, VFY_LBL("witness_poly_comms"), img + sh.wires_off + j * sh.wires_stride + k * G, cmp);
+    ch[0] = vfy_challenge<P>(t, VFY_LBL("tau"));
+    if (sh.ultra)
+        for (uint32_t j = 0; j < m; j++)
+            for (uint32_t k = 0; k < 2; k++) vfy_append_g1<X>(t, VFY_LBL("h_poly_comms"), img + sh.plk_off + j * sh.plk_stride + 9 + k * G, cmp);
+    ch[1] = vfy_challenge<P>(t, VFY_LBL("beta"));
+    ch[2] = vfy_challenge<P>(t, VFY_LBL("gamma"));
+    for (uint32_t j = 0; j < m; j++) vfy_append_g1<X>(t, VFY_LBL("perm_poly_comms"), img + sh.prod_off + j * G, cmp);
+    if (sh.ultra)
+        for (uint32_t j = 0; j < m; j++) vfy_append_g1<X>(t, VFY_LBL("plookup_poly_comms"), img + sh.plk_off + j * sh.plk_stride + 9 + 2 * G, cmp);
+    ch[3] = vfy_challenge<P>(t, VFY_LBL("alpha"));
+    for (uint32_t k = 0; k < W; k++) vfy_append_g1<X>(t, VFY_LBL("quot_poly_comms"), img + sh.quot_off + k * G, cmp);
+    ch[4] = vfy_challenge<P>(t, VFY_LBL("zeta"));
+    for (uint32_t j = 0; j < m; j++) {                            // transcript/mod.rs:140-163, instance by instance
+        const uint8_t* ev = img + sh.evals_off + j * sh.evals_stride;
+        for (uint32_t k = 0; k < W; k++) { t.append_begin(VFY_LBL("wire_evals"), 32); vfy_absorb_global(t, ev + 8 + 32 * k, 32); }
+        for (uint32_t k = 0; k + 1 < W; k++) { t.append_begin(VFY_LBL("wire_sigma_evals"), 32); vfy_absorb_global(t, ev + 16 + 32 * (W + k), 32); }
+        t.append_begin(VFY_LBL("perm_next_eval"), 32);
+        vfy_absorb_global(t, ev + 16 + 32 * (2 * W - 1), 32);
+    }
+    if (sh.ultra)
+        for (uint32_t j = 0; j < m; j++) {                        // transcript/mod.rs:165-202
+            const uint8_t* pe = img + sh.plk_off + j * sh.plk_stride + 9 + 3 * G;
+            t.append_begin(VFY_LBL("lookup_table_eval"), 32);      vfy_absorb_global(t, pe + 32 * 0, 32);
+            t.append_begin(VFY_LBL("h_1_eval"), 32);               vfy_absorb_global(t, pe + 32 * 4, 32);
+            t.append_begin(VFY_LBL("prod_next_eval"), 32);         vfy_absorb_global(t, pe + 32 * 6, 32);
+            t.append_begin(VFY_LBL("lookup_table_next_eval"), 32); vfy_absorb_global(t, pe + 32 * 7, 32);
+            t.append_begin(VFY_LBL("h_1_next_eval"), 32);          vfy_absorb_global(t, pe + 32 * 10, 32);
+            t.append_begin(VFY_LBL("h_2_next_eval"), 32);          vfy_absorb_global(t, pe + 32 * 11, 32);
+        }
+    ch[5] = vfy_challenge<P>(t, VFY_LBL("v"));
+    vfy_append_g1<X>(t, VFY_LBL("open_proof"), img + sh.quot_off + W * G, cmp);
+    vfy_append_g1<X>(t, VFY_LBL("shifted_open_proof"), img + sh.quot_off + (W + 1) * G, cmp);
+    ch[6] = vfy_challenge<P>(t, VFY_LBL("u"));
+#pragma unroll
+    for (int k = 0; k < 7; k++) store_fp<P>(challenges + (i * 7 + k) * 8ull, ch[k]);
+}
+
+// an Fr record of the image: its range check (stage C makes one pass over an instance's records) and its value
+template <class P>
+MZK_D void vfy_agg_check_eval(const uint8_t* __restrict__ p, unsigned long long* err, unsigned long long proof, uint32_t inst, uint32_t index) {
+    uint32_t a[8];
+    fr_read_record(p, a);
+    if (!ser_below_modulus<P>(a)) vfy_agg_report(err, proof, inst, VFY_FIELD_EVAL + index, VFY_REASON_NOT_BELOW_R);
+}
+template <class P>
+MZK_D Fp<P> vfy_agg_eval(const uint8_t* __restrict__ p) {
+    Fp<P> a;
+    fr_read_record(p, a.l);
+    return to_mont(a);
+}
+template <class P>
+MZK_D Fp<P> vfy_pow_small(Fp<P> b, uint32_t e) {
+    Fp<P> r = Fp<P>::one();
+    for (; e; e >>= 1) {
+        if (e & 1) r = r * b;
+        b = sqr(b);
+    }
+    return r;
+}
+
+// Instance j of proof i.  The type is a template switch, so W and every column index is a constant: each scalar is finished in registers and
+// stored once, straight to its place in the proof's two rows (no run-time-indexed row in scratch).  partials: K x m, what instance j adds
+// to the proof's aggregated evaluation: sum of e * (its powers of v and u v) - step^j * (its linearisation constant).
+template <class P, bool ULTRA>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_agg_scalars_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyAggShape sh,
+                                                                      const uint32_t* __restrict__ k_mont /* m x W */, const uint32_t* __restrict__ pos_tab,
+                                                                      const uint32_t* __restrict__ pub_inputs, const uint32_t* __restrict__ challenges,
+                                                                      uint32_t* __restrict__ key_rows, uint32_t* __restrict__ proof_rows,
+                                                                      uint32_t* __restrict__ partials, unsigned long long* __restrict__ err) {
+    using F = Fp<P>;
+    constexpr uint32_t W = ULTRA ? 6 : 5, NSEL = ULTRA ? 14 : 13, SIG = NSEL, PLK = NSEL + W;
+    constexpr uint32_t C_V = 2 * W - 1 + (ULTRA ? 6 : 0), C_U = ULTRA ? 10 : 1;   // commitments one instance opens at zeta / at zeta w (verifier.rs:453-506)
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= K * sh.m) return;
+    const unsigned long long i = t / sh.m;
+    const uint32_t j = (uint32_t)(t % sh.m), G = sh.g1_bytes;
+    const uint8_t* img = images + i * sh.proof_len;
+    const F tau = load_fp<P>(challenges + (i * 7 + 0) * 8ull), beta = load_fp<P>(challenges + (i * 7 + 1) * 8ull),
+            gamma = load_fp<P>(challenges + (i * 7 + 2) * 8ull), alpha = load_fp<P>(challenges + (i * 7 + 3) * 8ull),
+            zeta = load_fp<P>(challenges + (i * 7 + 4) * 8ull), v = load_fp<P>(challenges + (i * 7 + 5) * 8ull),
+            u = load_fp<P>(challenges + (i * 7 + 6) * 8ull);
+    const uint8_t* ev = img + sh.evals_off + j * sh.evals_stride;
+    const uint8_t* pl = img + sh.plk_off + j * sh.plk_stride + 9 + 3 * G;
+    // every record's range check first; the values are then read where they are used -- the fifteen Plookup evaluations two or three times
+    // each, from cache: held in registers together they are 120 of them
+#pragma unroll 1
+    for (uint32_t k = 0; k < 2 * W; k++) vfy_agg_check_eval<P>(ev + (k < W ? 8 : 16) + 32 * k, err, i, j, k);
+    if constexpr (ULTRA) {
+#pragma unroll 1
+        for (uint32_t k = 0; k < 15; k++) vfy_agg_check_eval<P>(pl + 32 * k, err, i, j, 2 * W + k);
+    }
+    F we[W], se[W - 1];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++) we[k] = vfy_agg_eval<P>(ev + 8 + 32 * k);
+#pragma unroll
+    for (uint32_t k = 0; k + 1 < W; k++) se[k] = vfy_agg_eval<P>(ev + 16 + 32 * (W + k));
+    const F zn = vfy_agg_eval<P>(ev + 16 + 32 * (2 * W - 1));
+    // structs.rs:496-541
+    enum { RNG, KEY, DOM, QDOM, H1, QL, PRODN, RNGN, KEYN, DOMN, H1N, H2N, QLN, W3N, W4N };
+    const auto pe = [&](uint32_t k) { return vfy_agg_eval<P>(pl + 32 * k); };
+
+    // the domain (verifier.rs:776-788) and PI(zeta) over this instance's inputs (:845-880)
+    F w = F::from_const(P::ROOT);
+    for (int k = (int)sh.log_n; k < P::TWO_ADICITY; k++) w = sqr(w);
+    const F w_inv = inv_safegcd<P>(w), one = F::one(), n_f = from_u64<P>(sh.n);
+    F zeta_n = zeta;
+    for (uint32_t k = 0; k < sh.log_n; k++) zeta_n = sqr(zeta_n);
+    const F vanish = zeta_n - one;
+    const F l1 = vanish * inv_safegcd<P>(n_f * (zeta - one));
+    const F ln = vanish * w_inv * inv_safegcd<P>(n_f * (zeta - w_inv));
+    F pi = F::zero();
+    {
+        const uint32_t p0 = pos_tab[3 * j + 2], p1 = pos_tab[3 * j + 5];
+        const F vn = vanish * inv_safegcd<P>(n_f);
+        F g = one;
+        for (uint32_t k = p0; k < p1; k++) {
+            F val = load_fp<P>(pub_inputs + (i * sh.total_inputs + k) * 8ull);
+            if (!ser_below_modulus<P>(val.l)) vfy_agg_report(err, i, j, VFY_FIELD_PUB_INPUT + (k - p0), VFY_REASON_NOT_BELOW_R);
+            if (!vanish.is_zero()) pi = pi + vn * g * inv_safegcd<P>(zeta - g) * to_mont(val);
+            g = g * w;
+        }
+    }
+    const F a2 = sqr(alpha), a3 = a2 * alpha, a4 = sqr(a2), a5 = a4 * alpha, a6 = a4 * a2;
+    const F b1 = one + beta, g_b1 = gamma * b1;
+    const F base = vfy_pow_small<P>(ULTRA ? a6 * alpha : a3, j);   // :130-138: alpha^7 | alpha^3 per instance
+    // the constant term of the linearisation polynomial (:340-414)
+    F lin = pi - a2 * l1;
+    {
+        F acc = alpha * zn * (gamma + we[W - 1]);
+#pragma unroll
+        for (uint32_t k = 0; k + 1 < W; k++) acc = acc * (gamma + we[k] + beta * se[k]);
+        lin = lin - acc;
+    }
+    if constexpr (ULTRA) {
+        const F h1_e = pe(H1), h2n_e = pe(H2N);
+        const F pc = ln * (h1_e - h2n_e - a2) - alpha * l1 - a3 * (zeta - w_inv) * pe(PRODN) * (g_b1 + h1_e + beta * pe(H1N)) * (g_b1 + beta * h2n_e);
+        lin = lin + a3 * pc;
+    }
+    uint32_t* kr = key_rows + (i * sh.nkey + (unsigned long long)j * sh.nkey1) * 8ull;
+    uint32_t* pr = proof_rows + (i * sh.np + (unsigned long long)j * (W + 1)) * 8ull;
+    uint32_t* pk = proof_rows + (i * sh.np + (unsigned long long)sh.m * (W + 1) + W + 2 + 3ull * j) * 8ull;   // Ultra: h_1, h_2, prod_lookup
+    // [D]_1 (:513-652), times step^j
+    {
+        const F w01 = we[0] * we[1], w23 = we[2] * we[3];
+        const auto p5 = [](const F& a) { const F s = sqr(a); return sqr(s) * a; };
+        store_fp<P>(kr + 8 * 0, we[0] * base); store_fp<P>(kr + 8 * 1, we[1] * base); store_fp<P>(kr + 8 * 2, we[2] * base); store_fp<P>(kr + 8 * 3, we[3] * base);
+        store_fp<P>(kr + 8 * 4, w01 * base); store_fp<P>(kr + 8 * 5, w23 * base);
+        store_fp<P>(kr + 8 * 6, p5(we[0]) * base); store_fp<P>(kr + 8 * 7, p5(we[1]) * base); store_fp<P>(kr + 8 * 8, p5(we[2]) * base);
+        store_fp<P>(kr + 8 * 9, p5(we[3]) * base);
+        store_fp<P>(kr + 8 * 10, neg(we[4]) * base); store_fp<P>(kr + 8 * 11, base); store_fp<P>(kr + 8 * 12, w01 * w23 * we[4] * base);
+    }
+    F prod_s, plook_s = F::zero(), h2_s = F::zero();
+    {
+        F coeff = alpha;
+#pragma unroll
+        for (uint32_t k = 0; k < W; k++) coeff = coeff * (beta * load_fp<P>(k_mont + ((unsigned long long)j * W + k) * 8ull) * zeta + gamma + we[k]);
+        prod_s = (coeff + a2 * l1) * base;
+        coeff = alpha * beta * zn;
+#pragma unroll
+        for (uint32_t k = 0; k + 1 < W; k++) coeff = coeff * (beta * se[k] + gamma + we[k]);
+        store_fp<P>(kr + 8 * (SIG + W - 1), neg(coeff) * base);
+    }
+    if constexpr (ULTRA) {
+        const F ql_tau = pe(QL) * tau;
+        const F merged_lookup_x = we[5] + ql_tau * (pe(QDOM) + tau * (we[0] + tau * (we[1] + tau * we[2])));
+        const F table_x = pe(RNG) + ql_tau * (pe(DOM) + tau * (pe(KEY) + tau * (we[3] + tau * we[4])));
+        const F table_xw = pe(RNGN) + pe(QLN) * tau * (pe(DOMN) + tau * (pe(KEYN) + tau * (pe(W3N) + tau * pe(W4N))));
+        plook_s = (a4 * l1 + a5 * ln + a6 * (zeta - w_inv) * b1 * (gamma + merged_lookup_x) * (g_b1 + table_x + beta * table_xw)) * base;
+        h2_s = a6 * (w_inv - zeta) * pe(PRODN) * (g_b1 + pe(H1) + beta * pe(H1N)) * base;
+    }
+    // this instance's powers of v at zeta and of u v at zeta w (:453-506, :673-733): they start where instance j - 1 stopped
+    F share = F::zero(), vb = v * vfy_pow_small<P>(v, j * C_V), uvb = u * vfy_pow_small<P>(v, j * C_U);
+    const auto at_zeta = [&](const F& e) { const F p = vb; share = share + e * p; vb = vb * v; return p; };
+    const auto at_zeta_omega = [&](const F& e) { const F p = uvb; share = share + e * p; uvb = uvb * v; return p; };
+    F wire_s[W];
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++) wire_s[k] = at_zeta(we[k]);
+#pragma unroll
+    for (uint32_t k = 0; k + 1 < W; k++) store_fp<P>(kr + 8 * (SIG + k), at_zeta(se[k]));
+    store_fp<P>(pr + 8 * W, prod_s + at_zeta_omega(zn));
+    if constexpr (ULTRA) {
+        const F rng_s = at_zeta(pe(RNG)), key_s = at_zeta(pe(KEY)), h1_s = at_zeta(pe(H1)), ql_s = at_zeta(pe(QL)), dom_s = at_zeta(pe(DOM));
+        store_fp<P>(kr + 8 * (PLK + 3), at_zeta(pe(QDOM)));
+        store_fp<P>(pk + 8 * 2, plook_s + at_zeta_omega(pe(PRODN)));
+        store_fp<P>(kr + 8 * (PLK + 0), rng_s + at_zeta_omega(pe(RNGN)));
+        store_fp<P>(kr + 8 * (PLK + 1), key_s + at_zeta_omega(pe(KEYN)));
+        store_fp<P>(pk + 8 * 0, h1_s + at_zeta_omega(pe(H1N)));
+        store_fp<P>(pk + 8 * 1, h2_s + at_zeta_omega(pe(H2N)));
+        store_fp<P>(kr + 8 * 13, ql_s + at_zeta_omega(pe(QLN)));
+        wire_s[3] = wire_s[3] + at_zeta_omega(pe(W3N));
+        wire_s[4] = wire_s[4] + at_zeta_omega(pe(W4N));
+        store_fp<P>(kr + 8 * (PLK + 2), dom_s + at_zeta_omega(pe(DOMN)));
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < W; k++) store_fp<P>(pr + 8 * k, wire_s[k]);
+    store_fp<P>(partials + t * 8ull, share - base * lin);
+}
+
+// Proof i: eval = the m shares in instance order (a fixed order, no atomics on field elements); the split quotient's scalars (:654-665),
+// the two opening proofs' scalars in B (:236-240) and a zero under open_key.g, whose scalar is the finish's.
+template <class P>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_agg_fold_kernel(unsigned long long K, VfyAggShape sh, const uint32_t* __restrict__ challenges,
+                                                                   const uint32_t* __restrict__ partials, uint32_t* __restrict__ key_rows,
+                                                                   uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ evals) {
+    using F = Fp<P>;
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const F zeta = load_fp<P>(challenges + (i * 7 + 4) * 8ull), u = load_fp<P>(challenges + (i * 7 + 6) * 8ull);
+    F w = F::from_const(P::ROOT);
+    for (int k = (int)sh.log_n; k < P::TWO_ADICITY; k++) w = sqr(w);
+    F zeta_n = zeta;
+    for (uint32_t k = 0; k < sh.log_n; k++) zeta_n = sqr(zeta_n);
+    const F zeta_n2 = zeta_n * sqr(zeta);
+    uint32_t* own = proof_rows + (i * sh.np + (unsigned long long)sh.m * (sh.W + 1)) * 8ull;
+    F c = neg(zeta_n - F::one());
+    for (uint32_t k = 0; k < sh.W; k++) { store_fp<P>(own + 8 * k, c); c = c * zeta_n2; }
+    store_fp<P>(own + 8 * sh.W, zeta);
+    store_fp<P>(own + 8 * (sh.W + 1), u * zeta * w);
+    F eval = F::zero();
+    for (uint32_t j = 0; j < sh.m; j++) eval = eval + load_fp<P>(partials + (i * sh.m + j) * 8ull);
+    store_fp<P>(evals + i * 8ull, eval);
+    store_fp<P>(key_rows + (i * sh.nkey + sh.nkey - 1) * 8ull, F::zero());
 }
 
 }  // namespace mzk

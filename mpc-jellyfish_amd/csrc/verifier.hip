@@ -1,10 +1,12 @@
-// verifier.hip -- mzk_verifier_*: PlonkKzgSnark::batch_verify for single-instance proofs (snark.rs:141-190, verifier.rs:68-251).  The per-proof
+// verifier.hip -- mzk_verifier_*: PlonkKzgSnark::batch_verify for single-instance proofs (snark.rs:141-190, verifier.rs:68-251) and
+// verify_batch_proof for aggregated BatchProofs under a tuple of keys (snark.rs:117-138; mzk_verifier_aggregate_*).  The per-proof
 // work runs on the device (verifier.cuh: decode, Fiat-Shamir, linearisation scalars), the two MSMs through the variable-base path over a base
 // array registered per batch, the two pairings on the host (hostpairing.hpp behind mzk_pairing_product_is_one).
 #include "internal.hpp"
 #include "hostfp.hpp"
 #include "verifier.cuh"
 
+#include <algorithm>
 #include <memory>
 
 namespace mzk {
@@ -14,13 +16,18 @@ struct Verifier {
     int curve = 0, device = -1;                                   // device: the logical device it was created on, where its memory lives
     VfyShape sh{};                                                // (sh.compressed: the mode of the key image and of every proof under it)
     DevOwned key_xy, key_inf, k_mont, script;
-    uint32_t n_items = 0;
+    uint32_t n_items = 0, script_len = 0;
     std::vector<uint64_t> h, beta_h;                              // mzk_g2_decode's output
+    std::vector<uint64_t> g;                                      // open_key.g as decoded (host copy: an aggregate's tuple compares open keys)
 };
 struct Batch {
-    std::shared_ptr<Verifier> v;                                  // an open batch keeps its verifier alive
+    std::shared_ptr<Verifier> v;                                  // an open batch keeps its verifier alive ...
+    std::vector<std::shared_ptr<Verifier>> more;                  // ... and an aggregate batch the verifiers at positions 1 .. m - 1 of its tuple too
     uint64_t K = 0;
+    uint32_t np = 0, nkey = 0;                                    // columns of one proof's row and of the key row (an aggregate: NP(m), NKEY(m))
     DevOwned images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
+    DevOwned col_off, col_fld, script, pos_tab, k_mont, partials;   // an aggregate's tables (verifier.cuh)
+    bool holds(const std::shared_ptr<Verifier>& x) const { return v == x || std::find(more.begin(), more.end(), x) != more.end(); }
 };
 
 // Handles name the logical device of their object (a batch has its verifier's).  g_vfy_lock covers map operations only: a look-up hands out a
@@ -218,6 +225,8 @@ int32_t verifier_create(int32_t curve, int device, const uint8_t* vk, uint64_t l
     }
     for (uint32_t j = 0; j < sh.nsel; j++) script_item(script, v->n_items, "selector commitments", &recs[(size_t)j * GC], GC);
     for (uint32_t j = 0; j < sh.W; j++) script_item(script, v->n_items, "sigma commitments", &recs[(size_t)(sh.nsel + j) * GC], GC);
+    v->script_len = (uint32_t)script.size();
+    v->g.assign(xy.begin() + (size_t)(nkey - 1) * fqw, xy.begin() + (size_t)nkey * fqw);
     MZK_TRY(v->script.alloc(script.size()));
     MZK_TRY(v->k_mont.alloc(k_mont.size() * 8));
     HIP_TRY(hipMemcpy(v->script.p, script.data(), script.size(), hipMemcpyHostToDevice));
@@ -289,7 +298,7 @@ int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, 
     const uint32_t np = sh.np, nkey = sh.nkey, fqw = fq_words(curve);
     const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
     auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
-    b->v = vp, b->K = K;
+    b->v = vp, b->K = K, b->np = np, b->nkey = nkey;
     MZK_TRY(b->images.alloc(K * proof_len));
     MZK_TRY(b->pub.alloc(K * sh.num_inputs * 32));
     MZK_TRY(b->extra.alloc(extra_len));
@@ -375,7 +384,7 @@ void launch_finish(const Batch& b, uint64_t K, uint32_t np, uint32_t nkey) {
 int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_t* out_B) {
     const Verifier& v = *b.v;
     const uint64_t K = b.K;
-    const uint32_t np = v.sh.np, nkey = v.sh.nkey;
+    const uint32_t np = b.np, nkey = b.nkey;
     HIP_TRY(hipMemcpy(b.weights.p, weights, K * 32, hipMemcpyHostToDevice));
     if (v.curve == MZK_CURVE_BLS12_381) launch_finish<BlsFr>(b, K, np, nkey);
     else launch_finish<BnFr>(b, K, np, nkey);
@@ -392,6 +401,289 @@ int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_
         (void)mzk_srs_release(srs);
         MZK_TRY(rc);
     }
+    return MZK_OK;
+}
+
+// ---- aggregated BatchProofs (structs.rs:266-291) -------------------------------------------------------------------------------------------
+void batch_proof_layout(uint32_t G, bool ultra, uint32_t m, mzk_batch_proof_layout_t& L) {
+    const uint32_t W = ultra ? 6 : 5;
+    L = mzk_batch_proof_layout_t{};
+    L.m = m, L.num_wire_types = W, L.ultra = ultra, L.g1_record_bytes = G;
+    uint64_t o = 8;                                                                  // wires_poly_comms_vec
+    for (uint32_t j = 0; j < m; j++) { L.wires_off[j] = o + 8; o += 8 + (uint64_t)W * G; }
+    o += 8;                                                                          // prod_perm_poly_comms_vec
+    for (uint32_t j = 0; j < m; j++, o += G) L.prod_perm_off[j] = o;
+    o += 8;                                                                          // poly_evals_vec
+    for (uint32_t j = 0; j < m; j++) {
+        L.wires_evals_off[j] = o + 8; o += 8 + 32 * W;
+        L.sigma_evals_off[j] = o + 8; o += 8 + 32 * (W - 1);
+        L.perm_next_off[j] = o; o += 32;
+    }
+    o += 8;                                                                          // plookup_proofs_vec
+    for (uint32_t j = 0; j < m; j++) {
+        L.plookup_tag_off[j] = o; o += 1;
+        if (!ultra) continue;
+        L.h_off[j] = o + 8; o += 8 + 2 * G;
+        L.prod_lookup_off[j] = o; o += G;
+        L.plookup_evals_off[j] = o; o += 32 * 15;
+    }
+    L.split_quot_off = o + 8; o += 8 + (uint64_t)W * G;
+    L.opening_off = o; o += G;
+    L.shifted_opening_off = o; o += G;
+    L.total_len = o;
+}
+// the container of one image against the layout, in image order: `inst` is the instance the defect belongs to (m: the whole proof)
+bool batch_proof_container_ok(const mzk_batch_proof_layout_t& L, const uint8_t* img, uint64_t len, uint32_t& inst, std::string& why) {
+    const uint32_t m = L.m, W = L.num_wire_types;
+    inst = m;
+    if (len != L.total_len) {
+        why = "length: " + std::to_string(len) + " bytes, expected " + std::to_string(L.total_len) + " under these keys";
+        return false;
+    }
+    const auto expect = [&](const char* field, uint64_t off, uint64_t want, uint32_t j) {
+        uint64_t c;
+        std::memcpy(&c, img + off, 8);
+        if (c == want) return true;
+        inst = j;
+        why = std::string(field) + ".len: " + std::to_string(c) + ", expected " + std::to_string(want);
+        return false;
+    };
+    if (!expect("wires_poly_comms_vec", 0, m, m)) return false;
+    for (uint32_t j = 0; j < m; j++)
+        if (!expect("wires_poly_comms", L.wires_off[j] - 8, W, j)) return false;
+    if (!expect("prod_perm_poly_comms_vec", L.prod_perm_off[0] - 8, m, m) || !expect("poly_evals_vec", L.wires_evals_off[0] - 16, m, m)) return false;
+    for (uint32_t j = 0; j < m; j++)
+        if (!expect("wires_evals", L.wires_evals_off[j] - 8, W, j) || !expect("wire_sigma_evals", L.sigma_evals_off[j] - 8, W - 1, j)) return false;
+    if (!expect("plookup_proofs_vec", L.plookup_tag_off[0] - 8, m, m)) return false;
+    for (uint32_t j = 0; j < m; j++) {
+        const uint8_t tag = img[L.plookup_tag_off[j]];
+        if (tag != (L.ultra ? 1 : 0)) {
+            inst = j;
+            why = tag > 1 ? "plookup_proof: invalid Option tag" : L.ultra ? "plookup_proof: absent under an UltraPlonk key" : "plookup_proof: present under a TurboPlonk key";
+            return false;
+        }
+        if (L.ultra && !expect("plookup_proof.h_poly_comms", L.h_off[j] - 8, 2, j)) return false;
+    }
+    return expect("split_quot_poly_comms", L.split_quot_off - 8, W, m);
+}
+
+// the tuple on the host: one curve, device, mode, domain, open key and type; fills the shape the kernels take
+int32_t tuple_shape(const std::vector<std::shared_ptr<Verifier>>& vs, VfyAggShape& ag, mzk_batch_proof_layout_t& L) {
+    const Verifier& v0 = *vs[0];
+    const uint32_t m = (uint32_t)vs.size();
+    uint64_t total_inputs = 0;
+    for (uint32_t j = 0; j < m; j++) {
+        const Verifier& v = *vs[j];
+        if (v.curve != v0.curve) { set_error("the verification keys are of different curves"); return MZK_ERR_INVALID_ARG; }
+        if (v.device != v0.device) { set_error("the verifiers live on different devices"); return MZK_ERR_INVALID_ARG; }
+        if (v.sh.compressed != v0.sh.compressed) { set_error("the verification keys have different image modes"); return MZK_ERR_INVALID_ARG; }
+        if (v.sh.n != v0.sh.n) { set_error("the domain size of the " + std::to_string(j) + "-th verification key is different"); return MZK_ERR_INVALID_ARG; }
+        if (v.g != v0.g || v.h != v0.h || v.beta_h != v0.beta_h) { set_error("the verification keys have different open keys"); return MZK_ERR_INVALID_ARG; }
+        if (v.sh.ultra != v0.sh.ultra) { set_error("a tuple of TurboPlonk and UltraPlonk keys is not supported"); return MZK_ERR_UNSUPPORTED; }
+        total_inputs += v.sh.num_inputs;
+    }
+    if (total_inputs >= (1ull << 28)) { set_error("too many public inputs"); return MZK_ERR_UNSUPPORTED; }
+    const VfyShape& s = v0.sh;
+    batch_proof_layout(s.g1_bytes, s.ultra, m, L);
+    ag = VfyAggShape{};
+    ag.m = m, ag.W = s.W, ag.nsel = s.nsel, ag.ultra = s.ultra, ag.log_n = s.log_n, ag.compressed = s.compressed, ag.g1_bytes = s.g1_bytes, ag.n = s.n;
+    ag.nkey1 = s.nkey - 1, ag.nkey = m * ag.nkey1 + 1;
+    ag.np = m * (s.W + 1) + s.W + 2 + (s.ultra ? 3 * m : 0);
+    ag.proof_len = (uint32_t)L.total_len, ag.total_inputs = (uint32_t)total_inputs;
+    ag.wires_off = (uint32_t)L.wires_off[0], ag.wires_stride = 8 + s.W * s.g1_bytes;
+    ag.prod_off = (uint32_t)L.prod_perm_off[0];
+    ag.evals_off = (uint32_t)L.wires_evals_off[0] - 8, ag.evals_stride = 16 + 32 * 2 * s.W;
+    ag.plk_off = (uint32_t)L.plookup_tag_off[0], ag.plk_stride = s.ultra ? 9 + 3 * s.g1_bytes + 32 * 15 : 1;
+    ag.quot_off = (uint32_t)L.split_quot_off;
+    return MZK_OK;
+}
+int32_t find_tuple(const uint64_t* handles, uint32_t m, std::vector<std::shared_ptr<Verifier>>& vs) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    for (uint32_t j = 0; j < m; j++) {
+        auto it = g_verifiers.find(handles[j]);
+        if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
+        vs.push_back(it->second);
+    }
+    return MZK_OK;
+}
+int32_t tuple_args(const uint64_t* handles, uint32_t m) {
+    if (!handles || !m) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (m > MZK_VERIFIER_MAX_INSTANCES) { set_error("more than " + std::to_string(MZK_VERIFIER_MAX_INSTANCES) + " instances in one aggregate"); return MZK_ERR_UNSUPPORTED; }
+    return MZK_OK;
+}
+std::string agg_field_name(const VfyAggShape& ag, uint32_t inst, uint32_t field) {
+    const uint32_t W = ag.W;
+    std::string buf;
+    if (field >= VFY_FIELD_PUB_INPUT) return "public_input[" + std::to_string(field - VFY_FIELD_PUB_INPUT) + "]";
+    if (field >= VFY_FIELD_EVAL) {
+        VfyShape one{};
+        one.W = W;
+        return proof_eval_name(one, field - VFY_FIELD_EVAL, buf);
+    }
+    if (inst == ag.m) return field < W ? "split_quot_poly_comms[" + std::to_string(field) + "]" : field == W ? "opening_proof" : "shifted_opening_proof";
+    if (field < W) return "wires_poly_comms[" + std::to_string(field) + "]";
+    if (field == W) return "prod_perm_poly_comm";
+    return field < W + 3 ? "plookup_proof.h_poly_comms[" + std::to_string(field - W - 1) + "]" : "plookup_proof.prod_lookup_poly_comm";
+}
+
+template <class X>
+void launch_agg_decode(bool compressed, bool validate, const uint8_t* images, uint64_t K, const VfyAggShape& ag, const Batch& b, uint32_t* bases, uint32_t* inf,
+                       unsigned long long* err) {
+    const dim3 grid((unsigned)((K * ag.np + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+    const uint32_t open_idx = ag.m * (ag.W + 1) + ag.W;
+#define MZK_AGG_DECODE(C, V)                                                                                                                             \
+    hipLaunchKernelGGL((vfy_agg_decode_kernel<X, C, V>), grid, block, 0, nullptr, images, (unsigned long long)K, ag.np, ag.proof_len, b.col_off.as<uint32_t>(), \
+                       b.col_fld.as<uint32_t>(), open_idx, bases, inf, b.a_bases.as<uint32_t>(), b.a_inf.as<uint32_t>(), err)
+    if (compressed) {
+        if (validate) MZK_AGG_DECODE(true, true);
+        else MZK_AGG_DECODE(true, false);
+    } else {
+        if (validate) MZK_AGG_DECODE(false, true);
+        else MZK_AGG_DECODE(false, false);
+    }
+#undef MZK_AGG_DECODE
+}
+template <class Fr>
+void launch_agg_scalars(const Batch& b, uint64_t K, const VfyAggShape& ag, uint32_t* proof_rows, unsigned long long* err) {
+    const dim3 grid((unsigned)((K * ag.m + VFY_THREADS - 1) / VFY_THREADS)), fold((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+    if (ag.ultra)
+        hipLaunchKernelGGL((vfy_agg_scalars_kernel<Fr, true>), grid, block, 0, nullptr, b.images.as<uint8_t>(), (unsigned long long)K, ag, b.k_mont.as<uint32_t>(),
+                           b.pos_tab.as<uint32_t>(), b.pub.as<uint32_t>(), b.chal.as<uint32_t>(), b.key_rows.as<uint32_t>(), proof_rows, b.partials.as<uint32_t>(), err);
+    else
+        hipLaunchKernelGGL((vfy_agg_scalars_kernel<Fr, false>), grid, block, 0, nullptr, b.images.as<uint8_t>(), (unsigned long long)K, ag, b.k_mont.as<uint32_t>(),
+                           b.pos_tab.as<uint32_t>(), b.pub.as<uint32_t>(), b.chal.as<uint32_t>(), b.key_rows.as<uint32_t>(), proof_rows, b.partials.as<uint32_t>(), err);
+    hipLaunchKernelGGL((vfy_agg_fold_kernel<Fr>), fold, block, 0, nullptr, (unsigned long long)K, ag, b.chal.as<uint32_t>(), b.partials.as<uint32_t>(),
+                       b.key_rows.as<uint32_t>(), proof_rows, b.evals.as<uint32_t>());
+}
+
+int32_t aggregate_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub,
+                        const uint8_t* extra, const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags, uint64_t* out_batch, uint64_t* out_u,
+                        uint64_t* out_bad) {
+    VfyAggShape ag;
+    mzk_batch_proof_layout_t L;
+    MZK_TRY(tuple_shape(vs, ag, L));
+    if (ag.total_inputs && !pub) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    const Verifier& v0 = *vs[0];
+    const uint32_t m = ag.m, W = ag.W, np = ag.np, nkey = ag.nkey, nkey1 = ag.nkey1;
+    if (out_bad) *out_bad = ~0ull;
+    for (uint64_t i = 0; i < K; i++) {                               // (a wrong length is every proof's: reported for proof 0, as the single-proof path does)
+        std::string why;
+        uint32_t inst;
+        if (!batch_proof_container_ok(L, proofs + i * proof_len, proof_len, inst, why)) {
+            if (out_bad) *out_bad = i;
+            set_error("proof " + std::to_string(i) + ": instance " + std::to_string(inst) + ": " + why);
+            return MZK_ERR_ENCODING;
+        }
+    }
+    uint64_t extra_len = 0;
+    if (extra_ranges)
+        for (uint64_t i = 0; i < K; i++) {
+            const uint64_t b = extra_ranges[2 * i], e = extra_ranges[2 * i + 1];
+            if (b == ~0ull) continue;
+            if (e < b || e - b >= (1ull << 31) || !extra) { set_error("bad extra message range"); return MZK_ERR_INVALID_ARG; }
+            extra_len = std::max(extra_len, e);
+        }
+    // the tables: columns of stage A (offset; instance << 8 | field), the positions' scripts and public-input ranges
+    std::vector<uint32_t> col_off, col_fld, pos_tab;
+    const auto col = [&](uint64_t off, uint32_t inst, uint32_t field) { col_off.push_back((uint32_t)off); col_fld.push_back(inst << 8 | field); };
+    for (uint32_t j = 0; j < m; j++) {
+        for (uint32_t k = 0; k < W; k++) col(L.wires_off[j] + (uint64_t)k * ag.g1_bytes, j, k);
+        col(L.prod_perm_off[j], j, W);
+    }
+    for (uint32_t k = 0; k < W; k++) col(L.split_quot_off + (uint64_t)k * ag.g1_bytes, m, k);
+    col(L.opening_off, m, W);
+    col(L.shifted_opening_off, m, W + 1);
+    if (ag.ultra)
+        for (uint32_t j = 0; j < m; j++) {
+            col(L.h_off[j], j, W + 1);
+            col(L.h_off[j] + ag.g1_bytes, j, W + 2);
+            col(L.prod_lookup_off[j], j, W + 3);
+        }
+    uint32_t script_len = 0, inputs = 0;
+    for (uint32_t j = 0; j < m; j++) {
+        pos_tab.insert(pos_tab.end(), {script_len, vs[j]->n_items, inputs});
+        script_len += vs[j]->script_len, inputs += vs[j]->sh.num_inputs;
+    }
+    pos_tab.insert(pos_tab.end(), {script_len, 0u, inputs});
+    const int curve = v0.curve;
+    const uint32_t fqw = fq_words(curve);
+    const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
+    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
+    b->v = vs[0], b->more.assign(vs.begin() + 1, vs.end()), b->K = K, b->np = np, b->nkey = nkey;
+    MZK_TRY(b->images.alloc(K * proof_len));
+    MZK_TRY(b->pub.alloc(K * ag.total_inputs * 32));
+    MZK_TRY(b->extra.alloc(extra_len));
+    MZK_TRY(b->extra_range.alloc(K * 16));
+    MZK_TRY(b->bases.alloc(n_bases * pt_bytes));
+    MZK_TRY(b->inf.alloc(n_bases * 4));
+    MZK_TRY(b->a_bases.alloc(2 * K * pt_bytes));
+    MZK_TRY(b->a_inf.alloc(2 * K * 4));
+    MZK_TRY(b->chal.alloc(K * 7 * 32));
+    MZK_TRY(b->key_rows.alloc(K * nkey * 32));
+    MZK_TRY(b->b_scal.alloc(n_bases * 32));
+    MZK_TRY(b->evals.alloc(K * 32));
+    MZK_TRY(b->a_scal.alloc(2 * K * 32));
+    MZK_TRY(b->weights.alloc(K * 32));
+    MZK_TRY(b->err.alloc(8));
+    MZK_TRY(b->col_off.alloc((size_t)np * 4));
+    MZK_TRY(b->col_fld.alloc((size_t)np * 4));
+    MZK_TRY(b->script.alloc(script_len));
+    MZK_TRY(b->pos_tab.alloc(pos_tab.size() * 4));
+    MZK_TRY(b->k_mont.alloc((size_t)m * W * 32));
+    MZK_TRY(b->partials.alloc(K * m * 32));
+    HIP_TRY(hipMemcpy(b->images.p, proofs, K * proof_len, hipMemcpyHostToDevice));
+    if (ag.total_inputs) HIP_TRY(hipMemcpy(b->pub.p, pub, K * ag.total_inputs * 32, hipMemcpyHostToDevice));
+    if (extra_len) HIP_TRY(hipMemcpy(b->extra.p, extra, extra_len, hipMemcpyHostToDevice));
+    if (extra_ranges) HIP_TRY(hipMemcpy(b->extra_range.p, extra_ranges, K * 16, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->col_off.p, col_off.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->col_fld.p, col_fld.data(), (size_t)np * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->pos_tab.p, pos_tab.data(), pos_tab.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b->err.p, 0xFF, 8));
+    for (uint32_t j = 0; j < m; j++) {                                // per POSITION: a repeated key repeats its block, its script and its k
+        const Verifier& v = *vs[j];
+        HIP_TRY(hipMemcpyAsync(b->bases.as<uint8_t>() + (size_t)j * nkey1 * pt_bytes, v.key_xy.p, nkey1 * pt_bytes, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(b->inf.as<uint32_t>() + (size_t)j * nkey1, v.key_inf.p, nkey1 * 4, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(b->script.as<uint8_t>() + pos_tab[3 * j], v.script.p, v.script_len, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(b->k_mont.as<uint8_t>() + (size_t)j * W * 32, v.k_mont.p, (size_t)W * 32, hipMemcpyDeviceToDevice, nullptr));
+    }
+    HIP_TRY(hipMemcpyAsync(b->bases.as<uint8_t>() + (size_t)(nkey - 1) * pt_bytes, v0.key_xy.as<uint8_t>() + (size_t)nkey1 * pt_bytes, pt_bytes, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(b->inf.as<uint32_t>() + (nkey - 1), v0.key_inf.as<uint32_t>() + nkey1, 4, hipMemcpyDeviceToDevice, nullptr));
+    unsigned long long* err = b->err.as<unsigned long long>();
+    uint32_t* bases = b->bases.as<uint32_t>() + (size_t)nkey * 2 * fqw;
+    uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
+    const bool validate = flags & MZK_SER_VALIDATE;
+    if (curve == MZK_CURVE_BLS12_381) launch_agg_decode<BlsFqX>(ag.compressed, validate, b->images.as<uint8_t>(), K, ag, *b, bases, b->inf.as<uint32_t>() + nkey, err);
+    else launch_agg_decode<BnFqX>(ag.compressed, validate, b->images.as<uint8_t>(), K, ag, *b, bases, b->inf.as<uint32_t>() + nkey, err);
+    HIP_TRY(hipGetLastError());
+    if (challenges) {
+        HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
+    } else {
+        const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+        const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
+        if (curve == MZK_CURVE_BLS12_381)
+            hipLaunchKernelGGL((vfy_agg_transcript_kernel<BlsFr, BlsFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, ag, b->script.as<uint8_t>(),
+                               b->pos_tab.as<uint32_t>(), b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>());
+        else
+            hipLaunchKernelGGL((vfy_agg_transcript_kernel<BnFr, BnFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, ag, b->script.as<uint8_t>(),
+                               b->pos_tab.as<uint32_t>(), b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    if (curve == MZK_CURVE_BLS12_381) launch_agg_scalars<BlsFr>(*b, K, ag, proof_rows, err);
+    else launch_agg_scalars<BnFr>(*b, K, ag, proof_rows, err);
+    HIP_TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));                             // (synchronises the stages)
+    if (bad != ~0ull) {
+        const uint64_t i = bad >> 40;
+        const uint32_t inst = (uint32_t)(bad >> 33) & 0x7F, field = (uint32_t)(bad >> 4) & 0x1FFFFFFF, reason = (uint32_t)bad & 0xF;
+        if (out_bad) *out_bad = i;
+        set_error("proof " + std::to_string(i) + ": instance " + std::to_string(inst) + ": " + agg_field_name(ag, inst, field) + ": " + reason_text(reason));
+        return MZK_ERR_ENCODING;
+    }
+    if (out_u) HIP_TRY(hipMemcpy2D(out_u, 32, b->chal.as<uint8_t>() + 6 * 32, 7 * 32, 32, K, hipMemcpyDeviceToHost));
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    *out_batch = handle_make(v0.device, g_next_batch++);
+    g_batches[*out_batch] = std::move(b);
     return MZK_OK;
 }
 
@@ -423,7 +715,7 @@ extern "C" int32_t mzk_verifier_destroy(uint64_t verifier) {
     auto it = g_verifiers.find(verifier);
     if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
     for (const auto& kv : g_batches)
-        if (kv.second->v == it->second) { set_error("the verifier has an open batch"); return MZK_ERR_INVALID_ARG; }
+        if (kv.second->holds(it->second)) { set_error("the verifier has an open batch"); return MZK_ERR_INVALID_ARG; }
     v = std::move(it->second);
     g_verifiers.erase(it);
     return MZK_OK;
@@ -452,6 +744,57 @@ extern "C" int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* pr
     return batch_begin(v, proofs, proof_len, K, public_inputs_canonical, extra_msgs, extra_ranges, challenges_mont, flags, out_batch, out_u_mont, out_bad_index);
 }
 
+extern "C" int32_t mzk_batch_proof_layout(int32_t curve_id, uint32_t ultra, uint32_t m, uint32_t flags, const uint8_t* image, uint64_t len,
+                                          mzk_batch_proof_layout_t* out) {
+    if (!valid_curve(curve_id) || ultra > 1 || !out || !m) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (m > MZK_VERIFIER_MAX_INSTANCES) { set_error("more than " + std::to_string(MZK_VERIFIER_MAX_INSTANCES) + " instances in one aggregate"); return MZK_ERR_UNSUPPORTED; }
+    batch_proof_layout(g1_bytes(curve_id, flags & MZK_SER_COMPRESSED), ultra, m, *out);
+    if (!image) return MZK_OK;
+    std::string why;
+    uint32_t inst;
+    if (batch_proof_container_ok(*out, image, len, inst, why)) return MZK_OK;
+    set_error("instance " + std::to_string(inst) + ": " + why);
+    return MZK_ERR_ENCODING;
+}
+
+extern "C" int32_t mzk_verifier_aggregate_shape(const uint64_t* verifiers, uint32_t m, uint32_t* out_n_proof_points, uint32_t* out_n_key_bases,
+                                                uint64_t* out_proof_len, uint64_t* out_num_inputs) {
+    MZK_TRY(tuple_args(verifiers, m));
+    VfyAggShape ag;
+    mzk_batch_proof_layout_t L;
+    {
+        std::lock_guard<std::mutex> lk(g_vfy_lock);                   // host-only, no device bound: the references (declared after the lock) are dropped
+        std::vector<std::shared_ptr<Verifier>> vs;                    // before the lock is, while the registry holds its own: never the last holder
+        for (uint32_t j = 0; j < m; j++) {
+            auto it = g_verifiers.find(verifiers[j]);
+            if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
+            vs.push_back(it->second);
+        }
+        MZK_TRY(tuple_shape(vs, ag, L));
+    }
+    if (out_n_proof_points) *out_n_proof_points = ag.np;
+    if (out_n_key_bases) *out_n_key_bases = ag.nkey;
+    if (out_proof_len) *out_proof_len = ag.proof_len;
+    if (out_num_inputs) *out_num_inputs = ag.total_inputs;
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_verifier_aggregate_begin(const uint64_t* verifiers, uint32_t m, const uint8_t* proofs, uint64_t proof_len, uint64_t K,
+                                                const uint64_t* public_inputs_canonical, const uint8_t* extra_msgs, const uint64_t* extra_ranges,
+                                                const uint64_t* challenges_mont, uint32_t flags, uint64_t* out_batch, uint64_t* out_u_mont,
+                                                uint64_t* out_bad_index) {
+    MZK_TRY(tuple_args(verifiers, m));
+    DeviceGuard guard(handle_ctx(verifiers[0]));                      // the tuple's device (tuple_shape refuses a verifier of another)
+    MZK_TRY(guard_status(guard));
+    std::vector<std::shared_ptr<Verifier>> vs;                        // declared after the guard: a last reference drops while that device is bound
+    MZK_TRY(find_tuple(verifiers, m, vs));
+    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (flags & ~MZK_SER_VALIDATE)) {
+        set_error("bad argument");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return aggregate_begin(vs, proofs, proof_len, K, public_inputs_canonical, extra_msgs, extra_ranges, challenges_mont, flags, out_batch, out_u_mont, out_bad_index);
+}
+
 extern "C" int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out) {
     ON_DEVICE_OF(batch, b, find_batch);
     if (!out) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
@@ -460,9 +803,8 @@ extern "C" int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out) 
 
 extern "C" int32_t mzk_verifier_batch_scalars(uint64_t batch, uint64_t* out_key_rows, uint64_t* out_proof_rows, uint64_t* out_evals) {
     ON_DEVICE_OF(batch, b, find_batch);
-    const VfyShape& sh = b->v->sh;
-    if (out_key_rows) HIP_TRY(hipMemcpy(out_key_rows, b->key_rows.p, b->K * sh.nkey * 32, hipMemcpyDeviceToHost));
-    if (out_proof_rows) HIP_TRY(hipMemcpy(out_proof_rows, b->b_scal.as<uint8_t>() + (size_t)sh.nkey * 32, b->K * sh.np * 32, hipMemcpyDeviceToHost));
+    if (out_key_rows) HIP_TRY(hipMemcpy(out_key_rows, b->key_rows.p, b->K * b->nkey * 32, hipMemcpyDeviceToHost));
+    if (out_proof_rows) HIP_TRY(hipMemcpy(out_proof_rows, b->b_scal.as<uint8_t>() + (size_t)b->nkey * 32, b->K * b->np * 32, hipMemcpyDeviceToHost));
     if (out_evals) HIP_TRY(hipMemcpy(out_evals, b->evals.p, b->K * 32, hipMemcpyDeviceToHost));
     return MZK_OK;
 }

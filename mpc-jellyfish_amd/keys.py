@@ -106,12 +106,31 @@ class ProofEncodingError(SerializationError):
     """A proof that ark-serialize or the verifier's range checks would refuse (MZK_ERR_ENCODING).  .index: the lowest bad proof of the batch;
     .field: the field of the `Proof` ("wires_poly_comms[2]", "wires_evals[0]", "length", ..); .reason: the library's text."""
 
-    def __init__(self, reason: str, index: int, field: str | None):
+    def __init__(self, reason: str, index: int, field: str | None, instance: int | None = None):
         ValueError.__init__(self, reason)
         self.index, self.field, self.reason = index, field, reason
+        self.instance = instance                                       # of a BatchProof: the instance the field is in (m: the whole proof's)
 
 
 _PROOF_MSG = re.compile(r"^proof (\d+): ([^:]+): ")
+_BATCH_PROOF_MSG = re.compile(r"^(?:proof (\d+): )?instance (\d+): ([^:]+): ")
+
+
+def _begin_arrays(proofs, flat_inputs, extra_msgs, challenges):
+    """what a begin call takes: the K images back to back, the public inputs as canonical limbs (None without any), the extra messages as one
+    blob with K (begin, end) ranges (None when no proof has one) and the challenges as (K, 7, 4)"""
+    K = len(proofs)
+    images = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8)
+    pub = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in flat_inputs), dtype=np.uint64) if flat_inputs else None
+    extra = ranges = None
+    if extra_msgs is not None and any(m is not None for m in extra_msgs):
+        blob, r = b"", []
+        for m in extra_msgs:
+            r += [2**64 - 1, 0] if m is None else [len(blob), len(blob) + len(m)]
+            blob += b"" if m is None else bytes(m)
+        extra, ranges = np.frombuffer(blob + b"\0", dtype=np.uint8), np.array(r, dtype=np.uint64)
+    ch = None if challenges is None else np.ascontiguousarray(challenges, dtype=np.uint64).reshape(K, 7, 4)
+    return images, pub, extra, ranges, ch
 
 
 class Verifier:
@@ -147,16 +166,7 @@ class Verifier:
         for pi in public_inputs:
             if len(pi) != self.num_inputs:
                 raise ValueError("the circuit public input length != the verification key public input length")   # verifier.rs:99-108
-        images = np.frombuffer(b"".join(bytes(p) for p in proofs), dtype=np.uint8)
-        pub = np.frombuffer(b"".join(int(x).to_bytes(32, "little") for pi in public_inputs for x in pi), dtype=np.uint64) if self.num_inputs else None
-        extra = ranges = None
-        if extra_msgs is not None and any(m is not None for m in extra_msgs):
-            blob, r = b"", []
-            for m in extra_msgs:
-                r += [2**64 - 1, 0] if m is None else [len(blob), len(blob) + len(m)]
-                blob += b"" if m is None else bytes(m)
-            extra, ranges = np.frombuffer(blob + b"\0", dtype=np.uint8), np.array(r, dtype=np.uint64)
-        ch = None if challenges is None else np.ascontiguousarray(challenges, dtype=np.uint64).reshape(K, 7, 4)
+        images, pub, extra, ranges, ch = _begin_arrays(proofs, [x for pi in public_inputs for x in pi], extra_msgs, challenges)
         ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
         batch, bad = C.c_uint64(), C.c_uint64()
         u = np.zeros((K, 4), dtype=np.uint64)
@@ -216,6 +226,92 @@ class VerifierBatch:
         if self.handle:
             h, self.handle = self.handle, 0
             _lib.check(_lib.load().mzk_verifier_batch_finish(h, None, None, None), "mzk_verifier_batch_finish")
+
+
+def batch_proof_layout(curve, ultra: bool, m: int, compress: bool = True, image=None) -> _lib.BatchProofLayout:
+    """mzk_batch_proof_layout: the length and the offset of every record of a BatchProof image of m instances.  Host-only.  With `image` its
+    container (length, Vec counts, Option tags) is checked too: ProofEncodingError with .instance and .field."""
+    c = _curve(curve)
+    L = _lib.load()
+    out = _lib.BatchProofLayout()
+    buf = None if image is None else np.frombuffer(bytes(image) + b"\0", dtype=np.uint8)
+    rc = L.mzk_batch_proof_layout(c.curve_id, int(bool(ultra)), m, _SER_COMPRESSED if compress else 0, None if buf is None else C.c_void_p(buf.ctypes.data),
+                                  0 if buf is None else buf.shape[0] - 1, C.byref(out))
+    if rc == _ERR_ENCODING:
+        msg = L.mzk_last_error().decode()
+        mt = _BATCH_PROOF_MSG.match(msg)
+        raise ProofEncodingError(msg, 0, mt.group(3) if mt else None, int(mt.group(2)) if mt else None)
+    _lib.check(rc, "mzk_batch_proof_layout")
+    return out
+
+
+class AggregateVerifier:
+    """mzk_verifier_aggregate_*: `BatchProof`s of m instances under the tuple `vks` of m VerifyingKeys (one key may stand at several
+    positions: a circuit and its forks).  begin() runs the per-proof stages of K BatchProofs and returns an ordinary VerifierBatch; the
+    verifiers are the keys' own (VerifyingKey.verifier()), so release() has nothing of its own to free but the keys' verifiers on request."""
+
+    def __init__(self, vks, validate: bool = True):
+        vks = list(vks)
+        if not vks:
+            raise ValueError("the number of verification keys / instances / public inputs differ, or no key")           # verifier.rs:77-86
+        open_key = (vks[0].g, vks[0].h, vks[0].beta_h, vks[0].compressed)
+        for i, vk in enumerate(vks):
+            if (vk.g, vk.h, vk.beta_h, vk.compressed) != open_key:
+                raise ValueError("the verification keys have different open keys")                                      # snark.rs:160-166
+            if vk.domain_size != vks[0].domain_size:
+                raise ValueError("the domain size of the %d-th verification key is different" % i)                      # verifier.rs:88-97
+        self.vks, self.curve, self.m = vks, vks[0].curve, len(vks)
+        self.verifiers = [vk.verifier(validate) for vk in vks]
+        self.handles = (C.c_uint64 * self.m)(*[v.handle for v in self.verifiers])
+        np_, nkey, plen, nin = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _lib.check(_lib.load().mzk_verifier_aggregate_shape(self.handles, self.m, C.byref(np_), C.byref(nkey), C.byref(plen), C.byref(nin)),
+                   "mzk_verifier_aggregate_shape")
+        self.n_proof_points, self.n_key_bases, self.proof_len, self.num_inputs = np_.value, nkey.value, plen.value, nin.value
+
+    @property
+    def shape(self):
+        """(points per BatchProof, key bases of the tuple, image length, public inputs per proof)"""
+        return self.n_proof_points, self.n_key_bases, self.proof_len, self.num_inputs
+
+    def begin(self, batch_proofs, public_inputs, extra_msgs=None, challenges=None, validate: bool = True) -> "VerifierBatch":
+        """mzk_verifier_aggregate_begin.  batch_proofs: K images; public_inputs: per proof a list of m lists of canonical integers, in tuple
+        order; extra_msgs / challenges as for Verifier.begin.  Raises ProofEncodingError naming the lowest bad proof, its lowest instance
+        (.instance; m: the whole proof's) and the field."""
+        L = _lib.load()
+        K = len(batch_proofs)
+        if K == 0 or len(public_inputs) != K or (extra_msgs is not None and len(extra_msgs) != K):
+            raise ValueError("the number of proofs / public inputs / extra messages differ, or no proof")
+        for i, p in enumerate(batch_proofs):
+            if len(p) != self.proof_len:
+                raise ProofEncodingError(f"proof {i}: instance {self.m}: length: {len(p)} bytes, expected {self.proof_len} under these keys", i, "length", self.m)
+        for pubs in public_inputs:
+            if len(pubs) != self.m:
+                raise ValueError("the number of verification keys / instances / public inputs differ")                  # verifier.rs:77-86
+            for j, (pi, vk) in enumerate(zip(pubs, self.vks)):
+                if len(pi) != vk.num_inputs:
+                    raise ValueError("the circuit public input length != the %d-th verification key public input length" % j)   # verifier.rs:99-108
+        images, pub, extra, ranges, ch = _begin_arrays(batch_proofs, [x for pubs in public_inputs for pi in pubs for x in pi], extra_msgs, challenges)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+        batch, bad = C.c_uint64(), C.c_uint64()
+        u = np.zeros((K, 4), dtype=np.uint64)
+        rc = L.mzk_verifier_aggregate_begin(self.handles, self.m, ptr(images), self.proof_len, K, ptr(pub), ptr(extra), ptr(ranges), ptr(ch),
+                                            _SER_VALIDATE if validate else 0, C.byref(batch), ptr(u), C.byref(bad))
+        if rc == _ERR_ENCODING:
+            msg = L.mzk_last_error().decode()
+            mt = _BATCH_PROOF_MSG.match(msg)
+            raise ProofEncodingError(msg, bad.value, mt.group(3) if mt else None, int(mt.group(2)) if mt else None)
+        _lib.check(rc, "mzk_verifier_aggregate_begin")
+        return VerifierBatch(self, batch.value, K, u)
+
+    def check(self, A_xyz, B_xyz) -> bool:
+        """mzk_verifier_check with the tuple's open key (any group under the same open key may be among the summands)"""
+        return self.verifiers[0].check(A_xyz, B_xyz)
+
+    def release(self):
+        """frees the verifiers of the tuple's keys (VerifyingKey.release_verifier of each)"""
+        for vk in self.vks:
+            vk.release_verifier()
+        self.verifiers = []
 
 
 class ProvingKey:

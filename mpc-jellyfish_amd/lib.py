@@ -37,6 +37,17 @@ class KeyLayout(C.Structure):
                 ("beta_h_off", C.c_uint64), ("plookup_comms_off", C.c_uint64), ("total_len", C.c_uint64)]
 
 
+MAX_INSTANCES = 64                     # MZK_VERIFIER_MAX_INSTANCES
+
+
+class BatchProofLayout(C.Structure):
+    """mzk_batch_proof_layout_t (include/mzk.h)"""
+    _fields_ = [("m", C.c_uint32), ("num_wire_types", C.c_uint32), ("ultra", C.c_uint32), ("g1_record_bytes", C.c_uint32), ("total_len", C.c_uint64)] + \
+               [(name, C.c_uint64 * MAX_INSTANCES) for name in ("wires_off", "prod_perm_off", "wires_evals_off", "sigma_evals_off", "perm_next_off",
+                                                                "plookup_tag_off", "h_off", "prod_lookup_off", "plookup_evals_off")] + \
+               [("split_quot_off", C.c_uint64), ("opening_off", C.c_uint64), ("shifted_opening_off", C.c_uint64)]
+
+
 _SIGS = {
     "mzk_init": [C.c_int32],
     "mzk_set_device": [C.c_int32],
@@ -72,6 +83,11 @@ _SIGS = {
     "mzk_verifier_batch_scalars": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_verifier_batch_finish": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_verifier_check": [C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)],
+    "mzk_batch_proof_layout": [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(BatchProofLayout)],
+    "mzk_verifier_aggregate_shape": [C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint64)],
+    "mzk_verifier_aggregate_begin": [C.POINTER(C.c_uint64), C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)],
     "mzk_srs_register_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_srs_register_serialized_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_srs_serialize": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p],

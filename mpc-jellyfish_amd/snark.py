@@ -370,6 +370,40 @@ def batch_verify(vks, public_inputs, proofs, extra_msgs) -> bool:
     return vks[0].verifier().check(np.stack([a for a, _ in results]), np.stack([b for _, b in results]))
 
 
+def batch_verify_batch_proofs(vks, public_inputs_list, batch_proofs, extra_msgs) -> bool:
+    """K aggregated `BatchProof`s under ONE tuple of keys.VerifyingKey in one pass over the device (keys.AggregateVerifier.begin):
+    public_inputs_list holds, per proof, the instances' public inputs in tuple order; extra_msgs one Optional[bytes] per proof.  r is drawn
+    from the proofs' u as batch_verify draws it (1 for one proof) and the pairing check is one.  Raises ValueError on mismatched lengths, an
+    empty tuple, differing open keys or domain sizes and a public-input length that is not the key's num_inputs; keys.ProofEncodingError
+    on a malformed image."""
+    from . import keys as _keys, lib as _lib
+    import ctypes as C
+    K = len(batch_proofs)
+    if not (len(public_inputs_list) == K == len(extra_msgs)):
+        raise ValueError("the number of public inputs / proofs / extra messages differ")
+    if K == 0:
+        raise ValueError("no proof to verify")
+    agg = _keys.AggregateVerifier(vks)
+    c = agg.curve
+    b = agg.begin(batch_proofs, public_inputs_list, extra_msgs)
+    try:
+        r = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.load().mzk_batch_verify_challenge(c.curve_id, C.c_void_p(b.u.ctypes.data), K, C.c_void_p(r.ctypes.data)), "mzk_batch_verify_challenge")
+        r_int = fr_from_mont(c, r.reshape(1, 4))[0]
+        A, B = b.finish(fr_to_mont(c, [pow(r_int, i, c.r) for i in range(K)]))
+    finally:
+        b.discard()
+    return agg.check(A, B)
+
+
+def verify_batch_proof(vks, public_inputs, batch_proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None) -> bool:
+    """PlonkKzgSnark::verify_batch_proof (snark.rs:117-138): one aggregated proof of len(vks) instances, public_inputs one list per instance
+    (r = 1).  The reference's own entry point passes no extra message; batch_prove takes one, so it can be stated here."""
+    if len(vks) != len(public_inputs):
+        raise ValueError("the number of verification keys / instances / public inputs differ")                              # verifier.rs:77-86
+    return batch_verify_batch_proofs(vks, [public_inputs], [batch_proof_bytes], [extra_transcript_init_msg])
+
+
 def verify(vk, public_input, proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None) -> bool:
     """PlonkKzgSnark::verify (snark.rs:653-671): batch_verify of one proof (r = 1)."""
     return batch_verify([vk], [public_input], [proof_bytes], [extra_transcript_init_msg])
