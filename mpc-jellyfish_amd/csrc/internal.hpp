@@ -105,7 +105,7 @@ struct Srs {
     int curve = 0;
     uint64_t n = 0;
     uint32_t* d_xy = nullptr;   // n * 2 * fq words, boundary form (what mzk_srs_download returns)
-    uint32_t* d_int = nullptr;  // internal reduced-radix table used by the MSM (29-bit limbs, R'-Montgomery form: ecx.cuh)
+    uint32_t* d_int = nullptr;  // internal reduced-radix table used by the MSM (R'-Montgomery form; BLS12-381: 13 signed 30-bit limbs in 14-word slots, ecz.cuh; BN254: 29-bit limbs, ecx.cuh)
     uint32_t* d_pre = nullptr;  // [W][n] precomputed multiples 2^(c*w) P_i (msm_pre.cuh), built on first large MSM
     int pre_c = 0;              // window bits of d_pre; -1 = do not build
     int pre_levels = 0;         // W: levels of d_pre
@@ -115,7 +115,7 @@ struct Srs {
 inline bool valid_curve(int curve) { return curve == MZK_CURVE_BLS12_381 || curve == MZK_CURVE_BN254; }
 inline int fq_words(int curve) { return curve == MZK_CURVE_BLS12_381 ? 12 : 8; }
 inline size_t srs_point_bytes(int curve) { return (size_t)2 * fq_words(curve) * 4; }                            // boundary form (d_xy)
-constexpr size_t srs_int_point_bytes(int curve) { return curve == MZK_CURVE_BLS12_381 ? 2 * 14 * 4 : 2 * 9 * 4; }  // internal form (d_int, d_pre): pinned to EcFx::AFF_WORDS in msm.hip
+constexpr size_t srs_int_point_bytes(int curve) { return curve == MZK_CURVE_BLS12_381 ? 2 * 14 * 4 : 2 * 9 * 4; }  // internal form (d_int, d_pre): pinned to EcFz / EcFx::AFF_WORDS in msm.hip
 
 // ---- device contexts ---------------------------------------------------------------------------------
 // One context per LOGICAL device: the HIP device it runs on, its lock, workspace, I/O slots, SRS registry; the NTT plan cache,

@@ -22,6 +22,7 @@
 
 #include "ec.cuh"
 #include "ecx.cuh"
+#include "ecz.cuh"
 
 namespace mzk {
 
@@ -303,7 +304,8 @@ __device__ __forceinline__ void store_xyzz(uint32_t* __restrict__ buf, unsigned 
 // The bucket kernels are written once against a small policy.  EcFx keeps points in the reduced-radix form of
 // fx.cuh / ecx.cuh (one v_mad_u64_u32 per partial product and carry-free additions; 14 limbs for BLS12-381 Fq, 10 for
 // BN254 Fq), with the SRS converted once at registration and results converted back when they are collected: it is
-// what the library runs.  EcFp keeps points in the boundary's 32-bit-limb Montgomery form; it stays as the baseline
+// what the library runs for BN254; BLS12-381 runs EcFz, the same policy on the signed 13 x 30-bit limbs of fz.cuh / ecz.cuh (338 instead
+// of 392 multiply-adds per product, no subtraction pads) with the memory strides of the 14-limb form.  EcFp keeps points in the boundary's 32-bit-limb Montgomery form; it stays as the baseline
 // that tools/madd_bench.hip compares against.
 template <class FQ>
 struct EcFp {
@@ -337,7 +339,9 @@ struct EcFx {
     using Field = X;
     using Aff = AffineX<X>;
     using Pt = XYZZX<X>;
-    static constexpr int AFF_WORDS = 2 * X::XN, PT_WORDS = 4 * X::XN;      // BLS12-381: 28 / 56 words; BN254: 18 / 36
+    using Fe = Fx<X>;
+    static constexpr int LIMBS = X::XN, SLOT_WORDS = X::XN;                // limbs of a coordinate / words between coordinates in memory
+    static constexpr int AFF_WORDS = 2 * X::XN, PT_WORDS = 4 * X::XN;      // BN254: 18 / 36 words
     static_assert((4 * X::XN) % 4 == 0 && (2 * X::XN) % 2 == 0, "points are whole 16-byte / 8-byte words");
     static __device__ __forceinline__ Aff load_aff(const uint32_t* __restrict__ bases, unsigned long long idx) {
         uint32_t w[AFF_WORDS];
@@ -390,7 +394,90 @@ struct EcFx {
     static __device__ __forceinline__ Pt madd(const Pt& a, const Aff& q, bool negate) { return xyzzx_madd(a, q, negate); }
     static __device__ __forceinline__ Pt add(const Pt& a, const Pt& b) { return xyzzx_add(a, b); }
     static __device__ __forceinline__ XYZZ<Fp<X>> to_boundary(const Pt& p) { return xyzzx_to_boundary(p); }
+    static __device__ __forceinline__ Fe add_quad(const Fe& ca, const Fe& cb, int role) { return xyzzx_add_quad<X>(ca, cb, role); }
 };
+
+// EcFz: the signed 30-bit-limb form (fz.cuh / ecz.cuh; BLS12-381 Fq on 13 limbs).  The memory layout keeps the strides of the 14-limb
+// form it replaced -- 14 words per coordinate, 28 per affine point, 56 per accumulator, so every workspace and table size and the
+// 16-byte alignment of a point stay what they were --; word 13 of a coordinate is written as zero and never looked at.
+template <class Z>
+struct EcFz {
+    using Field = Z;
+    using Aff = AffineZ<Z>;
+    using Pt = XYZZZ<Z>;
+    using Fe = Fz<Z>;
+    static constexpr int LIMBS = Z::ZN, SLOT_WORDS = Z::ZN + 1;
+    static constexpr int AFF_WORDS = 2 * SLOT_WORDS, PT_WORDS = 4 * SLOT_WORDS;      // 28 / 56 words
+    static_assert(AFF_WORDS % 4 == 0, "points are whole 16-byte words");
+    static __device__ __forceinline__ Aff load_aff(const uint32_t* __restrict__ bases, unsigned long long idx) {
+        uint32_t w[AFF_WORDS];
+        const uint4* src = reinterpret_cast<const uint4*>(bases + idx * AFF_WORDS);
+#pragma unroll
+        for (int i = 0; i < AFF_WORDS / 4; i++) {
+            const uint4 v = src[i];
+            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+        Aff p;
+#pragma unroll
+        for (int i = 0; i < LIMBS; i++) { p.x.l[i] = (int32_t)w[i]; p.y.l[i] = (int32_t)w[SLOT_WORDS + i]; }
+        return p;
+    }
+    static __device__ __forceinline__ void store_aff(uint32_t* __restrict__ bases, unsigned long long idx, const Aff& p) {
+        uint32_t w[AFF_WORDS];
+#pragma unroll
+        for (int i = 0; i < LIMBS; i++) { w[i] = (uint32_t)p.x.l[i]; w[SLOT_WORDS + i] = (uint32_t)p.y.l[i]; }
+        w[LIMBS] = 0; w[SLOT_WORDS + LIMBS] = 0;
+        uint4* dst = reinterpret_cast<uint4*>(bases + idx * AFF_WORDS);
+#pragma unroll
+        for (int i = 0; i < AFF_WORDS / 4; i++) dst[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    }
+    static __device__ __forceinline__ Pt load_pt(const uint32_t* __restrict__ buf, unsigned long long idx) {
+        uint32_t w[PT_WORDS];
+        const uint4* src = reinterpret_cast<const uint4*>(buf + idx * PT_WORDS);
+#pragma unroll
+        for (int i = 0; i < PT_WORDS / 4; i++) {
+            const uint4 v = src[i];
+            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+        Pt p;
+#pragma unroll
+        for (int i = 0; i < LIMBS; i++) {
+            p.x.l[i] = (int32_t)w[i]; p.y.l[i] = (int32_t)w[SLOT_WORDS + i];
+            p.zz.l[i] = (int32_t)w[2 * SLOT_WORDS + i]; p.zzz.l[i] = (int32_t)w[3 * SLOT_WORDS + i];
+        }
+        return p;
+    }
+    static __device__ __forceinline__ void store_pt(uint32_t* __restrict__ buf, unsigned long long idx, const Pt& p) {
+        uint32_t w[PT_WORDS];
+#pragma unroll
+        for (int i = 0; i < LIMBS; i++) {
+            w[i] = (uint32_t)p.x.l[i]; w[SLOT_WORDS + i] = (uint32_t)p.y.l[i];
+            w[2 * SLOT_WORDS + i] = (uint32_t)p.zz.l[i]; w[3 * SLOT_WORDS + i] = (uint32_t)p.zzz.l[i];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k * SLOT_WORDS + LIMBS] = 0;
+        uint4* dst = reinterpret_cast<uint4*>(buf + idx * PT_WORDS);
+#pragma unroll
+        for (int i = 0; i < PT_WORDS / 4; i++) dst[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    }
+    static __device__ __forceinline__ Pt inf() { return Pt::inf(); }
+    static __device__ __forceinline__ Pt madd(const Pt& a, const Aff& q, bool negate) { return xyzzz_madd(a, q, negate); }
+    static __device__ __forceinline__ Pt add(const Pt& a, const Pt& b) { return xyzzz_add(a, b); }
+    static __device__ __forceinline__ XYZZ<Fp<Z>> to_boundary(const Pt& p) { return xyzzz_to_boundary(p); }
+    static __device__ __forceinline__ Fe add_quad(const Fe& ca, const Fe& cb, int role) { return xyzzz_add_quad<Z>(ca, cb, role); }
+};
+
+// boundary SRS (packed x||y, R-form) -> internal affine table of EcFz (x||y, class M, R'-form); (0, 0) stays (0, 0)
+template <class Z>
+__global__ __launch_bounds__(MSM_THREADS) void srs_to_internal_z_kernel(const uint32_t* __restrict__ xy, unsigned long long n, uint32_t* __restrict__ out) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * MSM_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const Fp<Z> x = load_fp<Z>(xy + i * 2 * Z::N), y = load_fp<Z>(xy + i * 2 * Z::N + Z::N);
+    AffineZ<Z> p;
+    p.x = fz_from_boundary<Z>(x);
+    p.y = fz_from_boundary<Z>(y);
+    EcFz<Z>::store_aff(out, i, p);
+}
 
 // boundary SRS (packed x||y, R-form) -> internal affine table of EcFx (x||y, 29-bit limbs, R'-form)
 template <class X>
@@ -487,7 +574,7 @@ __global__ __launch_bounds__(MSM_ACC_THREADS) void msm_accumulate_split_kernel(c
 // (word-major, so lanes touch consecutive banks) -- the active lanes stay dense and idle waves skip the addition altogether.
 template <class EC>
 __device__ __forceinline__ void pt_lds_put(uint32_t* lds, int slot, const typename EC::Pt& p) {
-    constexpr int N = EC::Field::XN;
+    constexpr int N = EC::LIMBS;
 #pragma unroll
     for (int i = 0; i < N; i++) {
         lds[i * MSM_ACC_THREADS + slot] = p.x.l[i];
@@ -498,7 +585,7 @@ __device__ __forceinline__ void pt_lds_put(uint32_t* lds, int slot, const typena
 }
 template <class EC>
 __device__ __forceinline__ typename EC::Pt pt_lds_get(const uint32_t* lds, int slot) {
-    constexpr int N = EC::Field::XN;
+    constexpr int N = EC::LIMBS;
     typename EC::Pt p;
 #pragma unroll
     for (int i = 0; i < N; i++) {
@@ -909,12 +996,12 @@ __global__ __launch_bounds__(256) void msm_fold_tail_kernel(uint32_t* __restrict
 // and a quad finishes one in four product latencies instead of fourteen.
 template <class EC>
 __device__ __forceinline__ void fold_one_quad(uint32_t* buckets, uint8_t* occ, unsigned long long ia, unsigned long long ib, int role) {
-    using X = typename EC::Field;
-    constexpr int XN = X::XN;
+    using Fe = typename EC::Fe;
+    constexpr int XN = EC::LIMBS, SLOT = EC::SLOT_WORDS;
     if (!occ[ib]) return;                                                 // (quad-uniform, as every branch below)
-    uint32_t* pa = buckets + ia * EC::PT_WORDS + role * XN;
-    const uint32_t* pb = buckets + ib * EC::PT_WORDS + role * XN;
-    Fx<X> cb;
+    uint32_t* pa = buckets + ia * EC::PT_WORDS + role * SLOT;
+    const uint32_t* pb = buckets + ib * EC::PT_WORDS + role * SLOT;
+    Fe cb;
 #pragma unroll
     for (int i = 0; i < XN; i++) cb.l[i] = pb[i];
     if (!occ[ia]) {
@@ -923,10 +1010,10 @@ __device__ __forceinline__ void fold_one_quad(uint32_t* buckets, uint8_t* occ, u
         occ[ia] = 1;                                                      // every lane of the quad: each then re-reads what IT wrote (msm_fold2_quad_kernel reads it again without a barrier)
         return;
     }
-    Fx<X> ca;
+    Fe ca;
 #pragma unroll
     for (int i = 0; i < XN; i++) ca.l[i] = pa[i];
-    const Fx<X> r = xyzzx_add_quad<X>(ca, cb, role);
+    const Fe r = EC::add_quad(ca, cb, role);
 #pragma unroll
     for (int i = 0; i < XN; i++) pa[i] = r.l[i];
 }

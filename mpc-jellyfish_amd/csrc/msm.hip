@@ -629,9 +629,8 @@ int32_t msm_batch_dev(const MsmItem* items, int count, int is_mont, const PreInf
 }
 
 // table[w][i] = 2^(c*w) * P_i for every SRS point (msm_pre.cuh)
-template <class X>
-int32_t srs_build_pre_t(Srs& s, hipStream_t st) {
-    using EC = EcFx<X>;
+template <class EC>
+int32_t srs_build_pre_t(Srs& s, hipStream_t st, void (*next_level)(const uint32_t*, uint32_t*, unsigned long long, int)) {
     int lg = 0;
     while ((2ull << lg) <= s.n) lg++;
     // Window size of the table.  Only sizes whose TOP digit still spans many buckets are eligible: with all windows sharing
@@ -661,7 +660,7 @@ int32_t srs_build_pre_t(Srs& s, hipStream_t st) {
     HIP_TRY(hipMemcpyAsync(s.d_pre, s.d_int, level * 4, hipMemcpyDeviceToDevice, st));
     const unsigned long long threads = (s.n + 3) / 4;
     for (int w = 1; w < W; w++)
-        hipLaunchKernelGGL((pre_next_level_kernel<X>), dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, st,
+        hipLaunchKernelGGL(next_level, dim3((unsigned)((threads + 127) / 128)), dim3(128), 0, st,
                            s.d_pre + (size_t)(w - 1) * level, s.d_pre + (size_t)w * level, (unsigned long long)s.n, c);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -673,7 +672,8 @@ int32_t srs_build_pre_t(Srs& s, hipStream_t st) {
 }  // namespace
 int32_t srs_build_pre(Srs& s, hipStream_t st) {
     if (s.d_pre || s.pre_c < 0 || !s.d_int) return MZK_OK;
-    return s.curve == MZK_CURVE_BLS12_381 ? srs_build_pre_t<BlsFqX>(s, st) : srs_build_pre_t<BnFqX>(s, st);
+    return s.curve == MZK_CURVE_BLS12_381 ? srs_build_pre_t<EcFz<BlsFqZ>>(s, st, pre_next_level_z_kernel<BlsFqZ>)
+                                          : srs_build_pre_t<EcFx<BnFqX>>(s, st, pre_next_level_kernel<BnFqX>);
 }
 
 int32_t msm_dispatch(const Srs& s, uint64_t base_offset, const uint32_t* d_scalars, uint64_t n, int is_mont, uint32_t* out, hipStream_t st) {
@@ -684,9 +684,9 @@ int32_t msm_dispatch(const Srs& s, uint64_t base_offset, const uint32_t* d_scala
 int32_t msm_batch_dispatch(const Srs& s, uint32_t n_polys, const uint32_t* const* d_scalars, const uint64_t* lens, const uint64_t* base_offsets,
                            int is_mont, uint32_t* out_xyz, hipStream_t st) {
     const int fw = fq_words(s.curve);
-    // both curves run on the reduced-radix internal table (EcFx: 14 x 29-bit limbs for BLS12-381 Fq, 10 x 29 for BN254 Fq)
+    // both curves run on a reduced-radix internal table (EcFz: 13 signed 30-bit limbs for BLS12-381 Fq; EcFx: 9 x 29 bits for BN254 Fq)
     const bool bls = s.curve == MZK_CURVE_BLS12_381;
-    const size_t aff_words = bls ? (size_t)EcFx<BlsFqX>::AFF_WORDS : (size_t)EcFx<BnFqX>::AFF_WORDS;
+    const size_t aff_words = bls ? (size_t)EcFz<BlsFqZ>::AFF_WORDS : (size_t)EcFx<BnFqX>::AFF_WORDS;
     const uint32_t* table = s.d_int;
     if (!table) { set_error("SRS has no internal table"); return MZK_ERR_BAD_HANDLE; }
     std::vector<MsmItem> items(n_polys);
@@ -708,20 +708,19 @@ int32_t msm_batch_dispatch(const Srs& s, uint32_t n_polys, const uint32_t* const
     }
     if (pre.c)
         for (auto& it : items) it.d_bases = s.d_pre;
-    if (bls) return msm_batch_dev<BlsFr, EcFx<BlsFqX>>(items.data(), (int)n_polys, is_mont, pre, table, aff_words, st);
+    if (bls) return msm_batch_dev<BlsFr, EcFz<BlsFqZ>>(items.data(), (int)n_polys, is_mont, pre, table, aff_words, st);
     return msm_batch_dev<BnFr, EcFx<BnFqX>>(items.data(), (int)n_polys, is_mont, pre, table, aff_words, st);
 }
 
-static_assert(srs_int_point_bytes(MZK_CURVE_BLS12_381) == EcFx<BlsFqX>::AFF_WORDS * 4 && srs_int_point_bytes(MZK_CURVE_BN254) == EcFx<BnFqX>::AFF_WORDS * 4,
-              "srs_int_point_bytes (internal.hpp) is the size of an EcFx affine point");
+static_assert(srs_int_point_bytes(MZK_CURVE_BLS12_381) == EcFz<BlsFqZ>::AFF_WORDS * 4 && srs_int_point_bytes(MZK_CURVE_BN254) == EcFx<BnFqX>::AFF_WORDS * 4,
+              "srs_int_point_bytes (internal.hpp) is the size of an internal affine point");
 // builds the internal (reduced-radix) copy of a freshly registered SRS
-template <class X>
-static int32_t srs_build_internal_t(Srs& s, hipStream_t st) {
-    using EC = EcFx<X>;
+template <class EC>
+static int32_t srs_build_internal_t(Srs& s, hipStream_t st, void (*to_internal)(const uint32_t*, unsigned long long, uint32_t*)) {
     HIP_TRY(hipMalloc((void**)&s.d_int, (size_t)(s.n ? s.n : 1) * EC::AFF_WORDS * 4));
     if (s.n) {
-        hipLaunchKernelGGL((srs_to_internal_kernel<X>), dim3((unsigned)((s.n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st,
-                           s.d_xy, s.n, s.d_int);
+        hipLaunchKernelGGL(to_internal, dim3((unsigned)((s.n + MSM_THREADS - 1) / MSM_THREADS)), dim3(MSM_THREADS), 0, st,
+                           (const uint32_t*)s.d_xy, (unsigned long long)s.n, s.d_int);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -731,7 +730,8 @@ int32_t srs_build_internal(Srs& s, hipStream_t st) {
     s.d_int = nullptr;
     s.d_pre = nullptr;
     s.pre_c = 0;
-    return s.curve == MZK_CURVE_BLS12_381 ? srs_build_internal_t<BlsFqX>(s, st) : srs_build_internal_t<BnFqX>(s, st);
+    return s.curve == MZK_CURVE_BLS12_381 ? srs_build_internal_t<EcFz<BlsFqZ>>(s, st, srs_to_internal_z_kernel<BlsFqZ>)
+                                          : srs_build_internal_t<EcFx<BnFqX>>(s, st, srs_to_internal_kernel<BnFqX>);
 }
 
 namespace {

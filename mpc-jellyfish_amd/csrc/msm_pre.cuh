@@ -430,5 +430,43 @@ __global__ __launch_bounds__(128) void pre_next_level_kernel(const uint32_t* __r
         for (int k = 0; k < X::XN; k++) { dst[k] = x.l[k]; dst[X::XN + k] = y.l[k]; }
     }
 }
+// the same on the signed 30-bit-limb table of EcFz: its entries are class-M products as they come (|value| < p, (0, 0) = infinity)
+template <class Z>
+__global__ __launch_bounds__(128) void pre_next_level_z_kernel(const uint32_t* __restrict__ cur, uint32_t* __restrict__ next, unsigned long long n, int c) {
+    constexpr int B = 4;
+    using EC = EcFz<Z>;
+    const unsigned long long t = (unsigned long long)blockIdx.x * 128 + threadIdx.x;
+    const unsigned long long start = t * B;
+    if (start >= n) return;
+    XYZZZ<Z> pt[B];
+    Fz<Z> pref[B];
+    Fz<Z> run = Fz<Z>::one();
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+        XYZZZ<Z> p = XYZZZ<Z>::inf();                                // slots past the end stay out of the shared inversion
+        if (start + j < n) {
+            p = XYZZZ<Z>::from_affine(EC::load_aff(cur, start + j));
+            for (int k = 0; k < c; k++) p = xyzzz_dbl(p);
+        }
+        pt[j] = p;
+        pref[j] = run;
+        if (!p.is_inf()) run = fz_mul(run, p.zzz);                   // class M
+    }
+    Fz<Z> inv_run = fz_inv(run);
+#pragma unroll
+    for (int j = B - 1; j >= 0; j--) {
+        if (start + j >= n) continue;
+        AffineZ<Z> a;
+        a.x = Fz<Z>::zero(); a.y = Fz<Z>::zero();
+        if (!pt[j].is_inf()) {
+            const Fz<Z> zi = fz_mul(inv_run, pref[j]);               // 1 / ZZZ_j
+            inv_run = fz_mul(inv_run, pt[j].zzz);
+            const Fz<Z> zzi = fz_sqr(fz_mul(zi, pt[j].zz));          // (ZZ/ZZZ)^2 = 1/ZZ
+            a.x = fz_mul(pt[j].x, zzi);
+            a.y = fz_mul(pt[j].y, zi);
+        }
+        EC::store_aff(next, start + j, a);
+    }
+}
 
 }  // namespace mzk
