@@ -334,6 +334,50 @@ MZK_API int32_t mzk_verifier_aggregate_begin(const uint64_t* verifiers, uint32_t
                                              const uint64_t* challenges_mont, uint32_t flags, uint64_t* out_batch, uint64_t* out_u_mont,
                                              uint64_t* out_bad_index);
 
+/* ---- proof links: PlonkKzgSnark::verify_link_proof (proof_linking.rs:240-286; DESIGN.md section 4.14, "Proof links").  A link of two proofs
+ * over a GroupLayout (relation/src/proof_linking/mod.rs:16-54) is the KZG opening of a_1 - a_2 - Z_D(eta) q at eta with value 0
+ * (univariate_kzg/mod.rs:194-216): it ends in the pair A = pi, B = a_1 - a_2 - Z_D(eta) Q + eta pi.  K links go through the device in one
+ * pass and leave an ordinary batch handle, so their (A, B) sums with the (A, B) of single-proof and aggregate groups under the same open key
+ * into ONE check of two pairings.
+ *
+ * mzk_verifier_create_open_key: a verifier handle that carries an OpenKey alone -- g (G1), h, beta_h (G2) as records of the mode
+ * MZK_SER_COMPRESSED states; MZK_SER_VALIDATE adds the subgroup checks, as in mzk_verifier_create.  MZK_ERR_ENCODING: "open_key.<field>:
+ * <reason>".  The handle rules above hold for it (the device of the calling thread, destroy refused with an open batch, released by
+ * mzk_shutdown).  mzk_verifier_shape reports 0 points, 0 key bases, length 0, 0 inputs; mzk_verifier_batch_begin and _aggregate_begin (and
+ * _aggregate_shape) return MZK_ERR_INVALID_ARG, "the verifier holds no verifying key"; mzk_verifier_check works with it.
+ *
+ * mzk_verifier_link_begin: `verifier` is ANY verifier handle, a full key or an open key: its curve, device and image mode are used.
+ * records: K x 4 G1 records of that mode, per link lhs.wires_poly_comms[0] (PROOF_LINK_WIRE_IDX = 0), rhs.wires_poly_comms[0],
+ * quotient_commitment, opening_proof -- the caller cuts the first two out of the two Plonk proof images.  layouts: K x 3 values (alignment,
+ * offset, size).  eta_mont (nullable): K Montgomery Fr that REPLACE the transcript stage (the seam of challenges_mont); flags:
+ * MZK_SER_VALIDATE (subgroup checks of the records); *out_eta_mont (nullable): the K challenges.  On the host, before anything is staged:
+ * K = 0 and an alignment above the field's two-adicity (32 | 28): MZK_ERR_INVALID_ARG; a size above 2^27, the largest domain of the library:
+ * MZK_ERR_UNSUPPORTED; offset + size beyond 2^alignment is accepted -- the roots wrap or repeat, as mzk_poly_div_roots_dev and the
+ * reference's loop take them.  On the device: A decode (the decoder of the proofs), Bl the transcript "PlonkLinkingProof" (the two wire
+ * commitments under "linking_wire_comms", the quotient commitment under "quotient_comm", eta; commitments in their compressed form), Cl
+ * Z_D(eta) = prod_{i < size} (eta - g^(offset + i)), g the 2^alignment-th root of unity of the NTT, one wave per link.  Any malformed record:
+ * MZK_ERR_ENCODING, *out_bad_index (nullable) the LOWEST bad link -- one 64-bit atomicMin, the same answer on every run -- and
+ * mzk_last_error() "link <i>: <field>: <reason>", the field one of lhs.wires_poly_comms[0] | rhs.wires_poly_comms[0] | quotient_commitment |
+ * opening_proof, the reasons those of mzk_srs_register_serialized; no batch is left open then.  Infinity is flagged, not refused: two proofs
+ * of one circuit link with Q = pi = O (proof_linking.rs:124-127).
+ * The batch: mzk_verifier_batch_scalars, _finish (discard too) and mzk_verifier_check take it under their contracts above with NKEY = 1
+ * (open_key.g, scalar zero: the opened value is 0), NP = 4 with the unweighted row (1, -1, -Z_D(eta), eta), evaluation 0 and A = sum w_i
+ * pi_i.  mzk_verifier_batch_challenges: MZK_ERR_INVALID_ARG (a link has no seven challenges).
+ * mzk_verifier_link_values (each nullable): K x eta_i and K x Z_D(eta_i), Montgomery Fr.
+ * mzk_verifier_link_weights: the K weights for mzk_verifier_batch_finish.  K = 1 and r_mont NULL: exactly 1, so one link alone is the
+ * reference's check.  Otherwise (host; csrc/merlin.cuh as mzk_batch_verify_challenge uses it) a Merlin transcript "batch verify links":
+ * r_mont, when given, under "r" (32 B little-endian canonical), per link in order eta_i under "eta", per link in order the staged
+ * opening-proof record as it stands under "opening_proof", 64 challenge bytes under "s" reduced mod r; weight i = s^(i + 1).  This batching
+ * is the library's own (the reference verifies links one at a time).  The pi_i enter because eta_i binds a_1, a_2 and Q but not pi_i:
+ * weights blind to them would let two opening "proofs" be chosen jointly so that two false links cancel.  No weight is 1, and r -- the
+ * challenge of the Plonk groups checked together with the links -- is absorbed, because the first Plonk proof has weight r^0 = 1. */
+MZK_API int32_t mzk_verifier_create_open_key(int32_t curve_id, const uint8_t* g_bytes, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, uint32_t flags,
+                                             uint64_t* out_handle);
+MZK_API int32_t mzk_verifier_link_begin(uint64_t verifier, const uint8_t* records, uint64_t K, const uint64_t* layouts, const uint64_t* eta_mont, uint32_t flags,
+                                        uint64_t* out_batch, uint64_t* out_eta_mont, uint64_t* out_bad_index);
+MZK_API int32_t mzk_verifier_link_values(uint64_t batch, uint64_t* out_eta_mont, uint64_t* out_vanishing_mont);
+MZK_API int32_t mzk_verifier_link_weights(uint64_t batch, const uint64_t* r_mont, uint64_t* out_weights_mont);
+
 /* ---- MSM: replaces <E::G1 as VariableBaseMSM>::msm_bigint(bases, bigints)
  *      at univariate_kzg/mod.rs:109-111 (commit) and :151-155 (open).
  * Computes sum_{i<n} scalars[i] * srs[base_offset + i]; base_offset = num_leading_zeros of
@@ -894,7 +938,8 @@ MZK_API int32_t mzk_dev_memset2d(void* dptr, uint64_t pitch, int32_t value, uint
 /* ---- measurement hooks (bench.py): HIP-event timing of the library's own kernels ---- */
 /* on != 0: every subsequent call brackets its dominant kernels with hipEvents on the launch stream. */
 MZK_API int32_t mzk_profile_enable(int32_t on);
-/* name: "msm_accumulate", "msm_total", "ntt_pass", "ntt_total".  Returns accumulated device
+/* name: "msm_accumulate", "msm_total", "ntt_pass", "ntt_total", "vfy_link_transcript", "vfy_link_vanishing" (the two
+ * kernels of mzk_verifier_link_begin; read them on the device the verifier lives on).  Returns accumulated device
  * milliseconds and launch count since the last reset (synchronises the recorded events). */
 MZK_API int32_t mzk_profile_get(const char* name, double* out_ms, uint64_t* out_count);
 MZK_API int32_t mzk_profile_reset(void);

@@ -20,4 +20,4 @@ from . import batch, linking, plonk, poly, prover, rng, sharding, snark, transcr
 from .kzg import (Commitment, PCSError, SerializationError, UnivariateKzgPCS, UnivariateProverParam,  # noqa: F401
                   UnivariateUniversalParams, jacobian_to_affine, msm_bigint, msm_bigint_batch)
 from . import keys  # noqa: F401
-from .keys import KeySerializationError, ProvingKey, VerifyingKey, key_layout  # noqa: F401
+from .keys import KeySerializationError, OpenKey, ProvingKey, VerifyingKey, key_layout  # noqa: F401

@@ -96,7 +96,9 @@ struct ProfScope {
     hipEvent_t a = nullptr, b = nullptr;
     hipStream_t st;
     const char* name;
+    int logical = -1;                             // >= 0: the record goes to that context (taken under its lock), not to cur()
     ProfScope(const char* n, hipStream_t s);
+    ProfScope(const char* n, hipStream_t s, int logical_device);   // for the translation units that run under a DeviceGuard, where cur() is not bound
     ~ProfScope();
 };
 extern std::atomic<bool> g_msm_precompute;

@@ -78,15 +78,19 @@ void ws_release(Workspace& ws, hipStream_t st) { (void)hipEventRecord(ws.last_us
 
 std::atomic<bool> g_prof{false};
 std::atomic<uint64_t> g_launches{0};
+extern Ctx g_ctx[MAX_CTX];                    // (defined below)
 ProfScope::ProfScope(const char* n, hipStream_t s) : st(s), name(n) {
     if (!g_prof) return;
     if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { a = b = nullptr; return; }
     (void)hipEventRecord(a, st);
 }
+ProfScope::ProfScope(const char* n, hipStream_t s, int logical_device) : ProfScope(n, s) { logical = logical_device; }
 ProfScope::~ProfScope() {
     if (!a) return;
     (void)hipEventRecord(b, st);
-    cur().prof_recs.push_back({name, a, b});
+    if (logical < 0) { cur().prof_recs.push_back({name, a, b}); return; }
+    std::lock_guard<std::mutex> lk(g_ctx[logical].lock);
+    g_ctx[logical].prof_recs.push_back({name, a, b});
 }
 
 // ---- contexts ------------------------------------------------------------------------------------------

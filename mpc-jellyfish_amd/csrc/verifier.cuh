@@ -1,5 +1,6 @@
 // verifier.cuh -- the per-proof work of PlonkKzgSnark::batch_verify on the device: K single-instance proofs under
-// ONE verifying key, staged as K images of proof_len bytes.  Aggregated BatchProofs under a tuple of keys: the second half of this file.
+// ONE verifying key, staged as K images of proof_len bytes.  Aggregated BatchProofs under a tuple of keys: the second half of this file;
+// proof links (verify_link_proof): its last section.
 //   A  vfy_decode_kernel      one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array
 //   B  vfy_transcript_kernel  one thread per proof: the Merlin transcript of compute_challenges (verifier.rs:274-319) -> 7 challenges
 //   C  vfy_scalars_kernel     one thread per proof: prepare_pcs_info for one instance (verifier.rs:122-184, 340-733) -> one scalar per base
@@ -325,22 +326,23 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_scalars_kernel(const uint8_t*
 }
 
 // ---- finish --------------------------------------------------------------------------------------------------------------------------
-// proof rows *= r_i (0 at a flagged base); A's scalars (r_i, r_i u_i)
-template <class P>
+// proof rows *= r_i (0 at a flagged base); A's scalars (r_i, r_i u_i).  NA: A bases per group member -- 2 for a proof (W, W'), 1 for a
+// proof link (its opening proof, scalar r_i alone: `challenges` is not read)
+template <class P, uint32_t NA = 2>
 __global__ __launch_bounds__(256) void vfy_weight_kernel(unsigned long long K, uint32_t np, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ challenges,
                                                          const uint32_t* __restrict__ inf_flags /* K x np */, const uint32_t* __restrict__ a_inf,
                                                          uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ a_scalars) {
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= K * (np + 2)) return;
-    const unsigned long long i = t / (np + 2);
-    const uint32_t j = (uint32_t)(t % (np + 2));
+    if (t >= K * (np + NA)) return;
+    const unsigned long long i = t / (np + NA);
+    const uint32_t j = (uint32_t)(t % (np + NA));
     const Fp<P> r = load_fp<P>(weights + i * 8ull);
     if (j < np) {
         const Fp<P> s = inf_flags[i * np + j] ? Fp<P>::zero() : r * load_fp<P>(proof_rows + (i * np + j) * 8ull);
         store_fp<P>(proof_rows + (i * np + j) * 8ull, s);
     } else {
-        const unsigned long long a = 2 * i + (j - np);
-        Fp<P> s = j == np ? r : r * load_fp<P>(challenges + (i * 7 + 6) * 8ull);
+        const unsigned long long a = NA * i + (j - np);
+        Fp<P> s = (NA == 1 || j == np) ? r : r * load_fp<P>(challenges + (i * 7 + 6) * 8ull);
         if (a_inf[a]) s = Fp<P>::zero();
         store_fp<P>(a_scalars + a * 8ull, s);
     }
@@ -700,6 +702,90 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_fold_kernel(unsigned long
     for (uint32_t j = 0; j < sh.m; j++) eval = eval + load_fp<P>(partials + (i * sh.m + j) * 8ull);
     store_fp<P>(evals + i * 8ull, eval);
     store_fp<P>(key_rows + (i * sh.nkey + sh.nkey - 1) * 8ull, F::zero());
+}
+
+// ---- proof links ---------------------------------------------------------------------------------------------------------------------
+// PlonkKzgSnark::verify_link_proof (proof_linking.rs:240-286) for K links, each staged as 4 G1 records back to back: lhs.wires_poly_comms[0],
+// rhs.wires_poly_comms[0], quotient_commitment, opening_proof.  A link is the KZG opening of a_1 - a_2 - Z_D(eta) q at eta with value 0
+// (univariate_kzg/mod.rs:194-216), so it ends in the pair  A = pi,  B = a_1 - a_2 - Z_D(eta) Q + eta pi  and joins the groups above:
+//   key bases    open_key.g alone, scalar zero (NKEY = 1)        proof points  the 4 records, row (1, -1, -Z_D(eta), eta) (NP = 4)
+//   A  vfy_decode_kernel          over a 4-record VfyPoints (infinity flagged: two proofs of one circuit link with Q = pi = O)
+//   Bl vfy_link_transcript_kernel one thread per link: eta (proof_linking.rs:185-197)
+//   Cl vfy_link_vanishing_kernel  one wave per link: Z_D(eta) (:162-176) and the link's row
+//   finish                        vfy_weight_kernel<P, 1> (one A base per link), vfy_colsum_kernel over the one key column
+template <class P, class X>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_link_transcript_kernel(const uint8_t* __restrict__ records, unsigned long long K, uint32_t g1_bytes,
+                                                                          uint32_t compressed, uint32_t* __restrict__ eta) {
+    __shared__ uint64_t lanes[25 * VFY_THREADS];
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const uint8_t* rec = records + i * 4ull * g1_bytes;
+    const bool cmp = compressed;
+    merlin::Transcript t;
+    t.init(lanes + threadIdx.x, VFY_THREADS, VFY_LBL("PlonkLinkingProof"));
+    vfy_append_g1<X>(t, VFY_LBL("linking_wire_comms"), rec, cmp);
+    vfy_append_g1<X>(t, VFY_LBL("linking_wire_comms"), rec + g1_bytes, cmp);
+    vfy_append_g1<X>(t, VFY_LBL("quotient_comm"), rec + 2 * g1_bytes, cmp);
+    store_fp<P>(eta + i * 8ull, vfy_challenge<P>(t, VFY_LBL("eta")));
+}
+
+// Link i, one wave: Z_D(eta) = prod_{k < size} (eta - g^(offset + k)), g the 2^alignment-th root of unity of the NTT (GroupLayout::
+// get_domain_generator).  Lane t takes the factors k = t, t + 64, ..: it starts at g^(offset + t) by square-and-multiply (the exponent
+// taken mod 2^alignment, the order of g -- an offset + size beyond it wraps, a size beyond it repeats roots, as the reference's loop does)
+// and steps by g^64; the 64 partial products meet in LDS by a fixed tree.  Field products are exact, so the order in which the factors
+// are multiplied does not change a bit of the result: the same value on every run, and no atomics.  layouts: K x (alignment, offset, size),
+// checked on the host (alignment <= TWO_ADICITY, size <= 2^27).  Lane 0 writes Z_D(eta) and the row (1, -1, -Z_D(eta), eta).
+template <class P>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_link_vanishing_kernel(const unsigned long long* __restrict__ layouts, const uint32_t* __restrict__ eta,
+                                                                         uint32_t* __restrict__ vanish, uint32_t* __restrict__ proof_rows) {
+    using F = Fp<P>;
+    __shared__ uint32_t part[8 * VFY_THREADS];                    // limb-major: lane t's limb k at part[k * 64 + t], no bank conflict
+    const unsigned long long i = blockIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const unsigned long long alignment = layouts[3 * i], offset = layouts[3 * i + 1], size = layouts[3 * i + 2];
+    const F x = load_fp<P>(eta + i * 8ull);
+    F g = F::from_const(P::ROOT);
+    for (int k = (int)alignment; k < P::TWO_ADICITY; k++) g = sqr(g);
+    F root = F::one(), step = g;
+    {
+        F b = g;
+        for (unsigned long long e = (offset + lane) & ((1ull << alignment) - 1); e; e >>= 1) {
+            if (e & 1) root = root * b;
+            b = sqr(b);
+        }
+    }
+#pragma unroll 1
+    for (int k = 0; k < 6; k++) step = sqr(step);                 // g^64
+    F acc = F::one();
+    for (unsigned long long k = lane; k < size; k += VFY_THREADS) {
+        acc = acc * (x - root);
+        root = root * step;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; k++) part[k * VFY_THREADS + lane] = acc.l[k];
+    __syncthreads();
+    for (uint32_t half = VFY_THREADS / 2; half; half >>= 1) {
+        if (lane < half) {
+            F a, b;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { a.l[k] = part[k * VFY_THREADS + lane]; b.l[k] = part[k * VFY_THREADS + lane + half]; }
+            a = a * b;
+#pragma unroll
+            for (int k = 0; k < 8; k++) part[k * VFY_THREADS + lane] = a.l[k];
+        }
+        __syncthreads();
+    }
+    if (lane == 0) {
+        F z;
+#pragma unroll
+        for (int k = 0; k < 8; k++) z.l[k] = part[k * VFY_THREADS];
+        store_fp<P>(vanish + i * 8ull, z);
+        uint32_t* row = proof_rows + i * 4 * 8ull;
+        store_fp<P>(row, F::one());
+        store_fp<P>(row + 8, neg(F::one()));
+        store_fp<P>(row + 16, neg(z));
+        store_fp<P>(row + 24, x);
+    }
 }
 
 }  // namespace mzk

@@ -1,5 +1,6 @@
 // verifier.hip -- mzk_verifier_*: PlonkKzgSnark::batch_verify for single-instance proofs (snark.rs:141-190, verifier.rs:68-251) and
-// verify_batch_proof for aggregated BatchProofs under a tuple of keys (snark.rs:117-138; mzk_verifier_aggregate_*).  The per-proof
+// verify_batch_proof for aggregated BatchProofs under a tuple of keys (snark.rs:117-138; mzk_verifier_aggregate_*), verify_link_proof for
+// proof links under an open key (proof_linking.rs:240-286; mzk_verifier_create_open_key, mzk_verifier_link_*).  The per-proof
 // work runs on the device (verifier.cuh: decode, Fiat-Shamir, linearisation scalars), the two MSMs through the variable-base path over a base
 // array registered per batch, the two pairings on the host (hostpairing.hpp behind mzk_pairing_product_is_one).
 #include "internal.hpp"
@@ -19,14 +20,20 @@ struct Verifier {
     uint32_t n_items = 0, script_len = 0;
     std::vector<uint64_t> h, beta_h;                              // mzk_g2_decode's output
     std::vector<uint64_t> g;                                      // open_key.g as decoded (host copy: an aggregate's tuple compares open keys)
+    bool open_only = false;                                       // mzk_verifier_create_open_key: no verifying key, key_xy holds open_key.g alone
+    uint32_t g_index() const { return open_only ? 0 : sh.nkey - 1; }   // open_key.g in key_xy / key_inf
 };
+enum class BatchKind { Proofs, Links };                           // Proofs: single proofs and aggregates (two A bases each); Links: one A base each
 struct Batch {
     std::shared_ptr<Verifier> v;                                  // an open batch keeps its verifier alive ...
     std::vector<std::shared_ptr<Verifier>> more;                  // ... and an aggregate batch the verifiers at positions 1 .. m - 1 of its tuple too
+    BatchKind kind = BatchKind::Proofs;
     uint64_t K = 0;
-    uint32_t np = 0, nkey = 0;                                    // columns of one proof's row and of the key row (an aggregate: NP(m), NKEY(m))
+    uint32_t np = 0, nkey = 0;                                    // columns of one proof's row and of the key row (an aggregate: NP(m), NKEY(m); links: 4, 1)
     DevOwned images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
     DevOwned col_off, col_fld, script, pos_tab, k_mont, partials;   // an aggregate's tables (verifier.cuh)
+    DevOwned layouts, vanish;                                     // links: K x (alignment, offset, size); Z_D(eta_i) (eta_i: the first K values of chal)
+    std::vector<uint8_t> open_recs;                               // links: the K opening-proof records as staged (mzk_verifier_link_weights)
     bool holds(const std::shared_ptr<Verifier>& x) const { return v == x || std::find(more.begin(), more.end(), x) != more.end(); }
 };
 
@@ -372,11 +379,11 @@ int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, 
     return MZK_OK;
 }
 
-template <class Fr>
+template <class Fr, uint32_t NA>
 void launch_finish(const Batch& b, uint64_t K, uint32_t np, uint32_t nkey) {
     uint32_t* proof_rows = b.b_scal.as<uint32_t>() + (size_t)nkey * 8;
-    const dim3 wgrid((unsigned)((K * (np + 2) + 255) / 256));
-    hipLaunchKernelGGL((vfy_weight_kernel<Fr>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
+    const dim3 wgrid((unsigned)((K * (np + NA) + 255) / 256));
+    hipLaunchKernelGGL((vfy_weight_kernel<Fr, NA>), wgrid, dim3(256), 0, nullptr, (unsigned long long)K, np, b.weights.as<uint32_t>(), b.chal.as<uint32_t>(),
                        b.inf.as<uint32_t>() + nkey, b.a_inf.as<uint32_t>(), proof_rows, b.a_scal.as<uint32_t>());
     hipLaunchKernelGGL((vfy_colsum_kernel<Fr>), dim3(nkey), dim3(256), 0, nullptr, (unsigned long long)K, nkey, b.weights.as<uint32_t>(), b.key_rows.as<uint32_t>(),
                        b.evals.as<uint32_t>(), b.inf.as<uint32_t>(), b.b_scal.as<uint32_t>());
@@ -386,12 +393,13 @@ int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_
     const uint64_t K = b.K;
     const uint32_t np = b.np, nkey = b.nkey;
     HIP_TRY(hipMemcpy(b.weights.p, weights, K * 32, hipMemcpyHostToDevice));
-    if (v.curve == MZK_CURVE_BLS12_381) launch_finish<BlsFr>(b, K, np, nkey);
-    else launch_finish<BnFr>(b, K, np, nkey);
+    const bool links = b.kind == BatchKind::Links;
+    if (v.curve == MZK_CURVE_BLS12_381) links ? launch_finish<BlsFr, 1>(b, K, np, nkey) : launch_finish<BlsFr, 2>(b, K, np, nkey);
+    else links ? launch_finish<BnFr, 1>(b, K, np, nkey) : launch_finish<BnFr, 2>(b, K, np, nkey);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    // the two MSMs of verifier.rs:217-247 through the variable-base path
-    const struct { void* bases; void* scalars; uint64_t n; uint64_t* out; } jobs[2] = {{b.a_bases.p, b.a_scal.p, 2 * K, out_A},
+    // the two MSMs of verifier.rs:217-247 through the variable-base path (links: A over the K opening proofs)
+    const struct { void* bases; void* scalars; uint64_t n; uint64_t* out; } jobs[2] = {{b.a_bases.p, b.a_scal.p, links ? K : 2 * K, out_A},
                                                                                       {b.bases.p, b.b_scal.p, nkey + K * np, out_B}};
     for (const auto& j : jobs) {
         uint64_t srs = 0;
@@ -474,6 +482,7 @@ int32_t tuple_shape(const std::vector<std::shared_ptr<Verifier>>& vs, VfyAggShap
     uint64_t total_inputs = 0;
     for (uint32_t j = 0; j < m; j++) {
         const Verifier& v = *vs[j];
+        if (v.open_only) { set_error("the verifier holds no verifying key"); return MZK_ERR_INVALID_ARG; }
         if (v.curve != v0.curve) { set_error("the verification keys are of different curves"); return MZK_ERR_INVALID_ARG; }
         if (v.device != v0.device) { set_error("the verifiers live on different devices"); return MZK_ERR_INVALID_ARG; }
         if (v.sh.compressed != v0.sh.compressed) { set_error("the verification keys have different image modes"); return MZK_ERR_INVALID_ARG; }
@@ -687,6 +696,189 @@ int32_t aggregate_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const 
     return MZK_OK;
 }
 
+// ---- proof links (proof_linking.rs:240-286; verifier.cuh "proof links") ---------------------------------------------------------------------
+int32_t open_key_create(int32_t curve, int device, const uint8_t* g_bytes, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, uint32_t flags, uint64_t* out_handle) {
+    const bool compressed = flags & MZK_SER_COMPRESSED, validate = flags & MZK_SER_VALIDATE;
+    auto v = std::make_shared<Verifier>();
+    v->curve = curve, v->device = device, v->open_only = true;
+    v->sh.compressed = compressed, v->sh.g1_bytes = g1_bytes(curve, compressed);       // np = nkey = proof_len = 0: no verifying key
+    const uint32_t G = v->sh.g1_bytes, fqw = fq_words(curve);
+    VfyPoints pts{};
+    pts.n = 1, pts.stride = G, pts.open_idx = -1;
+    DevOwned image, err;
+    MZK_TRY(image.alloc(G));
+    MZK_TRY(err.alloc(8));
+    MZK_TRY(v->key_xy.alloc((size_t)2 * fqw * 4));
+    MZK_TRY(v->key_inf.alloc(4));
+    HIP_TRY(hipMemcpy(image.p, g_bytes, G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(err.p, 0xFF, 8));
+    decode_points(curve, compressed, validate, image.as<uint8_t>(), 1, pts, v->key_xy.as<uint32_t>(), v->key_inf.as<uint32_t>(), nullptr, nullptr,
+                  err.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpy(&bad, err.p, 8, hipMemcpyDeviceToHost));
+    if (bad != ~0ull) {
+        set_error(std::string("open_key.g: ") + reason_text((uint32_t)(bad & 0xFF)));
+        return MZK_ERR_ENCODING;
+    }
+    uint32_t inf = 0;
+    v->g.resize((size_t)2 * fqw / 2);
+    HIP_TRY(hipMemcpy(v->g.data(), v->key_xy.p, (size_t)2 * fqw * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&inf, v->key_inf.p, 4, hipMemcpyDeviceToHost));
+    if (inf) std::fill(v->g.begin(), v->g.end(), 0);                 // (0, 0): as verifier_create keeps a flagged g
+    v->h.resize(4 * fqw / 2);
+    v->beta_h.resize(4 * fqw / 2);
+    if (mzk_g2_decode(curve, h_bytes, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->h.data()) != MZK_OK) {
+        set_error(std::string("open_key.h: ") + mzk_last_error());
+        return MZK_ERR_ENCODING;
+    }
+    if (mzk_g2_decode(curve, beta_h_bytes, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->beta_h.data()) != MZK_OK) {
+        set_error(std::string("open_key.beta_h: ") + mzk_last_error());
+        return MZK_ERR_ENCODING;
+    }
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    *out_handle = handle_make(device, g_next_verifier++);
+    g_verifiers[*out_handle] = std::move(v);
+    return MZK_OK;
+}
+
+constexpr uint64_t LINK_MAX_SIZE = 1ull << 27;                       // the largest domain of the library (mzk_ntt)
+const char* const LINK_FIELDS[4] = {"lhs.wires_poly_comms[0]", "rhs.wires_poly_comms[0]", "quotient_commitment", "opening_proof"};
+
+int32_t link_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, uint64_t K, const uint64_t* layouts, const uint64_t* eta, uint32_t flags,
+                   uint64_t* out_batch, uint64_t* out_eta, uint64_t* out_bad) {
+    const Verifier& v = *vp;
+    const int curve = v.curve;
+    if (out_bad) *out_bad = ~0ull;
+    const uint64_t two_adicity = curve == MZK_CURVE_BLS12_381 ? BlsFr::TWO_ADICITY : BnFr::TWO_ADICITY;
+    for (uint64_t i = 0; i < K; i++) {                                 // (offset + size beyond 2^alignment: accepted, the roots wrap or repeat)
+        if (layouts[3 * i] > two_adicity) {
+            set_error("link " + std::to_string(i) + ": alignment " + std::to_string(layouts[3 * i]) + " is above the field's two-adicity " + std::to_string(two_adicity));
+            return MZK_ERR_INVALID_ARG;
+        }
+        if (layouts[3 * i + 2] > LINK_MAX_SIZE) {
+            set_error("link " + std::to_string(i) + ": size " + std::to_string(layouts[3 * i + 2]) + " is above 2^27");
+            return MZK_ERR_UNSUPPORTED;
+        }
+    }
+    const uint32_t G = v.sh.g1_bytes, np = 4, nkey = 1, fqw = fq_words(curve);
+    const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
+    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
+    b->v = vp, b->kind = BatchKind::Links, b->K = K, b->np = np, b->nkey = nkey;
+    b->open_recs.resize(K * G);
+    for (uint64_t i = 0; i < K; i++) std::memcpy(&b->open_recs[i * G], records + (i * 4 + 3) * G, G);
+    MZK_TRY(b->images.alloc(K * 4 * G));
+    MZK_TRY(b->layouts.alloc(K * 24));
+    MZK_TRY(b->bases.alloc(n_bases * pt_bytes));
+    MZK_TRY(b->inf.alloc(n_bases * 4));
+    MZK_TRY(b->a_bases.alloc(K * pt_bytes));
+    MZK_TRY(b->a_inf.alloc(K * 4));
+    MZK_TRY(b->chal.alloc(K * 32));
+    MZK_TRY(b->vanish.alloc(K * 32));
+    MZK_TRY(b->key_rows.alloc(K * nkey * 32));
+    MZK_TRY(b->b_scal.alloc(n_bases * 32));
+    MZK_TRY(b->evals.alloc(K * 32));
+    MZK_TRY(b->a_scal.alloc(K * 32));
+    MZK_TRY(b->weights.alloc(K * 32));
+    MZK_TRY(b->err.alloc(8));
+    HIP_TRY(hipMemcpy(b->images.p, records, K * 4 * G, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->layouts.p, layouts, K * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b->err.p, 0xFF, 8));
+    HIP_TRY(hipMemset(b->key_rows.p, 0, K * nkey * 32));              // open_key.g: scalar zero, and the opened value is 0
+    HIP_TRY(hipMemset(b->evals.p, 0, K * 32));
+    HIP_TRY(hipMemcpy(b->bases.p, v.key_xy.as<uint8_t>() + (size_t)v.g_index() * pt_bytes, pt_bytes, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(b->inf.p, v.key_inf.as<uint32_t>() + v.g_index(), 4, hipMemcpyDeviceToDevice));
+    unsigned long long* err = b->err.as<unsigned long long>();
+    // A: the existing decoder over a 4-record image; the opening proofs (column 3) are then gathered as the bases of the MSM A
+    VfyPoints pts{};
+    pts.n = np, pts.stride = 4 * G, pts.open_idx = -1;
+    for (uint32_t j = 0; j < np; j++) pts.off[j] = j * G;
+    uint8_t* own_bases = b->bases.as<uint8_t>() + (size_t)nkey * pt_bytes;
+    decode_points(curve, v.sh.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, pts, reinterpret_cast<uint32_t*>(own_bases), b->inf.as<uint32_t>() + nkey,
+                  nullptr, nullptr, err);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(b->a_bases.p, pt_bytes, own_bases + 3 * pt_bytes, 4 * pt_bytes, pt_bytes, K, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpy2DAsync(b->a_inf.p, 4, b->inf.as<uint32_t>() + nkey + 3, 16, 4, K, hipMemcpyDeviceToDevice, nullptr));
+    // Bl, or the caller's eta
+    if (eta) {
+        HIP_TRY(hipMemcpy(b->chal.p, eta, K * 32, hipMemcpyHostToDevice));
+    } else {
+        ProfScope ps("vfy_link_transcript", nullptr, v.device);
+        const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+        if (curve == MZK_CURVE_BLS12_381)
+            hipLaunchKernelGGL((vfy_link_transcript_kernel<BlsFr, BlsFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, G, v.sh.compressed,
+                               b->chal.as<uint32_t>());
+        else
+            hipLaunchKernelGGL((vfy_link_transcript_kernel<BnFr, BnFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, G, v.sh.compressed,
+                               b->chal.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+    }
+    // Cl
+    {
+        ProfScope ps("vfy_link_vanishing", nullptr, v.device);
+        uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
+        const dim3 grid((unsigned)K), block(VFY_THREADS);
+        if (curve == MZK_CURVE_BLS12_381)
+            hipLaunchKernelGGL((vfy_link_vanishing_kernel<BlsFr>), grid, block, 0, nullptr, b->layouts.as<unsigned long long>(), b->chal.as<uint32_t>(),
+                               b->vanish.as<uint32_t>(), proof_rows);
+        else
+            hipLaunchKernelGGL((vfy_link_vanishing_kernel<BnFr>), grid, block, 0, nullptr, b->layouts.as<unsigned long long>(), b->chal.as<uint32_t>(),
+                               b->vanish.as<uint32_t>(), proof_rows);
+        HIP_TRY(hipGetLastError());
+    }
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));                             // (synchronises the stages)
+    if (bad != ~0ull) {
+        const uint64_t i = bad >> 32;
+        if (out_bad) *out_bad = i;
+        set_error("link " + std::to_string(i) + ": " + LINK_FIELDS[(bad >> 8) & 3] + ": " + reason_text((uint32_t)bad & 0xFF));
+        return MZK_ERR_ENCODING;
+    }
+    if (out_eta) HIP_TRY(hipMemcpy(out_eta, b->chal.p, K * 32, hipMemcpyDeviceToHost));
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    *out_batch = handle_make(v.device, g_next_batch++);
+    g_batches[*out_batch] = std::move(b);
+    return MZK_OK;
+}
+
+// 64 challenge bytes mod r, Montgomery: vfy_reduce_challenge on the host (lo + 2^256 hi, each half below r by subtraction: 2^256 < 6 r)
+template <class FrP>
+Fp64<FrP> reduce_challenge_host(const uint8_t* ch) {
+    using F = Fp64<FrP>;
+    F lo = F::zero(), hi = F::zero(), r2;
+    for (int s = 0; s < 32; s++) { lo.l[s >> 3] |= (uint64_t)ch[s] << (8 * (s & 7)); hi.l[s >> 3] |= (uint64_t)ch[32 + s] << (8 * (s & 7)); }
+    for (int i = 0; i < 4; i++) r2.l[i] = F::c64(FrP::R2, i);
+    while (F::geq_mod(lo.l)) F::sub_mod(lo.l);
+    while (F::geq_mod(hi.l)) F::sub_mod(hi.l);
+    return lo * r2 + (hi * r2) * r2;
+}
+template <class FrP>
+void fr_record_host(const uint64_t* mont, uint8_t* rec) {            // Montgomery -> 32 B little-endian canonical
+    Fp64<FrP> a;
+    std::memcpy(a.l, mont, sizeof a.l);
+    const auto c = h64::canonical(a);
+    for (int s = 0; s < 32; s++) rec[s] = (uint8_t)(c[s >> 3] >> (8 * (s & 7)));
+}
+// The weights of a link batch: s^(i + 1), s drawn from r (when the links stand beside Plonk groups), every eta_i and every opening-proof
+// record.  eta_i binds a_1, a_2 and Q but not pi_i, so the pi_i enter too; no weight is 1 beside a Plonk group, whose first proof has r^0.
+template <class FrP>
+void link_weights_t(const uint64_t* r_mont, const uint64_t* eta, const std::vector<uint8_t>& open_recs, uint64_t K, uint64_t* out) {
+    using F = Fp64<FrP>;
+    if (K == 1 && !r_mont) { const F one = F::one(); std::memcpy(out, one.l, sizeof one.l); return; }
+    const uint32_t G = (uint32_t)(open_recs.size() / K);
+    uint64_t lanes[25];
+    uint8_t rec[32], ch[64];
+    merlin::Transcript t;
+    t.init(lanes, 1, "batch verify links", 18);
+    if (r_mont) { fr_record_host<FrP>(r_mont, rec); t.append_message("r", 1, rec, 32); }
+    for (uint64_t i = 0; i < K; i++) { fr_record_host<FrP>(eta + 4 * i, rec); t.append_message("eta", 3, rec, 32); }
+    for (uint64_t i = 0; i < K; i++) t.append_message("opening_proof", 13, &open_recs[i * G], G);
+    t.challenge_bytes("s", 1, ch, 64);
+    const F s = reduce_challenge_host<FrP>(ch);
+    F w = s;
+    for (uint64_t i = 0; i < K; i++, w = w * s) std::memcpy(out + 4 * i, w.l, sizeof w.l);
+}
+
 }  // namespace
 
 void verifier_release_all() {                                         // mzk_shutdown, per context (bound): its handles go; what a call in flight holds goes with that call
@@ -737,6 +929,7 @@ extern "C" int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* pr
                                             const uint8_t* extra_msgs, const uint64_t* extra_ranges, const uint64_t* challenges_mont, uint32_t flags,
                                             uint64_t* out_batch, uint64_t* out_u_mont, uint64_t* out_bad_index) {
     ON_DEVICE_OF(verifier, v, find_verifier);
+    if (v->open_only) { set_error("the verifier holds no verifying key"); return MZK_ERR_INVALID_ARG; }
     if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->sh.num_inputs && !public_inputs_canonical) || (flags & ~MZK_SER_VALIDATE)) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
@@ -798,6 +991,7 @@ extern "C" int32_t mzk_verifier_aggregate_begin(const uint64_t* verifiers, uint3
 extern "C" int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out) {
     ON_DEVICE_OF(batch, b, find_batch);
     if (!out) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (b->kind == BatchKind::Links) { set_error("a link batch has no challenges: mzk_verifier_link_values"); return MZK_ERR_INVALID_ARG; }
     return hip_status(hipMemcpy(out, b->chal.p, b->K * 7 * 32, hipMemcpyDeviceToHost), "hipMemcpy of the challenges");
 }
 
@@ -838,4 +1032,41 @@ extern "C" int32_t mzk_verifier_check(uint64_t verifier, const uint64_t* A_xyz, 
     if (curve == MZK_CURVE_BLS12_381) fq_negate_host<BlsFq>(&g1[3 * L]);   // -B
     else fq_negate_host<BnFq>(&g1[3 * L]);
     return mzk_pairing_product_is_one(curve, g1.data(), g2.data(), 2, out_accept);   // e(A, beta_h) e(-B, h) = 1
+}
+
+extern "C" int32_t mzk_verifier_create_open_key(int32_t curve_id, const uint8_t* g_bytes, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, uint32_t flags,
+                                                uint64_t* out_handle) {
+    if (!valid_curve(curve_id) || !g_bytes || !h_bytes || !beta_h_bytes || !out_handle || (flags & ~(MZK_SER_COMPRESSED | MZK_SER_VALIDATE))) {
+        set_error("bad argument");
+        return MZK_ERR_INVALID_ARG;
+    }
+    int32_t device;                                                   // the calling thread's context, as mzk_verifier_create
+    MZK_TRY(mzk_get_device(&device));
+    return open_key_create(curve_id, device, g_bytes, h_bytes, beta_h_bytes, flags, out_handle);
+}
+
+extern "C" int32_t mzk_verifier_link_begin(uint64_t verifier, const uint8_t* records, uint64_t K, const uint64_t* layouts, const uint64_t* eta_mont, uint32_t flags,
+                                           uint64_t* out_batch, uint64_t* out_eta_mont, uint64_t* out_bad_index) {
+    ON_DEVICE_OF(verifier, v, find_verifier);
+    if (!records || !K || K >= (1ull << 24) || !layouts || !out_batch || (flags & ~MZK_SER_VALIDATE)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    return link_begin(v, records, K, layouts, eta_mont, flags, out_batch, out_eta_mont, out_bad_index);
+}
+
+extern "C" int32_t mzk_verifier_link_values(uint64_t batch, uint64_t* out_eta_mont, uint64_t* out_vanishing_mont) {
+    ON_DEVICE_OF(batch, b, find_batch);
+    if (b->kind != BatchKind::Links) { set_error("not a link batch"); return MZK_ERR_INVALID_ARG; }
+    if (out_eta_mont) HIP_TRY(hipMemcpy(out_eta_mont, b->chal.p, b->K * 32, hipMemcpyDeviceToHost));
+    if (out_vanishing_mont) HIP_TRY(hipMemcpy(out_vanishing_mont, b->vanish.p, b->K * 32, hipMemcpyDeviceToHost));
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_verifier_link_weights(uint64_t batch, const uint64_t* r_mont, uint64_t* out_weights_mont) {
+    ON_DEVICE_OF(batch, b, find_batch);
+    if (b->kind != BatchKind::Links) { set_error("not a link batch"); return MZK_ERR_INVALID_ARG; }
+    if (!out_weights_mont) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    std::vector<uint64_t> eta(b->K * 4);
+    HIP_TRY(hipMemcpy(eta.data(), b->chal.p, b->K * 32, hipMemcpyDeviceToHost));
+    if (b->v->curve == MZK_CURVE_BLS12_381) link_weights_t<BlsFr>(r_mont, eta.data(), b->open_recs, b->K, out_weights_mont);
+    else link_weights_t<BnFr>(r_mont, eta.data(), b->open_recs, b->K, out_weights_mont);
+    return MZK_OK;
 }

@@ -102,6 +102,36 @@ class VerifyingKey:
             self._verifier = None
 
 
+class OpenKey:
+    """UnivariateVerifierParam / OpenKey (univariate_kzg/srs.rs:48-55): g (G1), h, beta_h (G2) as records of the mode `compressed` -- all that
+    PlonkKzgSnark::verify_link_proof takes.  verifier(): a device verifier that carries the open key alone (mzk_verifier_create_open_key):
+    it begins link batches and runs the pairing check, but holds no verifying key (begin() raises)."""
+
+    def __init__(self, curve, g, h, beta_h, compressed: bool = True):
+        self.curve, self.compressed = _curve(curve), compressed
+        self.g, self.h, self.beta_h = bytes(g), bytes(h), bytes(beta_h)
+
+    def verifier(self, validate: bool = True) -> "Verifier":
+        v = getattr(self, "_verifier", None)
+        if v is None:
+            v = self._verifier = Verifier(self, validate)
+        return v
+
+    def begin_links(self, links, eta=None, validate: bool = True) -> "VerifierBatch":
+        return self.verifier().begin_links(links, eta, validate)
+
+    def check(self, A_xyz, B_xyz) -> bool:
+        return self.verifier().check(A_xyz, B_xyz)
+
+    def release(self):
+        v = getattr(self, "_verifier", None)
+        if v is not None:
+            v.release()
+            self._verifier = None
+
+    release_verifier = release
+
+
 class ProofEncodingError(SerializationError):
     """A proof that ark-serialize or the verifier's range checks would refuse (MZK_ERR_ENCODING).  .index: the lowest bad proof of the batch;
     .field: the field of the `Proof` ("wires_poly_comms[2]", "wires_evals[0]", "length", ..); .reason: the library's text."""
@@ -114,6 +144,7 @@ class ProofEncodingError(SerializationError):
 
 _PROOF_MSG = re.compile(r"^proof (\d+): ([^:]+): ")
 _BATCH_PROOF_MSG = re.compile(r"^(?:proof (\d+): )?instance (\d+): ([^:]+): ")
+_LINK_MSG = re.compile(r"^link (\d+): ([^:]+): ")
 
 
 def _begin_arrays(proofs, flat_inputs, extra_msgs, challenges):
@@ -137,13 +168,20 @@ class Verifier:
     """mzk_verifier_*: the decoded commitments, k and the transcript script of one VerifyingKey on the device, h and beta_h on the host.
     begin() runs the per-proof stages of a group of proofs under this key and returns a VerifierBatch."""
 
-    def __init__(self, vk: VerifyingKey, validate: bool = True):
+    def __init__(self, vk, validate: bool = True):
+        """vk: a VerifyingKey, or an OpenKey for a verifier of proof links alone"""
         L = _lib.ensure_init()
         self.vk, self.curve = vk, vk.curve
-        img = np.frombuffer(vk.serialize(), dtype=np.uint8)
+        flags = (_SER_COMPRESSED if vk.compressed else 0) | (_SER_VALIDATE if validate else 0)
         h = C.c_uint64()
-        rc = L.mzk_verifier_create(vk.curve.curve_id, C.c_void_p(img.ctypes.data), img.shape[0],
-                                   (_SER_COMPRESSED if vk.compressed else 0) | (_SER_VALIDATE if validate else 0), C.byref(h))
+        if isinstance(vk, OpenKey):
+            recs = [np.frombuffer(b, dtype=np.uint8) for b in (vk.g, vk.h, vk.beta_h)]
+            if [len(b) for b in recs] != [kzg.g1_record_bytes(vk.curve, vk.compressed)] + [kzg.g2_record_bytes(vk.curve, vk.compressed)] * 2:
+                raise KeySerializationError("open_key: a record of the wrong length for this curve and mode", "open_key")
+            rc = L.mzk_verifier_create_open_key(vk.curve.curve_id, *[C.c_void_p(b.ctypes.data) for b in recs], flags, C.byref(h))
+        else:
+            img = np.frombuffer(vk.serialize(), dtype=np.uint8)
+            rc = L.mzk_verifier_create(vk.curve.curve_id, C.c_void_p(img.ctypes.data), img.shape[0], flags, C.byref(h))
         if rc == _ERR_ENCODING:
             _raise_encoding(L, None)
         _lib.check(rc, "mzk_verifier_create")
@@ -157,6 +195,8 @@ class Verifier:
         K entries, each bytes or None; challenges: None or (K, 7, 4) uint64 Montgomery (tau, beta, gamma, alpha, zeta, v, u) replacing the
         transcript.  Raises ProofEncodingError naming the lowest bad proof."""
         L = _lib.load()
+        if isinstance(self.vk, OpenKey):
+            raise ValueError("the verifier holds no verifying key")     # (mzk_verifier_batch_begin: MZK_ERR_INVALID_ARG with this text)
         K = len(proofs)
         if K == 0 or len(public_inputs) != K or (extra_msgs is not None and len(extra_msgs) != K):
             raise ValueError("the number of proofs / public inputs / extra messages differ, or no proof")
@@ -179,6 +219,35 @@ class Verifier:
         _lib.check(rc, "mzk_verifier_batch_begin")
         return VerifierBatch(self, batch.value, K, u)
 
+    def begin_links(self, links, eta=None, validate: bool = True) -> "VerifierBatch":
+        """mzk_verifier_link_begin.  links: K tuples (lhs_record, rhs_record, link_proof_bytes, layout) -- wires_poly_comms[0] of the two
+        Plonk proofs (linking.linking_wire_record), the LinkingProof image (quotient_commitment || opening_proof) and a GroupLayout, records
+        in this verifier's mode; eta: None or (K, 4) uint64 Montgomery replacing the transcript.  Returns a VerifierBatch whose rows are (1, -1,
+        -Z_D(eta), eta) over the four records and whose .u holds the K challenges eta.  Raises ProofEncodingError naming the lowest bad link
+        (.index) and its field."""
+        L = _lib.load()
+        K = len(links)
+        if K == 0:
+            raise ValueError("no link to verify")
+        G = kzg.g1_record_bytes(self.curve, self.vk.compressed)
+        for i, (lhs, rhs, link, _) in enumerate(links):
+            for name, rec, want in (("lhs.wires_poly_comms[0]", lhs, G), ("rhs.wires_poly_comms[0]", rhs, G), ("length", link, 2 * G)):
+                if len(rec) != want:
+                    raise ProofEncodingError(f"link {i}: {name}: {len(rec)} bytes, expected {want} on this curve and in this mode", i, name)
+        records = np.frombuffer(b"".join(bytes(lhs) + bytes(rhs) + bytes(link) for lhs, rhs, link, _ in links), dtype=np.uint8)
+        layouts = np.array([[lay.alignment, lay.offset, lay.size] for _, _, _, lay in links], dtype=np.uint64)
+        e = None if eta is None else np.ascontiguousarray(eta, dtype=np.uint64).reshape(K, 4)
+        batch, bad = C.c_uint64(), C.c_uint64()
+        out = np.zeros((K, 4), dtype=np.uint64)
+        rc = L.mzk_verifier_link_begin(self.handle, C.c_void_p(records.ctypes.data), K, C.c_void_p(layouts.ctypes.data), None if e is None else C.c_void_p(e.ctypes.data),
+                                       _SER_VALIDATE if validate else 0, C.byref(batch), C.c_void_p(out.ctypes.data), C.byref(bad))
+        if rc == _ERR_ENCODING:
+            msg = L.mzk_last_error().decode()
+            m = _LINK_MSG.match(msg)
+            raise ProofEncodingError(msg, bad.value, m.group(2) if m else None)
+        _lib.check(rc, "mzk_verifier_link_begin")
+        return VerifierBatch(self, batch.value, K, out, shape=(1, 4))
+
     def check(self, A_xyz, B_xyz) -> bool:
         """mzk_verifier_check over the (A, B) of one or more groups with this key's open key: e(sum A, beta_h) e(-sum B, h) == 1."""
         A = np.ascontiguousarray(A_xyz, dtype=np.uint64).reshape(-1, 3, self.curve.fq_limbs)
@@ -198,8 +267,9 @@ class VerifierBatch:
     """An open batch: .u (K, 4) Montgomery, challenges() / scalars() the stage outputs, finish(r_weights) -> (A, B) Jacobian; finish or
     discard consumes it."""
 
-    def __init__(self, verifier: Verifier, handle: int, K: int, u: np.ndarray):
+    def __init__(self, verifier: Verifier, handle: int, K: int, u: np.ndarray, shape=None):
         self.verifier, self.handle, self.K, self.u = verifier, handle, K, u
+        self.n_key_bases, self.n_proof_points = shape or (verifier.n_key_bases, verifier.n_proof_points)   # (a link batch: 1, 4)
 
     def challenges(self) -> np.ndarray:
         out = np.zeros((self.K, 7, 4), dtype=np.uint64)
@@ -208,11 +278,25 @@ class VerifierBatch:
 
     def scalars(self):
         """(key_rows (K, NKEY, 4), proof_rows (K, NP, 4), evals (K, 4)), Montgomery, unweighted"""
-        v = self.verifier
-        kr, pr, ev = np.zeros((self.K, v.n_key_bases, 4), np.uint64), np.zeros((self.K, v.n_proof_points, 4), np.uint64), np.zeros((self.K, 4), np.uint64)
+        kr, pr, ev = np.zeros((self.K, self.n_key_bases, 4), np.uint64), np.zeros((self.K, self.n_proof_points, 4), np.uint64), np.zeros((self.K, 4), np.uint64)
         _lib.check(_lib.load().mzk_verifier_batch_scalars(self.handle, C.c_void_p(kr.ctypes.data), C.c_void_p(pr.ctypes.data), C.c_void_p(ev.ctypes.data)),
                    "mzk_verifier_batch_scalars")
         return kr, pr, ev
+
+    def link_values(self):
+        """mzk_verifier_link_values of a link batch: (eta (K, 4), Z_D(eta) (K, 4)), Montgomery"""
+        eta, van = np.zeros((self.K, 4), np.uint64), np.zeros((self.K, 4), np.uint64)
+        _lib.check(_lib.load().mzk_verifier_link_values(self.handle, C.c_void_p(eta.ctypes.data), C.c_void_p(van.ctypes.data)), "mzk_verifier_link_values")
+        return eta, van
+
+    def link_weights(self, r=None) -> np.ndarray:
+        """mzk_verifier_link_weights: the (K, 4) Montgomery weights for finish().  r: None, or the (4,) Montgomery batch challenge of the Plonk
+        groups this link batch is checked with.  One link and no r: exactly 1."""
+        rm = None if r is None else np.ascontiguousarray(r, dtype=np.uint64).reshape(4)
+        out = np.zeros((self.K, 4), np.uint64)
+        _lib.check(_lib.load().mzk_verifier_link_weights(self.handle, None if rm is None else C.c_void_p(rm.ctypes.data), C.c_void_p(out.ctypes.data)),
+                   "mzk_verifier_link_weights")
+        return out
 
     def finish(self, r_weights_mont):
         L = self.verifier.curve.fq_limbs

@@ -65,6 +65,16 @@ class LinkingProof:
         c = self.quotient_commitment.curve
         return _g1(c, self.quotient_commitment) + _g1(c, self.opening_proof)
 
+    @classmethod
+    def deserialize(cls, curve, data, compress: bool = True) -> "LinkingProof":
+        """LinkingProof::deserialize_(un)compressed: quotient_commitment || opening_proof (proof_linking.rs:33-39), parsed on the host"""
+        c = _curve(curve)
+        data = bytes(data)
+        G = kzg.g1_record_bytes(c, compress)
+        if len(data) != 2 * G:
+            raise kzg.SerializationError("a LinkingProof of %d bytes, expected %d" % (len(data), 2 * G))
+        return cls(_g1_from_record(c, data[:G], compress), _g1_from_record(c, data[G:], compress))
+
 
 def _point(c, cm: kzg.Commitment):
     if cm.is_infinity():
@@ -124,3 +134,80 @@ def link_proofs(lhs_link_hint: LinkingHint, rhs_link_hint: LinkingHint, group_la
     identity = poly.lincomb(c, terms)
     opening_proof, _ = kzg.UnivariateKzgPCS.open(commit_key, identity, eta)
     return LinkingProof(quotient_commitment, opening_proof)
+
+
+# ---- the verifier's half (proof_linking.rs:240-286): on the device through keys.Verifier.begin_links ------------------------
+_CURVE_B = {0: 4, 1: 3}                                      # y^2 = x^3 + b
+
+
+def _g1_from_record(c, rec: bytes, compress: bool) -> kzg.Commitment:
+    """One ark-serialize G1 record (include/mzk.h, "G1 records") as a Commitment, on the host: the flag rules, x, y < q and, compressed, that
+    x^3 + b is a square (q = 3 mod 4 on both curves: one power).  No subgroup check: the device decoder makes it when a link is verified."""
+    n = kzg.g1_record_bytes(c, True)
+    if len(rec) != (n if compress else 2 * n):
+        raise kzg.SerializationError("a G1 record of %d bytes, expected %d" % (len(rec), n if compress else 2 * n))
+    bls = c.curve_id == 0
+    flags = rec[0] if bls else rec[-1]
+    if bls and bool(flags & 0x80) != compress:
+        raise kzg.SerializationError("compression flag does not match the mode")
+    if not bls and (flags & 0xC0) == 0xC0:
+        raise kzg.SerializationError("invalid flag bits")
+    clear = (lambda b: bytes([b[0] & 0x1F]) + b[1:]) if bls else (lambda b: b[:-1] + bytes([b[-1] & 0x3F]))
+    order = "big" if bls else "little"
+    body = clear(bytes(rec)) if compress else (clear(bytes(rec)) if bls else bytes(rec[:n]) + clear(bytes(rec[n:])))
+    if flags & 0x40:
+        if any(body):
+            raise kzg.SerializationError("infinity flag with a non-zero coordinate")
+        return kzg.Commitment(c, np.zeros((2, c.fq_limbs), dtype=np.uint64))
+    x = int.from_bytes(body[:n], order)
+    if x >= c.q:
+        raise kzg.SerializationError("coordinate not below the field modulus")
+    if compress:
+        larger = bool(flags & (0x20 if bls else 0x80))
+        rhs = (x * x * x + _CURVE_B[c.curve_id]) % c.q
+        y = pow(rhs, (c.q + 1) // 4, c.q)
+        if y * y % c.q != rhs:
+            raise kzg.SerializationError("x is not on the curve")
+        if (y > c.q - y) != larger:
+            y = c.q - y
+    else:
+        y = int.from_bytes(body[n:], order)
+        if y >= c.q:
+            raise kzg.SerializationError("coordinate not below the field modulus")
+    from .params import fq_to_mont
+    return kzg.Commitment(c, np.ascontiguousarray(fq_to_mont(c, [x, y])).reshape(2, c.fq_limbs))
+
+
+def linking_wire_record(curve, proof_bytes, compress: bool = True, batch_layout=None, instance: int = 0) -> bytes:
+    """wires_poly_comms[PROOF_LINK_WIRE_IDX] as its record, cut out of a `Proof` image (after the Vec count: offset 8) or, with
+    batch_layout (keys.batch_proof_layout), out of instance `instance` of a `BatchProof` image."""
+    c = _curve(curve)
+    G = kzg.g1_record_bytes(c, compress)
+    off = 8 if batch_layout is None else int(batch_layout.wires_off[instance])
+    off += PROOF_LINK_WIRE_IDX * G
+    rec = bytes(proof_bytes[off:off + G])
+    if len(rec) != G:
+        raise kzg.SerializationError("truncated in wires_poly_comms[%d]" % PROOF_LINK_WIRE_IDX)
+    return rec
+
+
+def batch_verify_link_proofs(open_key_or_vk, links) -> bool:
+    """K proof links under one open key in one pass over the device and ONE pairing check.  open_key_or_vk: a keys.OpenKey or a
+    keys.VerifyingKey (its open key, its mode); links: [(lhs_record, rhs_record, link_proof_bytes, GroupLayout)].  One link is weighted by 1
+    -- PlonkKzgSnark::verify_link_proof as the reference checks it; several by the powers of a challenge drawn from every eta and every
+    opening proof (mzk_verifier_link_weights).  Raises keys.ProofEncodingError naming the lowest malformed link and its field."""
+    v = open_key_or_vk.verifier()
+    b = v.begin_links(links)
+    try:
+        A, B = b.finish(b.link_weights())
+    finally:
+        b.discard()
+    return v.check(A, B)
+
+
+def verify_link_proof(proof1_bytes, proof2_bytes, link_proof_bytes, layout: GroupLayout, open_key_or_vk) -> bool:
+    """PlonkKzgSnark::verify_link_proof (proof_linking.rs:240-286) on the serialized proofs: the two `Proof` images, the LinkingProof image and
+    the layout, under the open key of `open_key_or_vk` (keys.OpenKey or keys.VerifyingKey; images in its mode)."""
+    c, compress = open_key_or_vk.curve, open_key_or_vk.compressed
+    return batch_verify_link_proofs(open_key_or_vk, [(linking_wire_record(c, proof1_bytes, compress), linking_wire_record(c, proof2_bytes, compress),
+                                                      bytes(link_proof_bytes), layout)])

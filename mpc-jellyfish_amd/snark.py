@@ -329,12 +329,15 @@ def batch_prove(rng: _rng.ChaChaRng, circuits: list, pks: list, extra_transcript
     return core, _batch.serialize_batch_proof(circuits[0].curve, core)
 
 
-def batch_verify(vks, public_inputs, proofs, extra_msgs) -> bool:
+def batch_verify(vks, public_inputs, proofs, extra_msgs, links=None) -> bool:
     """PlonkKzgSnark::batch_verify (snark.rs:141-190) for single-instance proofs: vks are keys.VerifyingKey, proofs their serialized `Proof`s
     (the mode of each key), extra_msgs one Optional[bytes] per proof.  Proofs are grouped by key and each group goes through the device in
     one pass (keys.Verifier.begin); r is drawn from every proof's u in the CALLER's order (verifier.rs:203-215), the groups' (A, B) are
-    summed and checked by one product of two pairings.  Raises ValueError on mismatched lengths, an empty batch or differing open keys,
-    keys.ProofEncodingError on a malformed proof."""
+    summed and checked by one product of two pairings.  links: None, or [(i, j, link_proof_bytes, GroupLayout)] -- LinkingProofs
+    (PlonkKzgSnark::verify_link_proof, proof_linking.rs:240-286) between proofs i and j of this call: they go through the device as one more
+    group (keys.Verifier.begin_links), weighted by mzk_verifier_link_weights with this call's r, and their (A, B) joins the others' before
+    the one check.  Raises ValueError on mismatched lengths, an empty batch or differing open keys, keys.ProofEncodingError on a malformed
+    proof or link (.index: the proof, resp. the link)."""
     from . import lib as _lib
     import ctypes as C
     K = len(proofs)
@@ -359,11 +362,16 @@ def batch_verify(vks, public_inputs, proofs, extra_msgs) -> bool:
             b = vk.verifier().begin([proofs[i] for i in idx], [public_inputs[i] for i in idx], [extra_msgs[i] for i in idx])
             batches.append((vk, idx, b))
             u[idx] = b.u
+        if links:
+            from . import linking
+            wire = lambda i: linking.linking_wire_record(c, proofs[i], vks[i].compressed)
+            lb = vks[0].verifier().begin_links([(wire(i), wire(j), bytes(link), layout) for i, j, link, layout in links])
+            batches.append((None, None, lb))
         r = np.zeros(4, dtype=np.uint64)
         _lib.check(_lib.load().mzk_batch_verify_challenge(c.curve_id, C.c_void_p(u.ctypes.data), K, C.c_void_p(r.ctypes.data)), "mzk_batch_verify_challenge")
         r_int = fr_from_mont(c, r.reshape(1, 4))[0]
         weights = fr_to_mont(c, [pow(r_int, i, c.r) for i in range(K)])
-        results = [b.finish(weights[idx]) for _, idx, b in batches]
+        results = [b.finish(weights[idx] if idx is not None else b.link_weights(r)) for _, idx, b in batches]
     finally:
         for _, _, b in batches:
             b.discard()
