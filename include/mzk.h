@@ -226,12 +226,36 @@ MZK_API int32_t mzk_fr_encode_dev(int32_t curve_id, const void* d_in, uint64_t c
  * the sign of x).  Products compared with 1 do not see the difference.
  * mzk_batch_verify_challenge: r of batch_verify_opening_proofs (verifier.rs:203-215) from the K challenges u of the proofs (Montgomery Fr,
  * caller's order): 1 for K = 1; else a Merlin transcript "batch verify", K appends of u under "u" (32 B little-endian), 64 challenge
- * bytes under "r" reduced mod r (csrc/merlin.cuh, the transcript code of the device compiled for the host).  K = 0: MZK_ERR_INVALID_ARG. */
+ * bytes under "r" reduced mod r (csrc/merlin.cuh, the transcript code of the device compiled for the host).  K = 0: MZK_ERR_INVALID_ARG.
+ * mzk_batch_verify_challenge_t: the same r under the transcript kind that `flags` names -- 0: mzk_batch_verify_challenge; 
+ * MZK_TRANSCRIPT_SOLIDITY: 1 for K = 1, else one challenge of a SolidityTranscript (below) whose transcript is the K values u as 32 B
+ * little-endian canonical and whose state is zero.  Any other bit, K = 0: MZK_ERR_INVALID_ARG. */
 MZK_API int32_t mzk_g2_decode(int32_t curve_id, const uint8_t* bytes, uint32_t flags, uint64_t* out_xy_mont);
 MZK_API int32_t mzk_g2_mul(int32_t curve_id, const uint8_t* q_bytes, const uint64_t* k_canonical, uint32_t flags, uint8_t* out_bytes);
 MZK_API int32_t mzk_pairing_product_is_one(int32_t curve_id, const uint64_t* g1_xy_mont, const uint64_t* g2_xy_mont, uint64_t n, int32_t* out);
 MZK_API int32_t mzk_pairing_gt(int32_t curve_id, const uint64_t* g1_xy_mont, const uint64_t* g2_xy_mont, uint64_t* out);
 MZK_API int32_t mzk_batch_verify_challenge(int32_t curve_id, const uint64_t* u_mont, uint64_t K, uint64_t* out_r_mont);
+MZK_API int32_t mzk_batch_verify_challenge_t(int32_t curve_id, uint32_t flags, const uint64_t* u_mont, uint64_t K, uint64_t* out_r_mont);
+
+/* ---- the Keccak-256 transcript: SolidityTranscript (plonk/src/transcript/solidity.rs:31-78; csrc/keccak_transcript.cuh, one code for host and
+ * device), the transcript of proofs that an EVM-style keccak256 verifier checks.  The label of new() and of every append is dropped;
+ * `transcript` is the concatenation of the appended messages (the ark-serialize compressed bytes the Merlin transcript takes), `state` 64
+ * bytes, zero at first.  get_and_append_challenge: state = keccak256(state || transcript || 0x00) || keccak256(state || transcript || 0x01),
+ * challenge = state[0..48] little-endian mod r; the transcript is NOT cleared and the challenge is NOT appended, so every challenge hashes
+ * the whole transcript so far behind the new state.  An empty extra message therefore equals none.  keccak256 is sha3::Keccak256: rate 136,
+ * pad byte 0x01 (not SHA3's 0x06).
+ * MZK_TRANSCRIPT_SOLIDITY in `flags` of mzk_verifier_batch_begin, mzk_verifier_aggregate_begin and mzk_verifier_link_begin: the device's
+ * Fiat-Shamir stage runs this transcript instead of Merlin, over the same messages in the same order (one thread per proof, the transcript in
+ * a slot of device memory sized from the key's shape and the longest extra message; the two digests of a challenge share one absorption).
+ * Without the flag nothing changes; with challenges_mont / eta_mont given the flag has no effect.  One batch_verify uses one kind
+ * throughout: r comes from mzk_batch_verify_challenge_t with the same flag.
+ * Host-only (no GPU, no mzk_init), for hosts that write such proofs outside Rust:
+ * mzk_keccak256: out32 = keccak256(msg[0..len]) ("the quick brown fox jumps over the lazy dog" -> 865bf05c..14ec; "" -> c5d24601..a470).
+ * mzk_solidity_challenge: ONE get_and_append_challenge -- state64 (in, out: 64 zero bytes before the first challenge), the WHOLE transcript so
+ * far (len bytes, nullable when len = 0); *out_mont the challenge, Montgomery Fr. */
+#define MZK_TRANSCRIPT_SOLIDITY 4u
+MZK_API int32_t mzk_keccak256(const uint8_t* msg, uint64_t len, uint8_t* out32);
+MZK_API int32_t mzk_solidity_challenge(int32_t curve_id, uint8_t* state64, const uint8_t* transcript, uint64_t len, uint64_t* out_mont);
 
 /* ---- verifier: PlonkKzgSnark::batch_verify / verify (snark.rs:141-190, 653-671; verifier.rs:68-251) for single-instance `Proof`s of
  * TurboPlonk and UltraPlonk (csrc/verifier.cuh).  K >= 1 proofs under ONE verifying key go through the device in one
@@ -250,8 +274,8 @@ MZK_API int32_t mzk_batch_verify_challenge(int32_t curve_id, const uint64_t* u_m
  * mzk_verifier_batch_begin: K images of proof_len bytes each, back to back; public_inputs_canonical: K x num_inputs canonical integers of 4
  * limbs; extra_ranges (nullable: no proof has an extra transcript message): K pairs (begin, end) of byte offsets into extra_msgs, begin =
  * UINT64_MAX for a proof without one; challenges_mont (nullable): K x 7 Montgomery Fr (tau, beta, gamma, alpha, zeta, v, u) that REPLACE
- * the Merlin transcript -- for callers with another transcript (Solidity, Rescue); flags: MZK_SER_VALIDATE (subgroup checks of the proofs'
- * points).  On the host: proof_len, the Vec counts and the Option tag against the key's type.  On the device: A decode, B Fiat-Shamir, C
+ * the transcript -- for callers with another transcript (Rescue); flags: MZK_SER_VALIDATE (subgroup checks of the proofs' points),
+ * MZK_TRANSCRIPT_SOLIDITY (the Keccak-256 transcript instead of Merlin, above).  On the host: proof_len, the Vec counts and the Option tag against the key's type.  On the device: A decode, B Fiat-Shamir, C
  * scalars (one per base: repeated bases are summed).  *out_u_mont (nullable): the K challenges u, for mzk_batch_verify_challenge.
  * Any malformed proof: MZK_ERR_ENCODING, *out_bad_index (nullable) the LOWEST bad proof -- one 64-bit atomicMin, the same answer on every
  * run -- and mzk_last_error() "proof <i>: <field>: <reason>": a bad length, count or tag, a point (reasons of mzk_srs_register_serialized;
@@ -350,7 +374,7 @@ MZK_API int32_t mzk_verifier_aggregate_begin(const uint64_t* verifiers, uint32_t
  * records: K x 4 G1 records of that mode, per link lhs.wires_poly_comms[0] (PROOF_LINK_WIRE_IDX = 0), rhs.wires_poly_comms[0],
  * quotient_commitment, opening_proof -- the caller cuts the first two out of the two Plonk proof images.  layouts: K x 3 values (alignment,
  * offset, size).  eta_mont (nullable): K Montgomery Fr that REPLACE the transcript stage (the seam of challenges_mont); flags:
- * MZK_SER_VALIDATE (subgroup checks of the records); *out_eta_mont (nullable): the K challenges.  On the host, before anything is staged:
+ * MZK_SER_VALIDATE (subgroup checks of the records), MZK_TRANSCRIPT_SOLIDITY (eta from the Keccak-256 transcript); *out_eta_mont (nullable): the K challenges.  On the host, before anything is staged:
  * K = 0 and an alignment above the field's two-adicity (32 | 28): MZK_ERR_INVALID_ARG; a size above 2^27, the largest domain of the library:
  * MZK_ERR_UNSUPPORTED; offset + size beyond 2^alignment is accepted -- the roots wrap or repeat, as mzk_poly_div_roots_dev and the
  * reference's loop take them.  On the device: A decode (the decoder of the proofs), Bl the transcript "PlonkLinkingProof" (the two wire
@@ -938,8 +962,9 @@ MZK_API int32_t mzk_dev_memset2d(void* dptr, uint64_t pitch, int32_t value, uint
 /* ---- measurement hooks (bench.py): HIP-event timing of the library's own kernels ---- */
 /* on != 0: every subsequent call brackets its dominant kernels with hipEvents on the launch stream. */
 MZK_API int32_t mzk_profile_enable(int32_t on);
-/* name: "msm_accumulate", "msm_total", "ntt_pass", "ntt_total", "vfy_link_transcript", "vfy_link_vanishing" (the two
- * kernels of mzk_verifier_link_begin; read them on the device the verifier lives on).  Returns accumulated device
+/* name: "msm_accumulate", "msm_total", "ntt_pass", "ntt_total", "vfy_transcript" (stage B of mzk_verifier_batch_begin, either
+ * transcript kind), "vfy_link_transcript", "vfy_link_vanishing" (the two kernels of mzk_verifier_link_begin); read the
+ * verifier's regions on the device the verifier lives on.  Returns accumulated device
  * milliseconds and launch count since the last reset (synchronises the recorded events). */
 MZK_API int32_t mzk_profile_get(const char* name, double* out_ms, uint64_t* out_count);
 MZK_API int32_t mzk_profile_reset(void);

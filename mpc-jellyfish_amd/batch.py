@@ -45,7 +45,8 @@ def _pt(c, cm: kzg.Commitment):
     return (x, y)
 
 
-def batch_prove(provers, wire_values: list, pub_inputs: list, blinds: list, quot_blinders: list, extra_transcript_init_msg: bytes | None = None):
+def batch_prove(provers, wire_values: list, pub_inputs: list, blinds: list, quot_blinders: list, extra_transcript_init_msg: bytes | None = None,
+                transcript: str = "merlin"):
     """PlonkKzgSnark::batch_prove (snark.rs:64-78, 201-469) over K native handles: rounds 1 - 2.5 and 4 per instance, rounds 3 and 5
     once over all handles.  pub_inputs[k]: instance k's public input as ints, on rows 0.. of its circuit.  Returns batch.BatchProofCore.
     One circuit several times in the aggregate -- the reference's `prove_keys` with one key repeated -- is `[pk, pk.fork(), pk.fork()]`:
@@ -68,7 +69,7 @@ def batch_prove(provers, wire_values: list, pub_inputs: list, blinds: list, quot
         if p.curve.curve_id != c.curve_id:
             raise ValueError("instances over different curves")
     pt = lambda cm: _pt(c, cm)
-    t = _transcript.StandardTranscript(c, b"PlonkProof")
+    t = _transcript.new(transcript, c, b"PlonkProof")
     if extra_transcript_init_msg is not None:
         t.append_message(b"extra info", extra_transcript_init_msg)
     for p, pub in zip(provers, pub_inputs):

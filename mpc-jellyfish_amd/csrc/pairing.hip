@@ -2,6 +2,7 @@
 // final check and its batch challenge r.  No kernel, no HIP call: they run without a GPU and before mzk_init, like mzk_key_layout.
 #include "internal.hpp"
 #include "hostpairing.hpp"
+#include "keccak_transcript.cuh"
 #include "merlin.cuh"
 
 namespace mzk {
@@ -91,6 +92,35 @@ void batch_challenge_t(const uint64_t* u_mont, uint64_t K, uint64_t* out) {
     std::memcpy(out, r.l, sizeof r.l);
 }
 
+// the first 48 bytes of a Solidity transcript's state, little-endian, mod r (solidity.rs:74-76), Montgomery
+template <class FrP>
+void solidity_reduce_t(const uint8_t* state64, uint64_t* out) {
+    using F = Fp64<FrP>;
+    F lo = F::zero(), hi = F::zero(), r2;
+    for (int s = 0; s < 32; s++) lo.l[s >> 3] |= (uint64_t)state64[s] << (8 * (s & 7));
+    for (int s = 0; s < 16; s++) hi.l[s >> 3] |= (uint64_t)state64[32 + s] << (8 * (s & 7));
+    for (int i = 0; i < 4; i++) r2.l[i] = F::c64(FrP::R2, i);
+    while (F::geq_mod(lo.l)) F::sub_mod(lo.l);
+    const F r = lo * r2 + (hi * r2) * r2;                                // (hi < 2^128 < r)
+    std::memcpy(out, r.l, sizeof r.l);
+}
+// verifier.rs:203-215 with T = SolidityTranscript: the K values u as the whole transcript, one challenge
+template <class FrP>
+void batch_challenge_solidity_t(const uint64_t* u_mont, uint64_t K, uint64_t* out) {
+    using F = Fp64<FrP>;
+    if (K == 1) { const F one = F::one(); std::memcpy(out, one.l, sizeof one.l); return; }
+    std::vector<uint8_t> tr(K * 32);
+    for (uint64_t i = 0; i < K; i++) {
+        F u;
+        std::memcpy(u.l, u_mont + 4 * i, sizeof u.l);
+        const auto v = h64::canonical(u);
+        for (int s = 0; s < 32; s++) tr[i * 32 + s] = (uint8_t)(v[s >> 3] >> (8 * (s & 7)));
+    }
+    uint8_t state[64] = {0};
+    keccak::solidity_squeeze_bytes(state, tr.data(), tr.size());
+    solidity_reduce_t<FrP>(state, out);
+}
+
 }  // namespace
 }  // namespace mzk
 
@@ -125,5 +155,28 @@ extern "C" int32_t mzk_batch_verify_challenge(int32_t curve_id, const uint64_t* 
     if (!valid_curve(curve_id) || !u_mont || !K || !out_r_mont) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     if (curve_id == MZK_CURVE_BLS12_381) batch_challenge_t<BlsFr>(u_mont, K, out_r_mont);
     else batch_challenge_t<BnFr>(u_mont, K, out_r_mont);
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_batch_verify_challenge_t(int32_t curve_id, uint32_t flags, const uint64_t* u_mont, uint64_t K, uint64_t* out_r_mont) {
+    if (flags & ~MZK_TRANSCRIPT_SOLIDITY) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (!(flags & MZK_TRANSCRIPT_SOLIDITY)) return mzk_batch_verify_challenge(curve_id, u_mont, K, out_r_mont);
+    if (!valid_curve(curve_id) || !u_mont || !K || !out_r_mont) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (curve_id == MZK_CURVE_BLS12_381) batch_challenge_solidity_t<BlsFr>(u_mont, K, out_r_mont);
+    else batch_challenge_solidity_t<BnFr>(u_mont, K, out_r_mont);
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_keccak256(const uint8_t* msg, uint64_t len, uint8_t* out32) {
+    if ((!msg && len) || !out32) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    keccak::keccak256(msg, len, out32);
+    return MZK_OK;
+}
+
+extern "C" int32_t mzk_solidity_challenge(int32_t curve_id, uint8_t* state64, const uint8_t* transcript, uint64_t len, uint64_t* out_mont) {
+    if (!valid_curve(curve_id) || !state64 || (!transcript && len) || !out_mont) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    keccak::solidity_squeeze_bytes(state64, transcript, len);
+    if (curve_id == MZK_CURVE_BLS12_381) solidity_reduce_t<BlsFr>(state64, out_mont);
+    else solidity_reduce_t<BnFr>(state64, out_mont);
     return MZK_OK;
 }

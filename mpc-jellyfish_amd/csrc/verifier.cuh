@@ -2,7 +2,8 @@
 // ONE verifying key, staged as K images of proof_len bytes.  Aggregated BatchProofs under a tuple of keys: the second half of this file;
 // proof links (verify_link_proof): its last section.
 //   A  vfy_decode_kernel      one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array
-//   B  vfy_transcript_kernel  one thread per proof: the Merlin transcript of compute_challenges (verifier.rs:274-319) -> 7 challenges
+//   B  vfy_transcript_kernel  one thread per proof: the transcript of compute_challenges (verifier.rs:274-319) -> 7 challenges; T is
+//                             merlin::Transcript (StandardTranscript) or keccak::SolidityTranscript (MZK_TRANSCRIPT_SOLIDITY)
 //   C  vfy_scalars_kernel     one thread per proof: prepare_pcs_info for one instance (verifier.rs:122-184, 340-733) -> one scalar per base
 //   finish                    vfy_weight_kernel / vfy_colsum_kernel: rows weighted by r^i, the key's columns summed by a fixed tree
 // Base array (boundary form, what mzk_srs_register_dev takes): [ key bases | proof 0's points | proof 1's points | .. ]
@@ -16,6 +17,7 @@
 #include "fp.cuh"
 #include "fp_inv.cuh"
 #include "key_io.cuh"                                              // fr_read_record
+#include "keccak_transcript.cuh"
 #include "merlin.cuh"
 #include "srs_io.cuh"
 
@@ -75,26 +77,36 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_decode_kernel(const uint8_t* 
 // ---- B -------------------------------------------------------------------------------------------------------------------------------
 // 64 challenge bytes (little-endian) mod r, Montgomery: lo + 2^256 hi, each half brought below r by subtraction (2^256 < 6 r)
 template <class P>
-MZK_D Fp<P> vfy_reduce_challenge(const uint8_t* ch) {
-    Fp<P> lo = Fp<P>::zero(), hi = Fp<P>::zero();
-#pragma unroll
-    for (int s = 0; s < 32; s++) { lo.l[s >> 2] |= (uint32_t)ch[s] << (8 * (s & 3)); hi.l[s >> 2] |= (uint32_t)ch[32 + s] << (8 * (s & 3)); }
+MZK_D Fp<P> vfy_reduce_halves(Fp<P> lo, Fp<P> hi) {
     while (!ser_below_modulus<P>(lo.l)) sub_limbs<P::N>(lo.l, lo.l, P::MOD);
     while (!ser_below_modulus<P>(hi.l)) sub_limbs<P::N>(hi.l, hi.l, P::MOD);
     return to_mont(lo) + to_mont(to_mont(hi));
 }
-MZK_D void vfy_absorb_global(merlin::Transcript& t, const uint8_t* __restrict__ p, uint32_t n) {
+template <class P>
+MZK_D Fp<P> vfy_reduce_challenge(const uint8_t* ch) {
+    Fp<P> lo = Fp<P>::zero(), hi = Fp<P>::zero();
+#pragma unroll
+    for (int s = 0; s < 32; s++) { lo.l[s >> 2] |= (uint32_t)ch[s] << (8 * (s & 3)); hi.l[s >> 2] |= (uint32_t)ch[32 + s] << (8 * (s & 3)); }
+    return vfy_reduce_halves<P>(lo, hi);
+}
+template <class T>
+constexpr bool VFY_SOLIDITY = false;                             // the transcript kinds of stage B: Merlin (StandardTranscript) unless stated
+template <>
+constexpr bool VFY_SOLIDITY<keccak::SolidityTranscript> = true;
+template <class T>
+MZK_D void vfy_absorb_global(T& t, const uint8_t* __restrict__ p, uint32_t n) {
     for (uint32_t i = 0; i < n; i++) t.absorb_byte(p[i]);
 }
-MZK_D void vfy_absorb_words(merlin::Transcript& t, const uint32_t (&w)[8]) {      // 32 bytes, little-endian (an Fr record)
+template <class T>
+MZK_D void vfy_absorb_words(T& t, const uint32_t (&w)[8]) {      // 32 bytes, little-endian (an Fr record)
 #pragma unroll
     for (int k = 0; k < 8; k++)
         for (int b = 0; b < 32; b += 8) t.absorb_byte(w[k] >> b);
 }
 // a G1 record of the image enters the transcript in its COMPRESSED form: as it stands, or rebuilt from an uncompressed record (x's bytes,
 // the infinity flag, and "y is the larger" = y > (q - 1) / 2)
-template <class X>
-MZK_D void vfy_append_g1(merlin::Transcript& t, const char* label, uint32_t label_len, const uint8_t* __restrict__ rec, bool compressed) {
+template <class X, class T>
+MZK_D void vfy_append_g1(T& t, const char* label, uint32_t label_len, const uint8_t* __restrict__ rec, bool compressed) {
     constexpr int B = SerFmt<X>::BYTES;
     constexpr bool BLS = SerFmt<X>::BE;
     t.append_begin(label, label_len, B);
@@ -118,47 +130,88 @@ MZK_D void vfy_append_g1(merlin::Transcript& t, const char* label, uint32_t labe
         t.absorb_byte(b);
     }
 }
-template <class P>
-MZK_D Fp<P> vfy_challenge(merlin::Transcript& t, const char* label, uint32_t label_len) {
-    uint8_t ch[64];
-    t.challenge_bytes(label, label_len, ch, 64);
-    const Fp<P> c = vfy_reduce_challenge<P>(ch);
-    const Fp<P> v = from_mont(c);
-    t.append_begin(label, label_len, 32);
-    vfy_absorb_words(t, v.l);
-    return c;
+// get_and_append_challenge.  The Solidity transcript only records the point (nothing is appended, solidity.rs:59-77): its challenges are
+// hashed together at the kernel's end (vfy_store_challenges) and the value returned here is not one
+template <class P, class T>
+MZK_D Fp<P> vfy_challenge(T& t, const char* label, uint32_t label_len) {
+    if constexpr (VFY_SOLIDITY<T>) {
+        t.mark();
+        return Fp<P>::zero();
+    } else {
+        uint8_t ch[64];
+        t.challenge_bytes(label, label_len, ch, 64);
+        const Fp<P> c = vfy_reduce_challenge<P>(ch);
+        const Fp<P> v = from_mont(c);
+        t.append_begin(label, label_len, 32);
+        vfy_absorb_words(t, v.l);
+        return c;
+    }
 }
 
+// A thread's n challenges to out[8 k ..]: Merlin's are in ch; the Solidity transcript hashes its recorded prefixes now, each challenge
+// the first 48 bytes of the new state, reduced as the 64 of Merlin with the high 16 zero
+template <class P, class T>
+MZK_D void vfy_store_challenges(T& t, const Fp<P>* ch, int n, uint32_t* __restrict__ out) {
+    if constexpr (VFY_SOLIDITY<T>) {
+        t.squeeze_all([&](uint32_t k, const uint64_t (&st)[keccak::STATE_WORDS]) {
+            Fp<P> lo = Fp<P>::zero(), hi = Fp<P>::zero();
+#pragma unroll
+            for (int j = 0; j < 4; j++) { lo.l[2 * j] = (uint32_t)st[j]; lo.l[2 * j + 1] = (uint32_t)(st[j] >> 32); }
+#pragma unroll
+            for (int j = 0; j < 2; j++) { hi.l[2 * j] = (uint32_t)st[4 + j]; hi.l[2 * j + 1] = (uint32_t)(st[4 + j] >> 32); }
+            store_fp<P>(out + k * 8ull, vfy_reduce_halves<P>(lo, hi));
+        });
+    } else {
+        for (int k = 0; k < n; k++) store_fp<P>(out + k * 8ull, ch[k]);
+    }
+}
 // script: the appends of append_vk_and_pub_input up to the public inputs, as items { label_len u8, msg_len u8, label, msg }, n_items of them
-template <class P, class X>
+// (the Solidity transcript drops the labels and the lengths: it takes the messages alone)
+template <class T>
+MZK_D const uint8_t* vfy_append_script(T& t, const uint8_t* __restrict__ s, uint32_t n_items) {
+    for (uint32_t k = 0; k < n_items; k++) {
+        const uint32_t ll = s[0], ml = s[1];
+        if constexpr (!VFY_SOLIDITY<T>) {
+            t.begin_op(merlin::F_M | merlin::F_A);
+            vfy_absorb_global(t, s + 2, ll);
+            t.absorb_u32le(ml);
+            t.begin_op(merlin::F_A);
+        }
+        vfy_absorb_global(t, s + 2 + ll, ml);
+        s += 2 + ll + ml;
+    }
+    return s;
+}
+// A thread's transcript.  Merlin: 25 lanes in LDS (`lanes`), interleaved among the block's threads.  Solidity: a slot of slot_words words in
+// device memory, [ state | transcript ], interleaved among the block's 64 threads: word j of thread t at slots[(block * slot_words + j) * 64 + t]
+template <class T>
+constexpr int VFY_LDS_LANES = VFY_SOLIDITY<T> ? 1 : 25 * VFY_THREADS;
+template <class T>
+MZK_D void vfy_transcript_init(T& t, uint64_t* lanes, uint64_t* slots, uint32_t slot_words, const char* label, uint32_t label_len) {
+    if constexpr (VFY_SOLIDITY<T>) t.init(slots + (unsigned long long)blockIdx.x * slot_words * VFY_THREADS + threadIdx.x, VFY_THREADS, slot_words);
+    else t.init(lanes + threadIdx.x, VFY_THREADS, label, label_len);
+}
+template <class P, class X, class T = merlin::Transcript>
 __global__ __launch_bounds__(VFY_THREADS) void vfy_transcript_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyShape sh,
                                                                      const uint8_t* __restrict__ script, uint32_t n_items,
                                                                      const uint32_t* __restrict__ pub_inputs /* K x num_inputs canonical */,
                                                                      const uint8_t* __restrict__ extra, const unsigned long long* __restrict__ extra_range,
-                                                                     uint32_t* __restrict__ challenges, unsigned long long* __restrict__ err) {
-    __shared__ uint64_t lanes[25 * VFY_THREADS];
+                                                                     uint32_t* __restrict__ challenges, unsigned long long* __restrict__ err,
+                                                                     uint64_t* slots, uint32_t slot_words) {
+    __shared__ uint64_t lanes[VFY_LDS_LANES<T>];
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= K) return;
     const uint8_t* img = images + i * sh.proof_len;
     const uint32_t G = sh.g1_bytes;
     const bool cmp = sh.compressed;
-    merlin::Transcript t;
-    t.init(lanes + threadIdx.x, VFY_THREADS, VFY_LBL("PlonkProof"));
+    T t;
+    vfy_transcript_init(t, lanes, slots, slot_words, VFY_LBL("PlonkProof"));
     if (extra_range && extra_range[2 * i] != ~0ull) {
         const unsigned long long b = extra_range[2 * i], e = extra_range[2 * i + 1];
         t.append_begin(VFY_LBL("extra info"), (uint32_t)(e - b));
         vfy_absorb_global(t, extra + b, (uint32_t)(e - b));
     }
-    const uint8_t* s = script;
-    for (uint32_t k = 0; k < n_items; k++) {
-        const uint32_t ll = s[0], ml = s[1];
-        t.begin_op(merlin::F_M | merlin::F_A);
-        vfy_absorb_global(t, s + 2, ll);
-        t.absorb_u32le(ml);
-        t.begin_op(merlin::F_A);
-        vfy_absorb_global(t, s + 2 + ll, ml);
-        s += 2 + ll + ml;
-    }
+    vfy_append_script(t, script, n_items);
     for (uint32_t k = 0; k < sh.num_inputs; k++) {
         const uint32_t* w = pub_inputs + (i * sh.num_inputs + k) * 8ull;
         uint32_t v[8];
@@ -198,8 +251,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_transcript_kernel(const uint8
     vfy_append_g1<X>(t, VFY_LBL("open_proof"), img + sh.pt_off[2 * W + 1], cmp);
     vfy_append_g1<X>(t, VFY_LBL("shifted_open_proof"), img + sh.pt_off[2 * W + 2], cmp);
     ch[6] = vfy_challenge<P>(t, VFY_LBL("u"));
-#pragma unroll
-    for (int k = 0; k < 7; k++) store_fp<P>(challenges + (i * 7 + k) * 8ull, ch[k]);
+    vfy_store_challenges<P>(t, ch, 7, challenges + i * 7 * 8ull);
 }
 
 // ---- C -------------------------------------------------------------------------------------------------------------------------------
@@ -437,37 +489,28 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_decode_kernel(const uint8
     }
 }
 
-template <class P, class X>
+template <class P, class X, class T = merlin::Transcript>
 __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_transcript_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyAggShape sh,
                                                                          const uint8_t* __restrict__ script, const uint32_t* __restrict__ pos_tab,
                                                                          const uint32_t* __restrict__ pub_inputs /* K x total_inputs canonical */,
                                                                          const uint8_t* __restrict__ extra, const unsigned long long* __restrict__ extra_range,
-                                                                         uint32_t* __restrict__ challenges) {
-    __shared__ uint64_t lanes[25 * VFY_THREADS];
+                                                                         uint32_t* __restrict__ challenges, uint64_t* slots, uint32_t slot_words) {
+    __shared__ uint64_t lanes[VFY_LDS_LANES<T>];
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= K) return;
     const uint8_t* img = images + i * sh.proof_len;
     const uint32_t G = sh.g1_bytes, W = sh.W, m = sh.m;
     const bool cmp = sh.compressed;
-    merlin::Transcript t;
-    t.init(lanes + threadIdx.x, VFY_THREADS, VFY_LBL("PlonkProof"));
+    T t;
+    vfy_transcript_init(t, lanes, slots, slot_words, VFY_LBL("PlonkProof"));
     if (extra_range && extra_range[2 * i] != ~0ull) {
         const unsigned long long b = extra_range[2 * i], e = extra_range[2 * i + 1];
         t.append_begin(VFY_LBL("extra info"), (uint32_t)(e - b));
         vfy_absorb_global(t, extra + b, (uint32_t)(e - b));
     }
     for (uint32_t j = 0; j < m; j++) {                            // append_vk_and_pub_input, position by position
-        const uint8_t* s = script + pos_tab[3 * j];
-        const uint32_t n_items = pos_tab[3 * j + 1], p0 = pos_tab[3 * j + 2], p1 = pos_tab[3 * j + 5];
-        for (uint32_t k = 0; k < n_items; k++) {
-            const uint32_t ll = s[0], ml = s[1];
-            t.begin_op(merlin::F_M | merlin::F_A);
-            vfy_absorb_global(t, s + 2, ll);
-            t.absorb_u32le(ml);
-            t.begin_op(merlin::F_A);
-            vfy_absorb_global(t, s + 2 + ll, ml);
-            s += 2 + ll + ml;
-        }
+        const uint32_t p0 = pos_tab[3 * j + 2], p1 = pos_tab[3 * j + 5];
+        vfy_append_script(t, script + pos_tab[3 * j], pos_tab[3 * j + 1]);
         for (uint32_t k = p0; k < p1; k++) {
             const uint32_t* w = pub_inputs + (i * sh.total_inputs + k) * 8ull;
             uint32_t v[8];
@@ -513,8 +556,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_transcript_kernel(const u
     vfy_append_g1<X>(t, VFY_LBL("open_proof"), img + sh.quot_off + W * G, cmp);
     vfy_append_g1<X>(t, VFY_LBL("shifted_open_proof"), img + sh.quot_off + (W + 1) * G, cmp);
     ch[6] = vfy_challenge<P>(t, VFY_LBL("u"));
-#pragma unroll
-    for (int k = 0; k < 7; k++) store_fp<P>(challenges + (i * 7 + k) * 8ull, ch[k]);
+    vfy_store_challenges<P>(t, ch, 7, challenges + i * 7 * 8ull);
 }
 
 // an Fr record of the image: its range check (stage C makes one pass over an instance's records) and its value
@@ -713,20 +755,22 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_fold_kernel(unsigned long
 //   Bl vfy_link_transcript_kernel one thread per link: eta (proof_linking.rs:185-197)
 //   Cl vfy_link_vanishing_kernel  one wave per link: Z_D(eta) (:162-176) and the link's row
 //   finish                        vfy_weight_kernel<P, 1> (one A base per link), vfy_colsum_kernel over the one key column
-template <class P, class X>
+template <class P, class X, class T = merlin::Transcript>
 __global__ __launch_bounds__(VFY_THREADS) void vfy_link_transcript_kernel(const uint8_t* __restrict__ records, unsigned long long K, uint32_t g1_bytes,
-                                                                          uint32_t compressed, uint32_t* __restrict__ eta) {
-    __shared__ uint64_t lanes[25 * VFY_THREADS];
+                                                                          uint32_t compressed, uint32_t* __restrict__ eta, uint64_t* slots,
+                                                                          uint32_t slot_words) {
+    __shared__ uint64_t lanes[VFY_LDS_LANES<T>];
     const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= K) return;
     const uint8_t* rec = records + i * 4ull * g1_bytes;
     const bool cmp = compressed;
-    merlin::Transcript t;
-    t.init(lanes + threadIdx.x, VFY_THREADS, VFY_LBL("PlonkLinkingProof"));
+    T t;
+    vfy_transcript_init(t, lanes, slots, slot_words, VFY_LBL("PlonkLinkingProof"));
     vfy_append_g1<X>(t, VFY_LBL("linking_wire_comms"), rec, cmp);
     vfy_append_g1<X>(t, VFY_LBL("linking_wire_comms"), rec + g1_bytes, cmp);
     vfy_append_g1<X>(t, VFY_LBL("quotient_comm"), rec + 2 * g1_bytes, cmp);
-    store_fp<P>(eta + i * 8ull, vfy_challenge<P>(t, VFY_LBL("eta")));
+    const Fp<P> ch = vfy_challenge<P>(t, VFY_LBL("eta"));
+    vfy_store_challenges<P>(t, &ch, 1, eta + i * 8ull);
 }
 
 // Link i, one wave: Z_D(eta) = prod_{k < size} (eta - g^(offset + k)), g the 2^alignment-th root of unity of the NTT (GroupLayout::

@@ -275,6 +275,20 @@ bool proof_container_ok(const VfyShape& sh, const uint8_t* img, std::string& why
     return !sh.ultra || expect("plookup_proof.h_poly_comms", sh.perm_next_off + 33, 2);
 }
 
+// Stage B under MZK_TRANSCRIPT_SOLIDITY keeps each transcript in a slot of device memory (verifier.cuh, vfy_transcript_init): the 64 bytes of
+// the state, at most `transcript_bytes` of transcript and the recorded challenge points, for every thread of the ceil(K / 64) blocks.
+uint64_t longest_extra(const uint64_t* extra_ranges, uint64_t K) {
+    uint64_t longest = 0;
+    if (extra_ranges)
+        for (uint64_t i = 0; i < K; i++)
+            if (extra_ranges[2 * i] != ~0ull) longest = std::max(longest, extra_ranges[2 * i + 1] - extra_ranges[2 * i]);
+    return longest;
+}
+int32_t alloc_slots(DevOwned& slots, uint64_t K, uint64_t transcript_bytes, uint32_t& slot_words) {
+    slot_words = keccak::SolidityTranscript::slot_words(transcript_bytes);
+    return slots.alloc((K + VFY_THREADS - 1) / VFY_THREADS * VFY_THREADS * slot_words * 8);
+}
+
 int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub, const uint8_t* extra,
                     const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags, uint64_t* out_batch, uint64_t* out_u, uint64_t* out_bad) {
     const Verifier& v = *vp;
@@ -338,16 +352,29 @@ int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, 
     HIP_TRY(hipGetLastError());
     // B, or the caller's challenges
     const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+    DevOwned slots;                                                   // Solidity: the transcripts' memory, freed when the stages are through
     if (challenges) {
         HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
     } else {
+        ProfScope ps("vfy_transcript", nullptr, v.device);
         const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
-        if (curve == MZK_CURVE_BLS12_381)
-            hipLaunchKernelGGL((vfy_transcript_kernel<BlsFr, BlsFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.script.as<uint8_t>(),
-                               v.n_items, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), err);
-        else
-            hipLaunchKernelGGL((vfy_transcript_kernel<BnFr, BnFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.script.as<uint8_t>(),
-                               v.n_items, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), err);
+        const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
+        uint32_t slot_words = 0;
+        // (the script's length bounds its messages; the proof's own: np commitments in compressed form, 2 W (+ 6) evaluations)
+        if (solidity)
+            MZK_TRY(alloc_slots(slots, K, longest_extra(extra_ranges, K) + v.script_len + 32ull * sh.num_inputs + (uint64_t)np * g1_bytes(curve, true) +
+                                              32ull * (2 * sh.W + 6), slot_words));
+#define MZK_VFY_TRANSCRIPT(Fr, FqX, T)                                                                                                                        \
+    hipLaunchKernelGGL((vfy_transcript_kernel<Fr, FqX, T>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.script.as<uint8_t>(), \
+                       v.n_items, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), err, slots.as<uint64_t>(), slot_words)
+        if (curve == MZK_CURVE_BLS12_381) {
+            if (solidity) MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, keccak::SolidityTranscript);
+            else MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, merlin::Transcript);
+        } else {
+            if (solidity) MZK_VFY_TRANSCRIPT(BnFr, BnFqX, keccak::SolidityTranscript);
+            else MZK_VFY_TRANSCRIPT(BnFr, BnFqX, merlin::Transcript);
+        }
+#undef MZK_VFY_TRANSCRIPT
         HIP_TRY(hipGetLastError());
     }
     // C
@@ -664,17 +691,28 @@ int32_t aggregate_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const 
     if (curve == MZK_CURVE_BLS12_381) launch_agg_decode<BlsFqX>(ag.compressed, validate, b->images.as<uint8_t>(), K, ag, *b, bases, b->inf.as<uint32_t>() + nkey, err);
     else launch_agg_decode<BnFqX>(ag.compressed, validate, b->images.as<uint8_t>(), K, ag, *b, bases, b->inf.as<uint32_t>() + nkey, err);
     HIP_TRY(hipGetLastError());
+    DevOwned slots;                                                   // Solidity: the transcripts' memory, freed when the stages are through
     if (challenges) {
         HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
     } else {
         const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
         const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
-        if (curve == MZK_CURVE_BLS12_381)
-            hipLaunchKernelGGL((vfy_agg_transcript_kernel<BlsFr, BlsFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, ag, b->script.as<uint8_t>(),
-                               b->pos_tab.as<uint32_t>(), b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>());
-        else
-            hipLaunchKernelGGL((vfy_agg_transcript_kernel<BnFr, BnFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, ag, b->script.as<uint8_t>(),
-                               b->pos_tab.as<uint32_t>(), b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>());
+        const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
+        uint32_t slot_words = 0;
+        if (solidity)
+            MZK_TRY(alloc_slots(slots, K, longest_extra(extra_ranges, K) + script_len + 32ull * ag.total_inputs + (uint64_t)np * g1_bytes(curve, true) +
+                                              32ull * m * (2 * W + 6), slot_words));
+#define MZK_VFY_TRANSCRIPT(Fr, FqX, T)                                                                                                                           \
+    hipLaunchKernelGGL((vfy_agg_transcript_kernel<Fr, FqX, T>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, ag, b->script.as<uint8_t>(), \
+                       b->pos_tab.as<uint32_t>(), b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), slots.as<uint64_t>(), slot_words)
+        if (curve == MZK_CURVE_BLS12_381) {
+            if (solidity) MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, keccak::SolidityTranscript);
+            else MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, merlin::Transcript);
+        } else {
+            if (solidity) MZK_VFY_TRANSCRIPT(BnFr, BnFqX, keccak::SolidityTranscript);
+            else MZK_VFY_TRANSCRIPT(BnFr, BnFqX, merlin::Transcript);
+        }
+#undef MZK_VFY_TRANSCRIPT
         HIP_TRY(hipGetLastError());
     }
     if (curve == MZK_CURVE_BLS12_381) launch_agg_scalars<BlsFr>(*b, K, ag, proof_rows, err);
@@ -800,17 +838,26 @@ int32_t link_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, 
     HIP_TRY(hipMemcpy2DAsync(b->a_bases.p, pt_bytes, own_bases + 3 * pt_bytes, 4 * pt_bytes, pt_bytes, K, hipMemcpyDeviceToDevice, nullptr));
     HIP_TRY(hipMemcpy2DAsync(b->a_inf.p, 4, b->inf.as<uint32_t>() + nkey + 3, 16, 4, K, hipMemcpyDeviceToDevice, nullptr));
     // Bl, or the caller's eta
+    DevOwned slots;                                                   // Solidity: the transcripts' memory, freed when the stages are through
     if (eta) {
         HIP_TRY(hipMemcpy(b->chal.p, eta, K * 32, hipMemcpyHostToDevice));
     } else {
         ProfScope ps("vfy_link_transcript", nullptr, v.device);
         const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
-        if (curve == MZK_CURVE_BLS12_381)
-            hipLaunchKernelGGL((vfy_link_transcript_kernel<BlsFr, BlsFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, G, v.sh.compressed,
-                               b->chal.as<uint32_t>());
-        else
-            hipLaunchKernelGGL((vfy_link_transcript_kernel<BnFr, BnFqX>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, G, v.sh.compressed,
-                               b->chal.as<uint32_t>());
+        const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
+        uint32_t slot_words = 0;
+        if (solidity) MZK_TRY(alloc_slots(slots, K, 3ull * g1_bytes(curve, true), slot_words));
+#define MZK_VFY_TRANSCRIPT(Fr, FqX, T)                                                                                                                      \
+    hipLaunchKernelGGL((vfy_link_transcript_kernel<Fr, FqX, T>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, G, v.sh.compressed, \
+                       b->chal.as<uint32_t>(), slots.as<uint64_t>(), slot_words)
+        if (curve == MZK_CURVE_BLS12_381) {
+            if (solidity) MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, keccak::SolidityTranscript);
+            else MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, merlin::Transcript);
+        } else {
+            if (solidity) MZK_VFY_TRANSCRIPT(BnFr, BnFqX, keccak::SolidityTranscript);
+            else MZK_VFY_TRANSCRIPT(BnFr, BnFqX, merlin::Transcript);
+        }
+#undef MZK_VFY_TRANSCRIPT
         HIP_TRY(hipGetLastError());
     }
     // Cl
@@ -930,7 +977,7 @@ extern "C" int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* pr
                                             uint64_t* out_batch, uint64_t* out_u_mont, uint64_t* out_bad_index) {
     ON_DEVICE_OF(verifier, v, find_verifier);
     if (v->open_only) { set_error("the verifier holds no verifying key"); return MZK_ERR_INVALID_ARG; }
-    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->sh.num_inputs && !public_inputs_canonical) || (flags & ~MZK_SER_VALIDATE)) {
+    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->sh.num_inputs && !public_inputs_canonical) || (flags & ~(MZK_SER_VALIDATE | MZK_TRANSCRIPT_SOLIDITY))) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
     }
@@ -981,7 +1028,7 @@ extern "C" int32_t mzk_verifier_aggregate_begin(const uint64_t* verifiers, uint3
     MZK_TRY(guard_status(guard));
     std::vector<std::shared_ptr<Verifier>> vs;                        // declared after the guard: a last reference drops while that device is bound
     MZK_TRY(find_tuple(verifiers, m, vs));
-    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (flags & ~MZK_SER_VALIDATE)) {
+    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (flags & ~(MZK_SER_VALIDATE | MZK_TRANSCRIPT_SOLIDITY))) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
     }
@@ -1048,7 +1095,7 @@ extern "C" int32_t mzk_verifier_create_open_key(int32_t curve_id, const uint8_t*
 extern "C" int32_t mzk_verifier_link_begin(uint64_t verifier, const uint8_t* records, uint64_t K, const uint64_t* layouts, const uint64_t* eta_mont, uint32_t flags,
                                            uint64_t* out_batch, uint64_t* out_eta_mont, uint64_t* out_bad_index) {
     ON_DEVICE_OF(verifier, v, find_verifier);
-    if (!records || !K || K >= (1ull << 24) || !layouts || !out_batch || (flags & ~MZK_SER_VALIDATE)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    if (!records || !K || K >= (1ull << 24) || !layouts || !out_batch || (flags & ~(MZK_SER_VALIDATE | MZK_TRANSCRIPT_SOLIDITY))) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     return link_begin(v, records, K, layouts, eta_mont, flags, out_batch, out_eta_mont, out_bad_index);
 }
 

@@ -4,6 +4,7 @@
 //   jf_utils::test_rng / F::rand / DensePolynomial::rand      utilities/src/lib.rs:62-70 [+ upstream ark-ff, rand_chacha]
 //   compute_coset_representatives                            relation/src/constants.rs:30-80
 //   StandardTranscript over merlin                           plonk/src/transcript/standard.rs:16-46, transcript/mod.rs:45-214
+//   SolidityTranscript over Keccak-256, PlonkTranscript      plonk/src/transcript/solidity.rs:31-78 (either kind behind one interface)
 //   gen_circuit_for_bench + finalize_for_arithmetization     plonk/benches/bench.rs:29-46, relation/src/constraint_system.rs:195-225, 743-778, 966-999
 //   PlonkKzgSnark::{preprocess, prove}                       plonk/src/proof_system/snark.rs:201-469, 529-651
 //   Prover::run_*_round, compute_*                            plonk/src/proof_system/prover.rs:72-509, 902-1122
@@ -305,6 +306,51 @@ struct StandardTranscript {
         const Fr c = lo_m + hi_m * two256;
         append_fr(label, c);
         return c;
+    }
+};
+
+// plonk/src/transcript/solidity.rs:31-78: labels dropped, messages concatenated, a challenge = the first 48 bytes (little-endian, mod r) of
+// state = keccak256(state || transcript || 0) || keccak256(state || transcript || 1); nothing is cleared or re-absorbed (mzk_solidity_challenge)
+template <class C>
+struct SolidityTranscript {
+    using E = Encoding<C>;
+    using Fr = typename E::Fr;
+    std::vector<uint8_t> transcript;
+    uint8_t state[64] = {0};
+    explicit SolidityTranscript(const char* = "PlonkProof") {}
+    void append_message(const std::string&, const uint8_t* m, size_t n) { transcript.insert(transcript.end(), m, m + n); }
+    Fr get_and_append_challenge(const std::string&) {
+        Fr c;
+        check(mzk_solidity_challenge(C::ID, state, transcript.data(), transcript.size(), c.l), "mzk_solidity_challenge");
+        return c;
+    }
+};
+
+// the transcript of one proof, of the kind the caller names: the PlonkTranscript appends over either
+enum class TranscriptKind { Merlin, Solidity };
+inline TranscriptKind transcript_kind(const std::string& name) {
+    if (name == "merlin") return TranscriptKind::Merlin;
+    if (name == "solidity") return TranscriptKind::Solidity;
+    throw std::runtime_error("transcript: merlin or solidity, not " + name);
+}
+template <class C>
+struct PlonkTranscript {
+    using E = Encoding<C>;
+    using Fr = typename E::Fr;
+    TranscriptKind kind;
+    StandardTranscript<C> merlin;
+    SolidityTranscript<C> solidity;
+    explicit PlonkTranscript(TranscriptKind k, const char* label = "PlonkProof") : kind(k), merlin(label), solidity(label) {}
+    void append_message(const std::string& label, const uint8_t* m, size_t n) {
+        if (kind == TranscriptKind::Merlin) merlin.append_message(label, m, n);
+        else solidity.append_message(label, m, n);
+    }
+    void append_u64(const std::string& label, uint64_t v) { uint8_t b[8]; std::memcpy(b, &v, 8); append_message(label, b, 8); }
+    void append_u32(const std::string& label, uint32_t v) { uint8_t b[4]; std::memcpy(b, &v, 4); append_message(label, b, 4); }
+    void append_fr(const std::string& label, const Fr& v) { uint8_t b[32]; E::fr_bytes(v, b); append_message(label, b, 32); }
+    void append_commitment(const std::string& label, const typename E::Affine& p) { uint8_t b[48]; E::g1_bytes(p, b); append_message(label, b, C::G1_BYTES); }
+    Fr get_and_append_challenge(const std::string& label) {
+        return kind == TranscriptKind::Merlin ? merlin.get_and_append_challenge(label) : solidity.get_and_append_challenge(label);
     }
 };
 

@@ -1,6 +1,6 @@
 // mzk_prove -- PlonkKzgSnark::prove on the reference's bench circuit from a compiled host: C++ above the C ABI of
 // include/mzk.h, no Python, no HIP in this translation unit (g++ builds it).
-//   mzk_prove <curve: 0 BLS12-381 | 1 BN254> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree]
+//   mzk_prove <curve: 0 BLS12-381 | 1 BN254> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--transcript merlin|solidity] [--host-witness | --host-witness-vars] [--check-agree]
 //   mzk_prove <curve> file <circuit file> [reps] [--gpus G] [--host-witness] ...
 // --check-witness (turbo, ultra, file): mzk_prover_check_witness before proving; prints one line -- `witness: satisfied`, or
 // `witness: gate row R residual 0x..`, `witness: lookup row R`, `witness: copy cell (wire,row) != (wire,row)` -- followed by the numbers of
@@ -47,6 +47,8 @@ struct Options {
     int host_witness = 0;         // --host-witness: every proof uploads its W x n wire values from page-locked host memory;
                                   // --host-witness-vars: only the witness vector, gathered per wire on the device
     bool check_agree = false;     // --check-agree: every rank's proof bytes are compared (tests)
+    TranscriptKind transcript = TranscriptKind::Merlin;  // --transcript merlin|solidity: the Fiat-Shamir transcript of every route (solidity: Keccak-256,
+                                  // plonk/src/transcript/solidity.rs, for proofs a keccak256 verifier checks)
     int slots = 0;                // --slots K: K threads on one key through K slots (run_slots)
     const char* srs_path = nullptr;  // --srs FILE: the commit key from a serialized setup
     bool slice_srs = true;        // --no-slice: with --gpus G every rank keeps the whole commit key (and its table) instead of its point range
@@ -82,6 +84,7 @@ int run(bool ultra, uint64_t num_gates, int reps, int range_bits, const Options&
     const auto beta_c = canonical(beta);                                // (drawn with --srs too, then unused: the same blinders follow)
     const SrsFile srs_file = opt.srs_path ? SrsFile::read(opt.srs_path, C::ID) : SrsFile();
     ShardedProver<C> sp(opt.gpus);
+    sp.transcript = opt.transcript;
     double circuit_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     t0 = std::chrono::steady_clock::now();
     const bool lagrange = opt.lagrange < 0 ? (host.log_n >= 18 && host.witness_is_small()) : opt.lagrange != 0;
@@ -188,14 +191,14 @@ int run_slots(bool ultra, uint64_t num_gates, int reps, int range_bits, const Op
     auto pass = [&](P& p, std::vector<std::vector<uint8_t>>& out) {
         ChaChaRng rng = test_rng();
         (void)fr_rand<typename C::Fr>(rng);                                 // the trapdoor's draw (bench.rs:50-54): the blinders follow it
-        for (int i = 0; i < count; i++) out.push_back(p.prove(rng, cs).serialize_compressed());
+        for (int i = 0; i < count; i++) out.push_back(p.prove(rng, cs, false, opt.transcript).serialize_compressed());
     };
     std::vector<std::vector<uint8_t>> alone, warm;
     pass(*slots[0], warm);
     auto t0 = std::chrono::steady_clock::now();
     pass(*slots[0], alone);
     const double alone_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    for (int i = 1; i < K; i++) { ChaChaRng rng = test_rng(); (void)slots[i]->prove(rng, cs); }                          // warm-up of the other slots
+    for (int i = 1; i < K; i++) { ChaChaRng rng = test_rng(); (void)slots[i]->prove(rng, cs, false, opt.transcript); }                          // warm-up of the other slots
     std::vector<std::vector<std::vector<uint8_t>>> got(K);
     std::vector<std::exception_ptr> errors(K);
     std::vector<std::thread> threads;
@@ -234,7 +237,7 @@ static std::string to_hex(const std::vector<uint8_t>& bytes) {
 }
 
 template <class C>
-int run_link(uint64_t gates1, uint64_t gates2, const GroupLayout& layout, int reps) {
+int run_link(uint64_t gates1, uint64_t gates2, const GroupLayout& layout, int reps, TranscriptKind transcript) {
     using Fr = Fp64<typename C::Fr>;
     check(mzk_init(-1), "mzk_init");
     BenchCircuit<C> cs1 = BenchCircuit<C>::generate(gates1, false, 8), cs2 = BenchCircuit<C>::generate(gates2, false, 8);
@@ -245,16 +248,16 @@ int run_link(uint64_t gates1, uint64_t gates2, const GroupLayout& layout, int re
     uint64_t srs = 0;
     check(mzk_srs_generate_for_testing(C::ID, beta_c.data(), cs1.n + 3, &srs), "mzk_srs_generate_for_testing");
     Prover<C> p1(srs, cs1), p2(srs, cs2);
-    Proof<C> proof1 = p1.prove(rng, cs1);
+    Proof<C> proof1 = p1.prove(rng, cs1, false, transcript);
     LinkingHint<C> h1 = link_hint(p1, proof1);
-    Proof<C> proof2 = p2.prove(rng, cs2);
+    Proof<C> proof2 = p2.prove(rng, cs2, false, transcript);
     LinkingHint<C> h2 = link_hint(p2, proof2);
-    LinkingProof<C> link = link_proofs<C>(srs, h1, h2, layout);
+    LinkingProof<C> link = link_proofs<C>(srs, h1, h2, layout, transcript);
     double ms = 0;
     if (reps > 0) {
         check(mzk_dev_sync(), "sync");
         auto t0 = std::chrono::steady_clock::now();
-        for (int i = 0; i < reps; i++) link_proofs<C>(srs, h1, h2, layout);
+        for (int i = 0; i < reps; i++) link_proofs<C>(srs, h1, h2, layout, transcript);
         check(mzk_dev_sync(), "sync");
         ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() / reps;
     }
@@ -265,7 +268,7 @@ int run_link(uint64_t gates1, uint64_t gates2, const GroupLayout& layout, int re
 }
 
 template <class C>
-int run_batch(bool ultra, int range_bits, const std::vector<uint64_t>& gates) {
+int run_batch(bool ultra, int range_bits, const std::vector<uint64_t>& gates, TranscriptKind transcript) {
     using Fr = Fp64<typename C::Fr>;
     check(mzk_init(-1), "mzk_init");
     std::vector<BenchCircuit<C>> circuits;
@@ -284,7 +287,7 @@ int run_batch(bool ultra, int range_bits, const std::vector<uint64_t>& gates) {
         provers.push_back(owned.back().get());
         cs.push_back(&c);
     }
-    const BatchProof<C> proof = batch_prove<C>(rng, provers, cs);
+    const BatchProof<C> proof = batch_prove<C>(rng, provers, cs, transcript);
     std::printf("{\"curve\": %d, \"log_n\": %d, \"instances\": %zu, \"batch_proof_hex\": \"%s\"}\n", C::ID, circuits[0].log_n, gates.size(),
                 to_hex(proof.serialize_compressed()).c_str());
     owned.clear();
@@ -303,6 +306,9 @@ int main(int argc_in, char** argv_in) {
         else if (a == "--host-witness-vars") opt.host_witness = 2;
         else if (a == "--check-agree") opt.check_agree = true;
         else if (a == "--slots" && i + 1 < argc_in) opt.slots = std::atoi(argv_in[++i]);
+        else if (a == "--transcript" && i + 1 < argc_in) {
+            try { opt.transcript = transcript_kind(argv_in[++i]); } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
+        }
         else if (a == "--check-witness") opt.check_witness = true;
         else if (a == "--derive-variables") opt.derive_variables = true;
         else if (a == "--device-preprocess") opt.device_preprocess = true;
@@ -319,7 +325,7 @@ int main(int argc_in, char** argv_in) {
     const int argc = (int)args.size();
     char** argv = args.data();
     if (opt.gpus < 1 || opt.gpus > 16) { std::fprintf(stderr, "mzk_prove: --gpus 1..16\n"); return 2; }
-    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--derive-variables] [--device-preprocess] [--no-lagrange] [--srs FILE] [--save-pk FILE] [--pk FILE (file)] [--pk-uncompressed] [--pk-check]\n", argv[0]); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: %s <curve 0|1> <turbo|ultra> <num_gates> [reps] [range_bit_len] [--gpus G] [--transcript merlin|solidity] [--host-witness | --host-witness-vars] [--check-agree] [--check-witness] [--derive-variables] [--device-preprocess] [--no-lagrange] [--srs FILE] [--save-pk FILE] [--pk FILE (file)] [--pk-uncompressed] [--pk-check]\n", argv[0]); return 2; }
     const int curve = std::atoi(argv[1]);
     if (opt.device_preprocess && (std::string(argv[2]) == "file" || std::string(argv[2]) == "link" || std::string(argv[2]) == "batch")) {
         std::fprintf(stderr, "mzk_prove: --device-preprocess needs the circuit's variable table: a circuit file holds sigma values, not variables "
@@ -345,7 +351,7 @@ int main(int argc_in, char** argv_in) {
         const uint64_t g1 = std::strtoull(argv[3], nullptr, 10), g2 = std::strtoull(argv[4], nullptr, 10);
         const int reps = argc > 8 ? std::atoi(argv[8]) : 0;
         try {
-            return curve == 0 ? run_link<Bls12_381>(g1, g2, layout, reps) : run_link<Bn254>(g1, g2, layout, reps);
+            return curve == 0 ? run_link<Bls12_381>(g1, g2, layout, reps, opt.transcript) : run_link<Bn254>(g1, g2, layout, reps, opt.transcript);
         } catch (const std::exception& e) {
             std::fprintf(stderr, "mzk_prove: %s\n", e.what());
             return 1;
@@ -357,7 +363,7 @@ int main(int argc_in, char** argv_in) {
         for (int i = 5; i < argc; i++) gates.push_back(std::strtoull(argv[i], nullptr, 10));
         try {
             const bool u = std::string(argv[3]) == "ultra";
-            return curve == 0 ? run_batch<Bls12_381>(u, std::atoi(argv[4]), gates) : run_batch<Bn254>(u, std::atoi(argv[4]), gates);
+            return curve == 0 ? run_batch<Bls12_381>(u, std::atoi(argv[4]), gates, opt.transcript) : run_batch<Bn254>(u, std::atoi(argv[4]), gates, opt.transcript);
         } catch (const std::exception& e) {
             std::fprintf(stderr, "mzk_prove: %s\n", e.what());
             return 1;

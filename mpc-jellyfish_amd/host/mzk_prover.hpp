@@ -472,7 +472,7 @@ struct Prover {
         for (auto& row : v) { auto f = flat(row); out.insert(out.end(), f.begin(), f.end()); }
         return out;
     }
-    void append_vk_and_pub_input(StandardTranscript<C>& tr, const BenchCircuit<C>& cs) const {       // transcript/mod.rs:45-104
+    void append_vk_and_pub_input(PlonkTranscript<C>& tr, const BenchCircuit<C>& cs) const {       // transcript/mod.rs:45-104
         tr.append_u32("field size in bits", (uint32_t)FrP::BITS);
         tr.append_u64("domain size", n);
         tr.append_u64("input size", cs.pub_input.size());
@@ -542,12 +542,12 @@ struct Prover {
         check(mzk_prover_round5(hs.data(), (uint32_t)hs.size(), v.l, out.data()), "mzk_prover_round5");
         return points(out);
     }
-    void append_proof_evaluations(StandardTranscript<C>& tr) const {       // transcript/mod.rs:140-163
+    void append_proof_evaluations(PlonkTranscript<C>& tr) const {       // transcript/mod.rs:140-163
         for (auto& v : wires_evals) tr.append_fr("wire_evals", v);
         for (auto& v : wire_sigma_evals) tr.append_fr("wire_sigma_evals", v);
         tr.append_fr("perm_next_eval", perm_next_eval);
     }
-    void append_plookup_evaluations(StandardTranscript<C>& tr) const {     // transcript/mod.rs:165-202
+    void append_plookup_evaluations(PlonkTranscript<C>& tr) const {     // transcript/mod.rs:165-202
         if (!ultra) return;
         const std::vector<Fr>& pe = plookup_evals;
         tr.append_fr("lookup_table_eval", pe[RANGE_TABLE]); tr.append_fr("h_1_eval", pe[H_1]); tr.append_fr("prod_next_eval", pe[PROD_NEXT]);
@@ -576,16 +576,17 @@ struct Prover {
     }
 
     // PlonkKzgSnark::prove (snark.rs:624-651) -> batch_prove_internal (:201-469), one instance
-    Proof<C> prove(ChaChaRng& rng, const BenchCircuit<C>& cs, bool profile = false) {
+    Proof<C> prove(ChaChaRng& rng, const BenchCircuit<C>& cs, bool profile = false, TranscriptKind transcript = TranscriptKind::Merlin) {
         Blinds blinds = draw_blinds(rng, W, ultra);
         std::vector<Fr> b_quot;
         for (int i = 0; i < W - 1; i++) b_quot.push_back(fr_rand<FrP>(rng));                                   // prover.rs:947-955
-        return prove_with(blinds, b_quot, cs, profile);
+        return prove_with(blinds, b_quot, cs, profile, transcript);
     }
     // ... with the masking draws made by the caller: over several devices every rank runs this with the SAME draws (ShardedProver)
-    Proof<C> prove_with(const Blinds& blinds, const std::vector<Fr>& b_quot, const BenchCircuit<C>& cs, bool profile = false) {
+    Proof<C> prove_with(const Blinds& blinds, const std::vector<Fr>& b_quot, const BenchCircuit<C>& cs, bool profile = false,
+                        TranscriptKind transcript = TranscriptKind::Merlin) {
         check(mzk_prover_profile(handle, profile ? 1 : 0), "mzk_prover_profile");
-        StandardTranscript<C> tr;
+        PlonkTranscript<C> tr(transcript);
         append_vk_and_pub_input(tr, cs);
         Proof<C> proof;
         proof.has_plookup = ultra;
@@ -640,6 +641,7 @@ struct ShardedProver {
     std::vector<RankCtx> rank_ctx;
     std::vector<std::unique_ptr<BenchCircuit<C>>> circuit;             // per device
     std::vector<std::unique_ptr<P>> prover;
+    TranscriptKind transcript = TranscriptKind::Merlin;                // the kind every rank's prove_with runs
     std::vector<uint64_t> srs, srs_lagrange;
     double lagrange_key_s = 0;                                         // wall time of mzk_srs_lagrange_from_srs on rank 0 (set-up, once per SRS and domain)
     // worker threads
@@ -788,7 +790,7 @@ struct ShardedProver {
         for (int i = 0; i < prover[0]->W - 1; i++) b_quot.push_back(fr_rand<typename C::Fr>(rng));
         std::vector<Proof<C>> proofs(check_agree ? G : 1);
         each([&](int r) {
-            Proof<C> pr = prover[r]->prove_with(blinds, b_quot, *circuit[r], profile);
+            Proof<C> pr = prover[r]->prove_with(blinds, b_quot, *circuit[r], profile, transcript);
             if (r == 0 || check_agree) proofs[check_agree ? r : 0] = std::move(pr);
         });
         if (check_agree)
@@ -859,7 +861,8 @@ struct BatchProof {
 // commit key), one linearisation polynomial and the two opening proofs over the concatenated lists (prover.rs:362-419): all inside
 // mzk_prover_round3 / mzk_prover_round5.
 template <class C>
-BatchProof<C> batch_prove(ChaChaRng& rng, const std::vector<Prover<C>*>& provers, const std::vector<const BenchCircuit<C>*>& circuits) {
+BatchProof<C> batch_prove(ChaChaRng& rng, const std::vector<Prover<C>*>& provers, const std::vector<const BenchCircuit<C>*>& circuits,
+                          TranscriptKind transcript = TranscriptKind::Merlin) {
     using P = Prover<C>;
     using Fr = typename P::Fr;
     using FrP = typename C::Fr;
@@ -886,7 +889,7 @@ BatchProof<C> batch_prove(ChaChaRng& rng, const std::vector<Prover<C>*>& provers
     for (size_t i = 0; i < K; i++) blinds[i].z = draw(3);
     for (size_t i = 0; i < K; i++) if (provers[i]->ultra) blinds[i].pl = draw(3);
     const std::vector<Fr> b_quot = draw(W - 1);
-    StandardTranscript<C> tr;
+    PlonkTranscript<C> tr(transcript);
     for (size_t i = 0; i < K; i++) provers[i]->append_vk_and_pub_input(tr, *circuits[i]);
     BatchProof<C> proof;
     proof.plookup_proofs_vec.resize(K);
@@ -969,7 +972,8 @@ LinkingHint<C> link_hint(const Prover<C>& prover, const Proof<C>& proof) {
 
 // PlonkKzgSnark::link_proofs (proof_linking.rs:80-111)
 template <class C>
-LinkingProof<C> link_proofs(uint64_t srs, const LinkingHint<C>& lhs, const LinkingHint<C>& rhs, const GroupLayout& layout) {
+LinkingProof<C> link_proofs(uint64_t srs, const LinkingHint<C>& lhs, const LinkingHint<C>& rhs, const GroupLayout& layout,
+                            TranscriptKind transcript = TranscriptKind::Merlin) {
     using E = Encoding<C>;
     using Fr = typename E::Fr;
     using FrP = typename C::Fr;
@@ -1003,7 +1007,7 @@ LinkingProof<C> link_proofs(uint64_t srs, const LinkingHint<C>& lhs, const Linki
     LinkingProof<C> proof;
     proof.quotient_commitment = commit(quotient.p, q_len);
     // eta (proof_linking.rs:185-197)
-    StandardTranscript<C> tr("PlonkLinkingProof");
+    PlonkTranscript<C> tr(transcript, "PlonkLinkingProof");
     tr.append_commitment("linking_wire_comms", lhs.linking_wire_comm);
     tr.append_commitment("linking_wire_comms", rhs.linking_wire_comm);
     tr.append_commitment("quotient_comm", proof.quotient_commitment);

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import kzg
 from . import lib as _lib
+from . import transcript as _transcript
 from .kzg import SerializationError
 from .params import curve as _curve
 
@@ -117,8 +118,8 @@ class OpenKey:
             v = self._verifier = Verifier(self, validate)
         return v
 
-    def begin_links(self, links, eta=None, validate: bool = True) -> "VerifierBatch":
-        return self.verifier().begin_links(links, eta, validate)
+    def begin_links(self, links, eta=None, validate: bool = True, transcript: str = "merlin") -> "VerifierBatch":
+        return self.verifier().begin_links(links, eta, validate, transcript)
 
     def check(self, A_xyz, B_xyz) -> bool:
         return self.verifier().check(A_xyz, B_xyz)
@@ -190,11 +191,13 @@ class Verifier:
         _lib.check(L.mzk_verifier_shape(self.handle, C.byref(np_), C.byref(nkey), C.byref(plen), C.byref(nin)), "mzk_verifier_shape")
         self.n_proof_points, self.n_key_bases, self.proof_len, self.num_inputs = np_.value, nkey.value, plen.value, nin.value
 
-    def begin(self, proofs, public_inputs, extra_msgs=None, challenges=None, validate: bool = True) -> "VerifierBatch":
+    def begin(self, proofs, public_inputs, extra_msgs=None, challenges=None, validate: bool = True, transcript: str = "merlin") -> "VerifierBatch":
         """mzk_verifier_batch_begin.  proofs: K images (bytes); public_inputs: K lists of num_inputs canonical integers; extra_msgs: None or
         K entries, each bytes or None; challenges: None or (K, 7, 4) uint64 Montgomery (tau, beta, gamma, alpha, zeta, v, u) replacing the
-        transcript.  Raises ProofEncodingError naming the lowest bad proof."""
+        transcript; transcript: "merlin" | "solidity", the kind the device's Fiat-Shamir stage runs.  Raises ProofEncodingError naming the
+        lowest bad proof."""
         L = _lib.load()
+        kind = _transcript.flag(transcript)
         if isinstance(self.vk, OpenKey):
             raise ValueError("the verifier holds no verifying key")     # (mzk_verifier_batch_begin: MZK_ERR_INVALID_ARG with this text)
         K = len(proofs)
@@ -210,8 +213,8 @@ class Verifier:
         ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
         batch, bad = C.c_uint64(), C.c_uint64()
         u = np.zeros((K, 4), dtype=np.uint64)
-        rc = L.mzk_verifier_batch_begin(self.handle, ptr(images), self.proof_len, K, ptr(pub), ptr(extra), ptr(ranges), ptr(ch), _SER_VALIDATE if validate else 0,
-                                        C.byref(batch), ptr(u), C.byref(bad))
+        rc = L.mzk_verifier_batch_begin(self.handle, ptr(images), self.proof_len, K, ptr(pub), ptr(extra), ptr(ranges), ptr(ch),
+                                        (_SER_VALIDATE if validate else 0) | kind, C.byref(batch), ptr(u), C.byref(bad))
         if rc == _ERR_ENCODING:
             msg = L.mzk_last_error().decode()
             m = _PROOF_MSG.match(msg)
@@ -219,13 +222,14 @@ class Verifier:
         _lib.check(rc, "mzk_verifier_batch_begin")
         return VerifierBatch(self, batch.value, K, u)
 
-    def begin_links(self, links, eta=None, validate: bool = True) -> "VerifierBatch":
+    def begin_links(self, links, eta=None, validate: bool = True, transcript: str = "merlin") -> "VerifierBatch":
         """mzk_verifier_link_begin.  links: K tuples (lhs_record, rhs_record, link_proof_bytes, layout) -- wires_poly_comms[0] of the two
         Plonk proofs (linking.linking_wire_record), the LinkingProof image (quotient_commitment || opening_proof) and a GroupLayout, records
-        in this verifier's mode; eta: None or (K, 4) uint64 Montgomery replacing the transcript.  Returns a VerifierBatch whose rows are (1, -1,
+        in this verifier's mode; eta: None or (K, 4) uint64 Montgomery replacing the transcript; transcript: "merlin" | "solidity".  Returns a VerifierBatch whose rows are (1, -1,
         -Z_D(eta), eta) over the four records and whose .u holds the K challenges eta.  Raises ProofEncodingError naming the lowest bad link
         (.index) and its field."""
         L = _lib.load()
+        kind = _transcript.flag(transcript)
         K = len(links)
         if K == 0:
             raise ValueError("no link to verify")
@@ -240,7 +244,7 @@ class Verifier:
         batch, bad = C.c_uint64(), C.c_uint64()
         out = np.zeros((K, 4), dtype=np.uint64)
         rc = L.mzk_verifier_link_begin(self.handle, C.c_void_p(records.ctypes.data), K, C.c_void_p(layouts.ctypes.data), None if e is None else C.c_void_p(e.ctypes.data),
-                                       _SER_VALIDATE if validate else 0, C.byref(batch), C.c_void_p(out.ctypes.data), C.byref(bad))
+                                       (_SER_VALIDATE if validate else 0) | kind, C.byref(batch), C.c_void_p(out.ctypes.data), C.byref(bad))
         if rc == _ERR_ENCODING:
             msg = L.mzk_last_error().decode()
             m = _LINK_MSG.match(msg)
@@ -357,11 +361,12 @@ class AggregateVerifier:
         """(points per BatchProof, key bases of the tuple, image length, public inputs per proof)"""
         return self.n_proof_points, self.n_key_bases, self.proof_len, self.num_inputs
 
-    def begin(self, batch_proofs, public_inputs, extra_msgs=None, challenges=None, validate: bool = True) -> "VerifierBatch":
+    def begin(self, batch_proofs, public_inputs, extra_msgs=None, challenges=None, validate: bool = True, transcript: str = "merlin") -> "VerifierBatch":
         """mzk_verifier_aggregate_begin.  batch_proofs: K images; public_inputs: per proof a list of m lists of canonical integers, in tuple
-        order; extra_msgs / challenges as for Verifier.begin.  Raises ProofEncodingError naming the lowest bad proof, its lowest instance
+        order; extra_msgs / challenges / transcript as for Verifier.begin.  Raises ProofEncodingError naming the lowest bad proof, its lowest instance
         (.instance; m: the whole proof's) and the field."""
         L = _lib.load()
+        kind = _transcript.flag(transcript)
         K = len(batch_proofs)
         if K == 0 or len(public_inputs) != K or (extra_msgs is not None and len(extra_msgs) != K):
             raise ValueError("the number of proofs / public inputs / extra messages differ, or no proof")
@@ -379,7 +384,7 @@ class AggregateVerifier:
         batch, bad = C.c_uint64(), C.c_uint64()
         u = np.zeros((K, 4), dtype=np.uint64)
         rc = L.mzk_verifier_aggregate_begin(self.handles, self.m, ptr(images), self.proof_len, K, ptr(pub), ptr(extra), ptr(ranges), ptr(ch),
-                                            _SER_VALIDATE if validate else 0, C.byref(batch), ptr(u), C.byref(bad))
+                                            (_SER_VALIDATE if validate else 0) | kind, C.byref(batch), ptr(u), C.byref(bad))
         if rc == _ERR_ENCODING:
             msg = L.mzk_last_error().decode()
             mt = _BATCH_PROOF_MSG.match(msg)

@@ -74,6 +74,9 @@ _SIGS = {
     "mzk_pairing_product_is_one": [C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int32)],
     "mzk_pairing_gt": [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_batch_verify_challenge": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p],
+    "mzk_batch_verify_challenge_t": [C.c_int32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p],
+    "mzk_keccak256": [C.c_void_p, C.c_uint64, C.c_void_p],
+    "mzk_solidity_challenge": [C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p],
     "mzk_verifier_create": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)],
     "mzk_verifier_destroy": [C.c_uint64],
     "mzk_verifier_shape": [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],

@@ -96,10 +96,10 @@ def compute_vanishing_poly_eval(curve, challenge: int, layout: GroupLayout) -> i
     return out
 
 
-def compute_quotient_challenge(curve, a1_comm: kzg.Commitment, a2_comm: kzg.Commitment, quotient_comm: kzg.Commitment) -> int:
+def compute_quotient_challenge(curve, a1_comm: kzg.Commitment, a2_comm: kzg.Commitment, quotient_comm: kzg.Commitment, transcript: str = "merlin") -> int:
     """proof_linking.rs:185-197: eta from a transcript of its own that absorbs the two linking-wire commitments."""
     c = _curve(curve)
-    t = _transcript.StandardTranscript(c, b"PlonkLinkingProof")
+    t = _transcript.new(transcript, c, b"PlonkLinkingProof")
     t.append_commitments(b"linking_wire_comms", [_point(c, a1_comm), _point(c, a2_comm)])
     t.append_commitment(b"quotient_comm", _point(c, quotient_comm))
     return t.get_and_append_challenge(b"eta")
@@ -119,15 +119,16 @@ def _commit_dev(ck, t) -> kzg.Commitment:
     return kzg.UnivariateKzgPCS.commit(ck, t)
 
 
-def link_proofs(lhs_link_hint: LinkingHint, rhs_link_hint: LinkingHint, group_layout: GroupLayout, commit_key: kzg.UnivariateProverParam) -> LinkingProof:
-    """PlonkKzgSnark::link_proofs (proof_linking.rs:80-111)."""
+def link_proofs(lhs_link_hint: LinkingHint, rhs_link_hint: LinkingHint, group_layout: GroupLayout, commit_key: kzg.UnivariateProverParam,
+                transcript: str = "merlin") -> LinkingProof:
+    """PlonkKzgSnark::link_proofs (proof_linking.rs:80-111); transcript: "merlin" | "solidity", the kind eta is drawn from."""
     c = commit_key.curve
     a1, a2 = lhs_link_hint.linking_wire_poly, rhs_link_hint.linking_wire_poly
     if not (a1.is_cuda and a2.is_cuda):
         raise ValueError("linking wire polynomials must be device resident")
     diff, quotient = compute_linking_quotient(c, a1.contiguous(), a2.contiguous(), group_layout)
     quotient_commitment = _commit_dev(commit_key, quotient)
-    eta = compute_quotient_challenge(c, lhs_link_hint.linking_wire_comm, rhs_link_hint.linking_wire_comm, quotient_commitment)
+    eta = compute_quotient_challenge(c, lhs_link_hint.linking_wire_comm, rhs_link_hint.linking_wire_comm, quotient_commitment, transcript)
     # identity polynomial a_1 - a_2 - q * Z_D(eta), opened at eta (proof_linking.rs:204-221)
     z_eta = compute_vanishing_poly_eval(c, eta, group_layout)
     terms = [(1, diff)] + ([((-z_eta) % c.r, quotient)] if quotient.shape[0] else [])
@@ -191,13 +192,13 @@ def linking_wire_record(curve, proof_bytes, compress: bool = True, batch_layout=
     return rec
 
 
-def batch_verify_link_proofs(open_key_or_vk, links) -> bool:
+def batch_verify_link_proofs(open_key_or_vk, links, transcript: str = "merlin") -> bool:
     """K proof links under one open key in one pass over the device and ONE pairing check.  open_key_or_vk: a keys.OpenKey or a
     keys.VerifyingKey (its open key, its mode); links: [(lhs_record, rhs_record, link_proof_bytes, GroupLayout)].  One link is weighted by 1
     -- PlonkKzgSnark::verify_link_proof as the reference checks it; several by the powers of a challenge drawn from every eta and every
-    opening proof (mzk_verifier_link_weights).  Raises keys.ProofEncodingError naming the lowest malformed link and its field."""
+    opening proof (mzk_verifier_link_weights).  transcript: "merlin" | "solidity", the kind every eta is drawn from.  Raises keys.ProofEncodingError naming the lowest malformed link and its field."""
     v = open_key_or_vk.verifier()
-    b = v.begin_links(links)
+    b = v.begin_links(links, transcript=transcript)
     try:
         A, B = b.finish(b.link_weights())
     finally:
@@ -205,9 +206,9 @@ def batch_verify_link_proofs(open_key_or_vk, links) -> bool:
     return v.check(A, B)
 
 
-def verify_link_proof(proof1_bytes, proof2_bytes, link_proof_bytes, layout: GroupLayout, open_key_or_vk) -> bool:
+def verify_link_proof(proof1_bytes, proof2_bytes, link_proof_bytes, layout: GroupLayout, open_key_or_vk, transcript: str = "merlin") -> bool:
     """PlonkKzgSnark::verify_link_proof (proof_linking.rs:240-286) on the serialized proofs: the two `Proof` images, the LinkingProof image and
     the layout, under the open key of `open_key_or_vk` (keys.OpenKey or keys.VerifyingKey; images in its mode)."""
     c, compress = open_key_or_vk.curve, open_key_or_vk.compressed
     return batch_verify_link_proofs(open_key_or_vk, [(linking_wire_record(c, proof1_bytes, compress), linking_wire_record(c, proof2_bytes, compress),
-                                                      bytes(link_proof_bytes), layout)])
+                                                      bytes(link_proof_bytes), layout)], transcript)

@@ -81,18 +81,19 @@ class FixedChallenges:
 
 
 class TranscriptChallenges:
-    """Challenge source following batch_prove_internal (snark.rs:263-431) on a StandardTranscript."""
+    """Challenge source following batch_prove_internal (snark.rs:263-431) on a StandardTranscript (transcript="merlin") or a
+    SolidityTranscript ("solidity")."""
 
-    def __init__(self, prover: "TurboPlonkProver", pub_input, extra_msg: bytes | None = None):
+    def __init__(self, prover: "TurboPlonkProver", pub_input, extra_msg: bytes | None = None, transcript: str = "merlin"):
         import copy
         c = prover.curve
         self.c = c
         # the transcript after the label, the verifying key and the public input is the same for every proof of one instance:
-        # absorbed once per (extra message, public input), its 200-byte STROBE state copied afterwards (0.25 ms of Python per proof)
+        # absorbed once per (kind, extra message, public input), its state copied afterwards (0.25 ms of Python per proof)
         cache = prover.__dict__.setdefault("_transcript_heads", {})
-        key = (extra_msg, tuple(int(x) for x in pub_input))
+        key = (transcript, extra_msg, tuple(int(x) for x in pub_input))
         if key not in cache:
-            t = _transcript.StandardTranscript(c, b"PlonkProof")
+            t = _transcript.new(transcript, c, b"PlonkProof")
             if extra_msg is not None:
                 t.append_message(b"extra info", extra_msg)
             sel, sig = prover.vk_commitments()

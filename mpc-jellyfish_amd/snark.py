@@ -270,24 +270,26 @@ def serialize_proof(curve, proof: _prover.ProofCore) -> bytes:
 
 
 def prove(rng: _rng.ChaChaRng, circuit: BenchCircuit, pk: _prover.TurboPlonkProver, extra_transcript_init_msg: bytes | None = None,
-          profile: bool = False, witness=None):
+          profile: bool = False, witness=None, transcript: str = "merlin"):
     """PlonkKzgSnark::prove (snark.rs:624-651) through the round-level C ABI: returns (ProofCore, compressed proof bytes).
-    witness: what to prove from instead of circuit.wire_values (a HostWitness, a host tensor ..)."""
+    witness: what to prove from instead of circuit.wire_values (a HostWitness, a host tensor ..); transcript: "merlin" (StandardTranscript) |
+    "solidity" (SolidityTranscript, for proofs a keccak256 verifier checks)."""
     if (circuit.plonk_type == ULTRA) != pk.ultra:
         raise ValueError("Mismatched Plonk types between the proving key and the circuit")                       # snark.rs:249-254
     if circuit.n != pk.n:
         raise ValueError("proving key domain size %d != expected domain size %d" % (pk.n, circuit.n))           # snark.rs:233-240
     blind = draw_blinders(circuit.curve, rng, circuit.num_wire_types, pk.ultra)
-    src = _prover.TranscriptChallenges(pk, circuit.public_input, extra_transcript_init_msg)
+    src = _prover.TranscriptChallenges(pk, circuit.public_input, extra_transcript_init_msg, transcript)
     core = pk.prove(circuit.wire_values if witness is None else witness, list(circuit.public_input), src, blind, profile=profile)
     return core, serialize_proof(circuit.curve, core)
 
 
-def prove_with_link_hint(rng: _rng.ChaChaRng, circuit: BenchCircuit, pk: _prover.TurboPlonkProver, extra_transcript_init_msg: bytes | None = None):
+def prove_with_link_hint(rng: _rng.ChaChaRng, circuit: BenchCircuit, pk: _prover.TurboPlonkProver, extra_transcript_init_msg: bytes | None = None,
+                         transcript: str = "merlin"):
     """PlonkKzgSnark::prove_with_link_hint (snark.rs:81-119): the proof plus the LinkingHint -- the masked wire polynomial that
     carries the proof-linking gates (wire PROOF_LINK_WIRE_IDX, device resident: mzk_prover_poly_dev) and its commitment from round 1."""
     from . import linking
-    core, proof_bytes = prove(rng, circuit, pk, extra_transcript_init_msg)
+    core, proof_bytes = prove(rng, circuit, pk, extra_transcript_init_msg, transcript=transcript)
     hint = linking.LinkingHint(pk.poly_dev(linking.PROOF_LINK_WIRE_IDX), core.wires_poly_comms[linking.PROOF_LINK_WIRE_IDX])
     return core, proof_bytes, hint
 
@@ -305,7 +307,7 @@ def draw_batch_blinders(curve, rng: _rng.ChaChaRng, num_wire_types: int, ultras:
     return [_prover.Blinders(wires[i], z[i], quot, h[i], pl[i]) for i in range(len(ultras))], quot
 
 
-def batch_prove(rng: _rng.ChaChaRng, circuits: list, pks: list, extra_transcript_init_msg: bytes | None = None):
+def batch_prove(rng: _rng.ChaChaRng, circuits: list, pks: list, extra_transcript_init_msg: bytes | None = None, transcript: str = "merlin"):
     """PlonkKzgSnark::batch_prove (snark.rs:64-78): one aggregated proof for several instances of one domain size.
     Returns (BatchProofCore, compressed BatchProof bytes).  To put one circuit three times into an aggregate pass
     `[pk, pk.fork(), pk.fork()]`: the forks share pk's key on the device and bring a workspace each (a repeated prover is refused)."""
@@ -325,22 +327,25 @@ def batch_prove(rng: _rng.ChaChaRng, circuits: list, pks: list, extra_transcript
         if cs.num_wire_types != W:
             raise ValueError("inconsistent plonk circuit types")
     blinds, quot = draw_batch_blinders(circuits[0].curve, rng, W, [pk.ultra for pk in pks])
-    core = _batch.batch_prove(pks, [cs.wire_values for cs in circuits], [list(cs.public_input) for cs in circuits], blinds, quot, extra_transcript_init_msg)
+    core = _batch.batch_prove(pks, [cs.wire_values for cs in circuits], [list(cs.public_input) for cs in circuits], blinds, quot, extra_transcript_init_msg,
+                              transcript)
     return core, _batch.serialize_batch_proof(circuits[0].curve, core)
 
 
-def batch_verify(vks, public_inputs, proofs, extra_msgs, links=None) -> bool:
+def batch_verify(vks, public_inputs, proofs, extra_msgs, links=None, transcript: str = "merlin") -> bool:
     """PlonkKzgSnark::batch_verify (snark.rs:141-190) for single-instance proofs: vks are keys.VerifyingKey, proofs their serialized `Proof`s
     (the mode of each key), extra_msgs one Optional[bytes] per proof.  Proofs are grouped by key and each group goes through the device in
     one pass (keys.Verifier.begin); r is drawn from every proof's u in the CALLER's order (verifier.rs:203-215), the groups' (A, B) are
     summed and checked by one product of two pairings.  links: None, or [(i, j, link_proof_bytes, GroupLayout)] -- LinkingProofs
     (PlonkKzgSnark::verify_link_proof, proof_linking.rs:240-286) between proofs i and j of this call: they go through the device as one more
     group (keys.Verifier.begin_links), weighted by mzk_verifier_link_weights with this call's r, and their (A, B) joins the others' before
-    the one check.  Raises ValueError on mismatched lengths, an empty batch or differing open keys, keys.ProofEncodingError on a malformed
+    the one check.  transcript: "merlin" | "solidity" -- one call uses one kind throughout, as batch_verify::<T> does: every proof's
+    challenges, every link's eta and r.  Raises ValueError on mismatched lengths, an empty batch or differing open keys, keys.ProofEncodingError on a malformed
     proof or link (.index: the proof, resp. the link)."""
     from . import lib as _lib
     import ctypes as C
     K = len(proofs)
+    kind = _transcript.flag(transcript)
     if not (len(vks) == len(public_inputs) == K == len(extra_msgs)):
         raise ValueError("the number of verification keys / public inputs / proofs / extra messages differ")       # snark.rs:150-158
     if K == 0:
@@ -359,16 +364,16 @@ def batch_verify(vks, public_inputs, proofs, extra_msgs, links=None) -> bool:
     try:
         for key in order:
             vk, idx = groups[key]
-            b = vk.verifier().begin([proofs[i] for i in idx], [public_inputs[i] for i in idx], [extra_msgs[i] for i in idx])
+            b = vk.verifier().begin([proofs[i] for i in idx], [public_inputs[i] for i in idx], [extra_msgs[i] for i in idx], transcript=transcript)
             batches.append((vk, idx, b))
             u[idx] = b.u
         if links:
             from . import linking
             wire = lambda i: linking.linking_wire_record(c, proofs[i], vks[i].compressed)
-            lb = vks[0].verifier().begin_links([(wire(i), wire(j), bytes(link), layout) for i, j, link, layout in links])
+            lb = vks[0].verifier().begin_links([(wire(i), wire(j), bytes(link), layout) for i, j, link, layout in links], transcript=transcript)
             batches.append((None, None, lb))
         r = np.zeros(4, dtype=np.uint64)
-        _lib.check(_lib.load().mzk_batch_verify_challenge(c.curve_id, C.c_void_p(u.ctypes.data), K, C.c_void_p(r.ctypes.data)), "mzk_batch_verify_challenge")
+        _lib.check(_lib.load().mzk_batch_verify_challenge_t(c.curve_id, kind, C.c_void_p(u.ctypes.data), K, C.c_void_p(r.ctypes.data)), "mzk_batch_verify_challenge_t")
         r_int = fr_from_mont(c, r.reshape(1, 4))[0]
         weights = fr_to_mont(c, [pow(r_int, i, c.r) for i in range(K)])
         results = [b.finish(weights[idx] if idx is not None else b.link_weights(r)) for _, idx, b in batches]
@@ -378,25 +383,27 @@ def batch_verify(vks, public_inputs, proofs, extra_msgs, links=None) -> bool:
     return vks[0].verifier().check(np.stack([a for a, _ in results]), np.stack([b for _, b in results]))
 
 
-def batch_verify_batch_proofs(vks, public_inputs_list, batch_proofs, extra_msgs) -> bool:
+def batch_verify_batch_proofs(vks, public_inputs_list, batch_proofs, extra_msgs, transcript: str = "merlin") -> bool:
     """K aggregated `BatchProof`s under ONE tuple of keys.VerifyingKey in one pass over the device (keys.AggregateVerifier.begin):
     public_inputs_list holds, per proof, the instances' public inputs in tuple order; extra_msgs one Optional[bytes] per proof.  r is drawn
-    from the proofs' u as batch_verify draws it (1 for one proof) and the pairing check is one.  Raises ValueError on mismatched lengths, an
+    from the proofs' u as batch_verify draws it (1 for one proof) and the pairing check is one; transcript as for batch_verify.  Raises ValueError on mismatched lengths, an
     empty tuple, differing open keys or domain sizes and a public-input length that is not the key's num_inputs; keys.ProofEncodingError
     on a malformed image."""
     from . import keys as _keys, lib as _lib
     import ctypes as C
     K = len(batch_proofs)
+    kind = _transcript.flag(transcript)
     if not (len(public_inputs_list) == K == len(extra_msgs)):
         raise ValueError("the number of public inputs / proofs / extra messages differ")
     if K == 0:
         raise ValueError("no proof to verify")
     agg = _keys.AggregateVerifier(vks)
     c = agg.curve
-    b = agg.begin(batch_proofs, public_inputs_list, extra_msgs)
+    b = agg.begin(batch_proofs, public_inputs_list, extra_msgs, transcript=transcript)
     try:
         r = np.zeros(4, dtype=np.uint64)
-        _lib.check(_lib.load().mzk_batch_verify_challenge(c.curve_id, C.c_void_p(b.u.ctypes.data), K, C.c_void_p(r.ctypes.data)), "mzk_batch_verify_challenge")
+        _lib.check(_lib.load().mzk_batch_verify_challenge_t(c.curve_id, kind, C.c_void_p(b.u.ctypes.data), K, C.c_void_p(r.ctypes.data)),
+                   "mzk_batch_verify_challenge_t")
         r_int = fr_from_mont(c, r.reshape(1, 4))[0]
         A, B = b.finish(fr_to_mont(c, [pow(r_int, i, c.r) for i in range(K)]))
     finally:
@@ -404,14 +411,14 @@ def batch_verify_batch_proofs(vks, public_inputs_list, batch_proofs, extra_msgs)
     return agg.check(A, B)
 
 
-def verify_batch_proof(vks, public_inputs, batch_proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None) -> bool:
+def verify_batch_proof(vks, public_inputs, batch_proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None, transcript: str = "merlin") -> bool:
     """PlonkKzgSnark::verify_batch_proof (snark.rs:117-138): one aggregated proof of len(vks) instances, public_inputs one list per instance
     (r = 1).  The reference's own entry point passes no extra message; batch_prove takes one, so it can be stated here."""
     if len(vks) != len(public_inputs):
         raise ValueError("the number of verification keys / instances / public inputs differ")                              # verifier.rs:77-86
-    return batch_verify_batch_proofs(vks, [public_inputs], [batch_proof_bytes], [extra_transcript_init_msg])
+    return batch_verify_batch_proofs(vks, [public_inputs], [batch_proof_bytes], [extra_transcript_init_msg], transcript)
 
 
-def verify(vk, public_input, proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None) -> bool:
+def verify(vk, public_input, proof_bytes: bytes, extra_transcript_init_msg: bytes | None = None, transcript: str = "merlin") -> bool:
     """PlonkKzgSnark::verify (snark.rs:653-671): batch_verify of one proof (r = 1)."""
-    return batch_verify([vk], [public_input], [proof_bytes], [extra_transcript_init_msg])
+    return batch_verify([vk], [public_input], [proof_bytes], [extra_transcript_init_msg], transcript=transcript)

@@ -3,6 +3,8 @@
 plonk/Cargo.toml; not vendored under the reference tree), with the message order of
 `PlonkTranscript` (plonk/src/transcript/mod.rs:40-214) and `batch_prove_internal` (snark.rs:263-431).
 
+`SolidityTranscript` (plonk/src/transcript/solidity.rs:31-78, Keccak-256 through mzk_keccak256) stands beside it; new(kind, ..) makes either.
+
 Pure host code (the transcript hashes ~40 short messages per proof).  Merlin is
 restated from its published construction: STROBE-128 (Strobe128 lite: R = 166, Keccak-f[1600]) under
 the framing  meta-AD(label) || meta-AD(LE32(len)) || AD(message)  /  PRF(len).  Keccak-f[1600] is pinned
@@ -204,3 +206,51 @@ class StandardTranscript:
         ch = int.from_bytes(buf, "little") % self.curve.r
         self.append_field_elem(label, ch)
         return ch
+
+
+def keccak256(msg: bytes) -> bytes:
+    """sha3::Keccak256 (rate 136, pad byte 0x01) through the library's host-only entry point mzk_keccak256 (no GPU involved)."""
+    import ctypes as C
+    from . import lib as _lib
+    msg = bytes(msg)
+    out = (C.c_uint8 * 32)()
+    _lib.check(_lib.load().mzk_keccak256(msg, len(msg), out), "mzk_keccak256")
+    return bytes(out)
+
+
+class SolidityTranscript(StandardTranscript):
+    """plonk/src/transcript/solidity.rs:31-78, the transcript of proofs that an EVM-style keccak256 verifier checks, with the interface of
+    StandardTranscript: labels are dropped, messages are concatenated, and a challenge is the first 48 bytes (little-endian, mod r) of
+    state = keccak256(state || transcript || 0x00) || keccak256(state || transcript || 0x01).  The transcript is not cleared and the
+    challenge is not appended (the code of the reference, not the comment above its struct)."""
+
+    def __init__(self, curve, label: bytes = b"PlonkProof"):
+        self.curve = _curve(curve)
+        self.transcript = bytearray()
+        self.state = bytes(64)
+
+    def append_message(self, label: bytes, msg: bytes):
+        self.transcript += msg
+
+    def get_and_append_challenge(self, label: bytes) -> int:
+        head = self.state + bytes(self.transcript)
+        self.state = keccak256(head + b"\x00") + keccak256(head + b"\x01")
+        return int.from_bytes(self.state[:48], "little") % self.curve.r
+
+
+KINDS = {"merlin": StandardTranscript, "solidity": SolidityTranscript}
+FLAGS = {"merlin": 0, "solidity": 4}                      # MZK_TRANSCRIPT_SOLIDITY
+
+
+def new(kind: str, curve, label: bytes = b"PlonkProof"):
+    """the transcript of one kind: "merlin" (StandardTranscript) | "solidity" (SolidityTranscript)"""
+    if kind not in KINDS:
+        raise ValueError('transcript: "merlin" or "solidity", not %r' % (kind,))
+    return KINDS[kind](curve, label)
+
+
+def flag(kind: str) -> int:
+    """the bit that names the kind in `flags` of the verifier's begin calls and of mzk_batch_verify_challenge_t"""
+    if kind not in FLAGS:
+        raise ValueError('transcript: "merlin" or "solidity", not %r' % (kind,))
+    return FLAGS[kind]
