@@ -962,8 +962,8 @@ MZK_API int32_t mzk_dev_memset2d(void* dptr, uint64_t pitch, int32_t value, uint
 /* ---- measurement hooks (bench.py): HIP-event timing of the library's own kernels ---- */
 /* on != 0: every subsequent call brackets its dominant kernels with hipEvents on the launch stream. */
 MZK_API int32_t mzk_profile_enable(int32_t on);
-/* name: "msm_accumulate", "msm_total", "ntt_pass", "ntt_total", "vfy_transcript" (stage B of mzk_verifier_batch_begin, either
- * transcript kind), "vfy_link_transcript", "vfy_link_vanishing" (the two kernels of mzk_verifier_link_begin); read the
+/* name: "msm_accumulate", "msm_total", "ntt_pass", "ntt_total", "vfy_transcript" (stage B of mzk_verifier_batch_begin and
+ * mzk_verifier_aggregate_begin, either transcript kind), "vfy_link_transcript", "vfy_link_vanishing" (the two kernels of mzk_verifier_link_begin); read the
  * verifier's regions on the device the verifier lives on.  Returns accumulated device
  * milliseconds and launch count since the last reset (synchronises the recorded events). */
 MZK_API int32_t mzk_profile_get(const char* name, double* out_ms, uint64_t* out_count);

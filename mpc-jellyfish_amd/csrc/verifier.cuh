@@ -1,16 +1,22 @@
-// verifier.cuh -- the per-proof work of PlonkKzgSnark::batch_verify on the device: K single-instance proofs under
-// ONE verifying key, staged as K images of proof_len bytes.  Aggregated BatchProofs under a tuple of keys: the second half of this file;
-// proof links (verify_link_proof): its last section.
-//   A  vfy_decode_kernel      one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array
-//   B  vfy_transcript_kernel  one thread per proof: the transcript of compute_challenges (verifier.rs:274-319) -> 7 challenges; T is
-//                             merlin::Transcript (StandardTranscript) or keccak::SolidityTranscript (MZK_TRANSCRIPT_SOLIDITY)
-//   C  vfy_scalars_kernel     one thread per proof: prepare_pcs_info for one instance (verifier.rs:122-184, 340-733) -> one scalar per base
-//   finish                    vfy_weight_kernel / vfy_colsum_kernel: rows weighted by r^i, the key's columns summed by a fixed tree
-// Base array (boundary form, what mzk_srs_register_dev takes): [ key bases | proof 0's points | proof 1's points | .. ]
-//   key bases    selectors (13 | 14), sigmas (W), Ultra: range, key, table_dom_sep, q_dom_sep; open_key.g last        (NKEY = nsel + W + 4 ultra + 1)
-//   proof points wires (W), prod_perm, split_quot (W), opening, shifted_opening, Ultra: h_1, h_2, prod_lookup       (NP = 13 | 18: image order)
-// A base at infinity holds the curve's generator and is FLAGGED; the finish zeroes its scalar.
-// Errors: one 64-bit atomicMin over (proof << 32 | field << 8 | reason): the lowest proof, then its first field, on every run.
+// verifier.cuh -- the per-proof work of PlonkKzgSnark::batch_verify and verify_batch_proof on the device: K images
+// of proof_len bytes, each of m instances under a tuple of m keys of one type, domain and open key.  ONE set of stages serves two image
+// layouts, both described by a VfyAggShape and a column table: a `Proof` (structs.rs:59-84; m = 1, the strides unused) and a `BatchProof`
+// (structs.rs:266-291; instance j's records at base + j * stride).  Proof links (verify_link_proof): the last section.
+//   A  vfy_decode_kernel          one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array;
+//                                 offsets and field names from device memory (a key image and a link's four records go through it too)
+//   B  vfy_agg_transcript_kernel  one thread per proof: compute_challenges over m keys (verifier.rs:256-321) -> 7 challenges; T is
+//                                 merlin::Transcript (StandardTranscript) or keccak::SolidityTranscript (MZK_TRANSCRIPT_SOLIDITY)
+//   C  vfy_agg_scalars_kernel     one thread per (proof, instance): that instance's share of prepare_pcs_info (verifier.rs:68-184, 340-733)
+//   F  vfy_agg_fold_kernel        one thread per proof: the m shares summed in instance order, the scalars that belong to the whole proof
+//   finish                        vfy_weight_kernel / vfy_colsum_kernel: rows weighted by r^i, the key's columns summed by a fixed tree
+// Base array (boundary form, what mzk_srs_register_dev takes): [ key bases | proof 0's points | proof 1's points | .. ], in COLUMN order:
+//   key columns    position 0's block (selectors (13 | 14), sigmas (W), Ultra: range, key, table_dom_sep, q_dom_sep), position 1's, .., then open_key.g
+//   proof columns  j < m: wires_j (W), prod_perm_j | split_quot (W), opening, shifted_opening | Ultra, j < m: h_1, h_2, prod_lookup
+// (m = 1: NKEY = nsel + W + 4 ultra + 1, NP = 13 | 18, the image order of a `Proof`).  A base at infinity holds the curve's generator and
+// is FLAGGED; the finish zeroes its scalar.
+// Errors: one 64-bit atomicMin over (proof << 40 | instance << 33 | field << 4 | reason): the lowest proof, then its lowest instance, then
+// its first field, on every run.  A BatchProof counts what belongs to the whole proof as instance m; a `Proof`, a key and a link name
+// every record by its index in the image under instance 0.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,38 +31,39 @@ namespace mzk {
 
 #define VFY_LBL(s) s, (uint32_t)(sizeof(s) - 1)                  // a transcript label and its length
 constexpr int VFY_THREADS = 64;                                  // one wave; stage B keeps 25 lanes x 64 transcripts = 12.5 KB of LDS
-constexpr int VFY_MAX_POINTS = 25;                               // records of one image that stage A decodes (a key: 25, a proof: 18)
 constexpr uint32_t VFY_REASON_NOT_BELOW_R = 6;                   // after SrsBad's six
 constexpr uint32_t VFY_FIELD_EVAL = 32, VFY_FIELD_PUB_INPUT = 64;  // fields: 0..24 point j, 32 + e evaluation e, 64 + i public input i
-
-struct VfyPoints {                                               // the G1 records of one image
-    uint32_t n, stride;                                          // records per image; bytes from one image to the next
-    uint32_t off[VFY_MAX_POINTS];                                // byte offset in the image
-    int32_t open_idx;                                            // >= 0: records open_idx, open_idx + 1 also go to a_bases (the MSM A)
-};
-struct VfyShape {                                                // one key's proofs
-    uint32_t W, nsel, ultra, np, nkey, log_n, num_inputs, compressed, g1_bytes, proof_len;
-    uint32_t pt_off[18];
-    uint32_t wires_evals_off, sigma_evals_off, perm_next_off, plookup_evals_off;
+constexpr uint32_t VFY_MAX_INSTANCES = 64;                       // MZK_VERIFIER_MAX_INSTANCES
+struct VfyAggShape {                                             // the images of one batch (a `Proof`: m = 1, nkey1 = nkey - 1, no stride read)
+    uint32_t m, W, nsel, ultra, np, nkey, nkey1, log_n, compressed, g1_bytes, proof_len, total_inputs;   // nkey1: one position's block
+    uint32_t wires_off, wires_stride;                            // instance j's first wire commitment
+    uint32_t prod_off;                                           // prod_perm_poly_comms_vec[0]; stride g1_bytes
+    uint32_t evals_off, evals_stride;                            // instance j's ProofEvaluations, at the count of wires_evals
+    uint32_t plk_off, plk_stride;                                // instance j's Option<PlookupProof>, at its tag
+    uint32_t quot_off;                                           // split_quot_poly_comms[0]; opening_proof and shifted_opening_proof follow the W records
     unsigned long long n;
 };
+// pos_tab, 3 (m + 1) words: per position { byte offset of its script, items of its script, first public input }, then the totals
 
-MZK_D void vfy_report(unsigned long long* err, unsigned long long proof, uint32_t field, uint32_t reason) {
-    atomicMin(err, (proof << 32) | ((unsigned long long)field << 8) | reason);
+MZK_D void vfy_agg_report(unsigned long long* err, unsigned long long proof, uint32_t inst, uint32_t field, uint32_t reason) {
+    atomicMin(err, (proof << 40) | ((unsigned long long)inst << 33) | ((unsigned long long)field << 4) | reason);
 }
 
 // ---- A -------------------------------------------------------------------------------------------------------------------------------
+// n_images images `stride` bytes apart, np records each: record j at off[j], reported as fld[j] = instance << 8 | field.  Records open_idx
+// and open_idx + 1 also go to a_bases (the MSM A); np names no record, so it stands for "no opening columns" (a_bases is not touched).
 template <class X, bool COMPRESSED, bool VALIDATE>
-__global__ __launch_bounds__(VFY_THREADS) void vfy_decode_kernel(const uint8_t* __restrict__ images, unsigned long long n_images, VfyPoints pts,
+__global__ __launch_bounds__(VFY_THREADS) void vfy_decode_kernel(const uint8_t* __restrict__ images, unsigned long long n_images, uint32_t np, uint32_t stride,
+                                                                 const uint32_t* __restrict__ off, const uint32_t* __restrict__ fld, uint32_t open_idx,
                                                                  uint32_t* __restrict__ bases, uint32_t* __restrict__ inf_flags, uint32_t* __restrict__ a_bases,
                                                                  uint32_t* __restrict__ a_inf, unsigned long long* __restrict__ err) {
     const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_images * pts.n) return;
-    const unsigned long long i = t / pts.n;
-    const uint32_t j = (uint32_t)(t % pts.n);
+    if (t >= n_images * np) return;
+    const unsigned long long i = t / np;
+    const uint32_t j = (uint32_t)(t % np);
     uint32_t xy[2 * X::N];
-    const int rc = srs_decode_point<X, COMPRESSED, VALIDATE, true>(images + i * pts.stride + pts.off[j], xy);
-    if (rc >= 0) vfy_report(err, i, j, (uint32_t)rc);
+    const int rc = srs_decode_point<X, COMPRESSED, VALIDATE, true>(images + i * stride + off[j], xy);
+    if (rc >= 0) vfy_agg_report(err, i, fld[j] >> 8, fld[j] & 0xFFu, (uint32_t)rc);
     const bool inf = rc != -1;                                    // (a refused record gets the generator too: the batch is refused anyway)
     if (inf) {
 #pragma unroll
@@ -66,8 +73,8 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_decode_kernel(const uint8_t* 
 #pragma unroll
     for (int k = 0; k < 2 * X::N; k++) out[k] = xy[k];
     inf_flags[t] = inf;
-    if (pts.open_idx >= 0 && (j == (uint32_t)pts.open_idx || j == (uint32_t)pts.open_idx + 1)) {
-        const unsigned long long a = 2 * i + (j - (uint32_t)pts.open_idx);
+    if (j == open_idx || j == open_idx + 1) {                     // the two opening columns also go to the MSM A
+        const unsigned long long a = 2 * i + (j - open_idx);
 #pragma unroll
         for (int k = 0; k < 2 * X::N; k++) a_bases[a * 2 * X::N + k] = xy[k];
         a_inf[a] = inf;
@@ -191,304 +198,7 @@ MZK_D void vfy_transcript_init(T& t, uint64_t* lanes, uint64_t* slots, uint32_t 
     if constexpr (VFY_SOLIDITY<T>) t.init(slots + (unsigned long long)blockIdx.x * slot_words * VFY_THREADS + threadIdx.x, VFY_THREADS, slot_words);
     else t.init(lanes + threadIdx.x, VFY_THREADS, label, label_len);
 }
-template <class P, class X, class T = merlin::Transcript>
-__global__ __launch_bounds__(VFY_THREADS) void vfy_transcript_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyShape sh,
-                                                                     const uint8_t* __restrict__ script, uint32_t n_items,
-                                                                     const uint32_t* __restrict__ pub_inputs /* K x num_inputs canonical */,
-                                                                     const uint8_t* __restrict__ extra, const unsigned long long* __restrict__ extra_range,
-                                                                     uint32_t* __restrict__ challenges, unsigned long long* __restrict__ err,
-                                                                     uint64_t* slots, uint32_t slot_words) {
-    __shared__ uint64_t lanes[VFY_LDS_LANES<T>];
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= K) return;
-    const uint8_t* img = images + i * sh.proof_len;
-    const uint32_t G = sh.g1_bytes;
-    const bool cmp = sh.compressed;
-    T t;
-    vfy_transcript_init(t, lanes, slots, slot_words, VFY_LBL("PlonkProof"));
-    if (extra_range && extra_range[2 * i] != ~0ull) {
-        const unsigned long long b = extra_range[2 * i], e = extra_range[2 * i + 1];
-        t.append_begin(VFY_LBL("extra info"), (uint32_t)(e - b));
-        vfy_absorb_global(t, extra + b, (uint32_t)(e - b));
-    }
-    vfy_append_script(t, script, n_items);
-    for (uint32_t k = 0; k < sh.num_inputs; k++) {
-        const uint32_t* w = pub_inputs + (i * sh.num_inputs + k) * 8ull;
-        uint32_t v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = w[j];
-        if (!ser_below_modulus<P>(v)) vfy_report(err, i, VFY_FIELD_PUB_INPUT + k, VFY_REASON_NOT_BELOW_R);
-        t.append_begin(VFY_LBL("public input"), 32);
-        vfy_absorb_words(t, v);
-    }
-    const uint32_t W = sh.W;
-    Fp<P> ch[7];
-    for (uint32_t k = 0; k < W; k++) vfy_append_g1<X>(t, VFY_LBL("witness_poly_comms"), img + sh.pt_off[k], cmp);
-    ch[0] = vfy_challenge<P>(t, VFY_LBL("tau"));
-    if (sh.ultra)
-        for (uint32_t k = 0; k < 2; k++) vfy_append_g1<X>(t, VFY_LBL("h_poly_comms"), img + sh.pt_off[2 * W + 3 + k], cmp);
-    ch[1] = vfy_challenge<P>(t, VFY_LBL("beta"));
-    ch[2] = vfy_challenge<P>(t, VFY_LBL("gamma"));
-    vfy_append_g1<X>(t, VFY_LBL("perm_poly_comms"), img + sh.pt_off[W], cmp);
-    if (sh.ultra) vfy_append_g1<X>(t, VFY_LBL("plookup_poly_comms"), img + sh.pt_off[2 * W + 5], cmp);
-    ch[3] = vfy_challenge<P>(t, VFY_LBL("alpha"));
-    for (uint32_t k = 0; k < W; k++) vfy_append_g1<X>(t, VFY_LBL("quot_poly_comms"), img + sh.pt_off[W + 1 + k], cmp);
-    ch[4] = vfy_challenge<P>(t, VFY_LBL("zeta"));
-    for (uint32_t k = 0; k < W; k++) { t.append_begin(VFY_LBL("wire_evals"), 32); vfy_absorb_global(t, img + sh.wires_evals_off + 32 * k, 32); }
-    for (uint32_t k = 0; k + 1 < W; k++) { t.append_begin(VFY_LBL("wire_sigma_evals"), 32); vfy_absorb_global(t, img + sh.sigma_evals_off + 32 * k, 32); }
-    t.append_begin(VFY_LBL("perm_next_eval"), 32);
-    vfy_absorb_global(t, img + sh.perm_next_off, 32);
-    if (sh.ultra) {                                               // transcript/mod.rs:165-202: six of the fifteen, under these labels
-        const uint8_t* pe = img + sh.plookup_evals_off;
-        t.append_begin(VFY_LBL("lookup_table_eval"), 32);      vfy_absorb_global(t, pe + 32 * 0, 32);
-        t.append_begin(VFY_LBL("h_1_eval"), 32);                vfy_absorb_global(t, pe + 32 * 4, 32);
-        t.append_begin(VFY_LBL("prod_next_eval"), 32);         vfy_absorb_global(t, pe + 32 * 6, 32);
-        t.append_begin(VFY_LBL("lookup_table_next_eval"), 32); vfy_absorb_global(t, pe + 32 * 7, 32);
-        t.append_begin(VFY_LBL("h_1_next_eval"), 32);          vfy_absorb_global(t, pe + 32 * 10, 32);
-        t.append_begin(VFY_LBL("h_2_next_eval"), 32);          vfy_absorb_global(t, pe + 32 * 11, 32);
-    }
-    ch[5] = vfy_challenge<P>(t, VFY_LBL("v"));
-    vfy_append_g1<X>(t, VFY_LBL("open_proof"), img + sh.pt_off[2 * W + 1], cmp);
-    vfy_append_g1<X>(t, VFY_LBL("shifted_open_proof"), img + sh.pt_off[2 * W + 2], cmp);
-    ch[6] = vfy_challenge<P>(t, VFY_LBL("u"));
-    vfy_store_challenges<P>(t, ch, 7, challenges + i * 7 * 8ull);
-}
-
-// ---- C -------------------------------------------------------------------------------------------------------------------------------
-template <class P>
-MZK_D Fp<P> vfy_read_eval(const uint8_t* __restrict__ p, unsigned long long* err, unsigned long long proof, uint32_t index) {
-    Fp<P> a;
-    fr_read_record(p, a.l);
-    if (!ser_below_modulus<P>(a.l)) vfy_report(err, proof, VFY_FIELD_EVAL + index, VFY_REASON_NOT_BELOW_R);
-    return to_mont(a);
-}
-
-// key_rows: K x nkey; proof_rows: K x np (the tail of the MSM's scalar array); evals: K.  k_mont: the key's W separators.
-template <class P>
-__global__ __launch_bounds__(VFY_THREADS) void vfy_scalars_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyShape sh,
-                                                                  const uint32_t* __restrict__ k_mont, const uint32_t* __restrict__ pub_inputs,
-                                                                  const uint32_t* __restrict__ challenges, uint32_t* __restrict__ key_rows,
-                                                                  uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ evals, unsigned long long* __restrict__ err) {
-    using F = Fp<P>;
-    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= K) return;
-    const uint8_t* img = images + i * sh.proof_len;
-    const uint32_t W = sh.W;
-    const bool ultra = sh.ultra;
-    const F tau = load_fp<P>(challenges + (i * 7 + 0) * 8ull), beta = load_fp<P>(challenges + (i * 7 + 1) * 8ull),
-            gamma = load_fp<P>(challenges + (i * 7 + 2) * 8ull), alpha = load_fp<P>(challenges + (i * 7 + 3) * 8ull),
-            zeta = load_fp<P>(challenges + (i * 7 + 4) * 8ull), v = load_fp<P>(challenges + (i * 7 + 5) * 8ull),
-            u = load_fp<P>(challenges + (i * 7 + 6) * 8ull);
-    F we[6], se[5], pe[15];
-    for (uint32_t k = 0; k < W; k++) we[k] = vfy_read_eval<P>(img + sh.wires_evals_off + 32 * k, err, i, k);
-    for (uint32_t k = 0; k + 1 < W; k++) se[k] = vfy_read_eval<P>(img + sh.sigma_evals_off + 32 * k, err, i, W + k);
-    const F zn = vfy_read_eval<P>(img + sh.perm_next_off, err, i, 2 * W - 1);
-    if (ultra)
-        for (uint32_t k = 0; k < 15; k++) pe[k] = vfy_read_eval<P>(img + sh.plookup_evals_off + 32 * k, err, i, 2 * W + k);
-    // structs.rs:496-541
-    const F &rng_e = pe[0], &key_e = pe[1], &dom_e = pe[2], &qdom_e = pe[3], &h1_e = pe[4], &ql_e = pe[5], &prodn_e = pe[6], &rngn_e = pe[7], &keyn_e = pe[8],
-            &domn_e = pe[9], &h1n_e = pe[10], &h2n_e = pe[11], &qln_e = pe[12], &w3n_e = pe[13], &w4n_e = pe[14];
-
-    // the domain: w, 1 / w, zeta^n, the vanishing and the two Lagrange evaluations (verifier.rs:776-788)
-    F w = F::from_const(P::ROOT);
-    for (int k = (int)sh.log_n; k < P::TWO_ADICITY; k++) w = sqr(w);
-    const F w_inv = inv_safegcd<P>(w), one = F::one(), n_f = from_u64<P>(sh.n);
-    F zeta_n = zeta;
-    for (uint32_t k = 0; k < sh.log_n; k++) zeta_n = sqr(zeta_n);
-    const F vanish = zeta_n - one;
-    const F l1 = vanish * inv_safegcd<P>(n_f * (zeta - one));
-    const F ln = vanish * w_inv * inv_safegcd<P>(n_f * (zeta - w_inv));
-    // PI(zeta) over num_inputs (verifier.rs:845-880, unmerged)
-    F pi = F::zero();
-    if (!vanish.is_zero()) {
-        const F vn = vanish * inv_safegcd<P>(n_f);
-        F g = one;
-        for (uint32_t k = 0; k < sh.num_inputs; k++) {
-            F val = load_fp<P>(pub_inputs + (i * sh.num_inputs + k) * 8ull);
-            if (!ser_below_modulus<P>(val.l)) vfy_report(err, i, VFY_FIELD_PUB_INPUT + k, VFY_REASON_NOT_BELOW_R);
-            val = to_mont(val);
-            pi = pi + vn * g * inv_safegcd<P>(zeta - g) * val;
-            g = g * w;
-        }
-    }
-    const F a2 = sqr(alpha), a3 = a2 * alpha, a4 = sqr(a2), a5 = a4 * alpha, a6 = a4 * a2;
-    const F b1 = one + beta, g_b1 = gamma * b1;
-    // the constant term of the linearisation polynomial (:340-414)
-    F lin = pi - a2 * l1;
-    F acc = alpha * zn * (gamma + we[W - 1]);
-    for (uint32_t k = 0; k + 1 < W; k++) acc = acc * (gamma + we[k] + beta * se[k]);
-    lin = lin - acc;
-    if (ultra) {
-        const F pc = ln * (h1_e - h2n_e - a2) - alpha * l1 - a3 * (zeta - w_inv) * prodn_e * (g_b1 + h1_e + beta * h1n_e) * (g_b1 + beta * h2n_e);
-        lin = lin + a3 * pc;
-    }
-    // scalars: one per base
-    F key[VFY_MAX_POINTS], own[18];
-    for (uint32_t k = 0; k < sh.nkey; k++) key[k] = F::zero();
-    for (uint32_t k = 0; k < sh.np; k++) own[k] = F::zero();
-    const uint32_t SIG = sh.nsel, PLK = sh.nsel + W;                                   // key columns
-    const uint32_t PROD = W, QUOT = W + 1, OPEN = 2 * W + 1, SHIFT = 2 * W + 2, H = 2 * W + 3, PLOOK = 2 * W + 5;   // proof columns
-    // [D]_1 (:513-652)
-    F coeff = alpha;
-    for (uint32_t k = 0; k < W; k++) coeff = coeff * (beta * load_fp<P>(k_mont + 8 * k) * zeta + gamma + we[k]);
-    own[PROD] = coeff + a2 * l1;
-    coeff = alpha * beta * zn;
-    for (uint32_t k = 0; k + 1 < W; k++) coeff = coeff * (beta * se[k] + gamma + we[k]);
-    key[SIG + W - 1] = neg(coeff);
-    {
-        const F w01 = we[0] * we[1], w23 = we[2] * we[3];
-        const auto p5 = [](const F& a) { const F s = sqr(a); return sqr(s) * a; };
-        key[0] = we[0]; key[1] = we[1]; key[2] = we[2]; key[3] = we[3]; key[4] = w01; key[5] = w23;
-        key[6] = p5(we[0]); key[7] = p5(we[1]); key[8] = p5(we[2]); key[9] = p5(we[3]);
-        key[10] = neg(we[4]); key[11] = one; key[12] = w01 * w23 * we[4];
-    }
-    if (ultra) {
-        const F merged_lookup_x = we[5] + ql_e * tau * (qdom_e + tau * (we[0] + tau * (we[1] + tau * we[2])));
-        const F table_x = rng_e + ql_e * tau * (dom_e + tau * (key_e + tau * (we[3] + tau * we[4])));
-        const F table_xw = rngn_e + qln_e * tau * (domn_e + tau * (keyn_e + tau * (w3n_e + tau * w4n_e)));
-        own[PLOOK] = a4 * l1 + a5 * ln + a6 * (zeta - w_inv) * b1 * (gamma + merged_lookup_x) * (g_b1 + table_x + beta * table_xw);
-        own[H + 1] = a6 * (w_inv - zeta) * prodn_e * (g_b1 + h1_e + beta * h1n_e);
-    }
-    // the split quotient (:654-665)
-    {
-        const F zeta_n2 = zeta_n * sqr(zeta);
-        F c = neg(vanish);
-        for (uint32_t k = 0; k < W; k++) { own[QUOT + k] = c; c = c * zeta_n2; }
-    }
-    // powers of v at zeta and of u v at zeta w, with the matching evaluations (:453-506, :673-733)
-    F eval = neg(lin), vb = v, uvb = u;
-    const auto at_zeta = [&](F& slot, const F& e) { slot = slot + vb; eval = eval + e * vb; vb = vb * v; };
-    const auto at_zeta_omega = [&](F& slot, const F& e) { slot = slot + uvb; eval = eval + e * uvb; uvb = uvb * v; };
-    for (uint32_t k = 0; k < W; k++) at_zeta(own[k], we[k]);
-    for (uint32_t k = 0; k + 1 < W; k++) at_zeta(key[SIG + k], se[k]);
-    at_zeta_omega(own[PROD], zn);
-    if (ultra) {
-        at_zeta(key[PLK + 0], rng_e); at_zeta(key[PLK + 1], key_e); at_zeta(own[H], h1_e); at_zeta(key[13], ql_e);
-        at_zeta(key[PLK + 2], dom_e); at_zeta(key[PLK + 3], qdom_e);
-        at_zeta_omega(own[PLOOK], prodn_e); at_zeta_omega(key[PLK + 0], rngn_e); at_zeta_omega(key[PLK + 1], keyn_e);
-        at_zeta_omega(own[H], h1n_e); at_zeta_omega(own[H + 1], h2n_e); at_zeta_omega(key[13], qln_e);
-        at_zeta_omega(own[3], w3n_e); at_zeta_omega(own[4], w4n_e); at_zeta_omega(key[PLK + 2], domn_e);
-    }
-    // the opening proofs' scalars in B (verifier.rs:236-240); open_key.g gets -sum r^i eval_i in the finish
-    own[OPEN] = zeta;
-    own[SHIFT] = u * zeta * w;
-    for (uint32_t k = 0; k < sh.nkey; k++) store_fp<P>(key_rows + (i * sh.nkey + k) * 8ull, key[k]);
-    for (uint32_t k = 0; k < sh.np; k++) store_fp<P>(proof_rows + (i * sh.np + k) * 8ull, own[k]);
-    store_fp<P>(evals + i * 8ull, eval);
-}
-
-// ---- finish --------------------------------------------------------------------------------------------------------------------------
-// proof rows *= r_i (0 at a flagged base); A's scalars (r_i, r_i u_i).  NA: A bases per group member -- 2 for a proof (W, W'), 1 for a
-// proof link (its opening proof, scalar r_i alone: `challenges` is not read)
-template <class P, uint32_t NA = 2>
-__global__ __launch_bounds__(256) void vfy_weight_kernel(unsigned long long K, uint32_t np, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ challenges,
-                                                         const uint32_t* __restrict__ inf_flags /* K x np */, const uint32_t* __restrict__ a_inf,
-                                                         uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ a_scalars) {
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= K * (np + NA)) return;
-    const unsigned long long i = t / (np + NA);
-    const uint32_t j = (uint32_t)(t % (np + NA));
-    const Fp<P> r = load_fp<P>(weights + i * 8ull);
-    if (j < np) {
-        const Fp<P> s = inf_flags[i * np + j] ? Fp<P>::zero() : r * load_fp<P>(proof_rows + (i * np + j) * 8ull);
-        store_fp<P>(proof_rows + (i * np + j) * 8ull, s);
-    } else {
-        const unsigned long long a = NA * i + (j - np);
-        Fp<P> s = (NA == 1 || j == np) ? r : r * load_fp<P>(challenges + (i * 7 + 6) * 8ull);
-        if (a_inf[a]) s = Fp<P>::zero();
-        store_fp<P>(a_scalars + a * 8ull, s);
-    }
-}
-// column c < nkey - 1: sum_i r_i key_rows[i][c]; the last column (open_key.g): -sum_i r_i evals[i].  One block per column; thread t adds
-// rows t, t + 256, .. in order and the 256 partial sums meet in a fixed tree: the same sum on every run, no atomics.
-template <class P>
-__global__ __launch_bounds__(256) void vfy_colsum_kernel(unsigned long long K, uint32_t nkey, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ key_rows,
-                                                         const uint32_t* __restrict__ evals, const uint32_t* __restrict__ key_inf, uint32_t* __restrict__ out) {
-    __shared__ uint32_t part[256 * 8];
-    const uint32_t c = blockIdx.x, tid = threadIdx.x;
-    const bool last = c == nkey - 1;
-    Fp<P> acc = Fp<P>::zero();
-    for (unsigned long long i = tid; i < K; i += 256)
-        acc = acc + load_fp<P>(weights + i * 8ull) * (last ? load_fp<P>(evals + i * 8ull) : load_fp<P>(key_rows + (i * nkey + c) * 8ull));
-#pragma unroll
-    for (int k = 0; k < 8; k++) part[tid * 8 + k] = acc.l[k];
-    __syncthreads();
-    for (uint32_t half = 128; half; half >>= 1) {
-        if (tid < half) {
-            Fp<P> a, b;
-#pragma unroll
-            for (int k = 0; k < 8; k++) { a.l[k] = part[tid * 8 + k]; b.l[k] = part[(tid + half) * 8 + k]; }
-            a = a + b;
-#pragma unroll
-            for (int k = 0; k < 8; k++) part[tid * 8 + k] = a.l[k];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        Fp<P> s;
-#pragma unroll
-        for (int k = 0; k < 8; k++) s.l[k] = part[k];
-        if (last) s = neg(s);
-        if (key_inf[c]) s = Fp<P>::zero();
-        store_fp<P>(out + c * 8ull, s);
-    }
-}
-
-// ---- aggregated BatchProofs ----------------------------------------------------------------------------------------------------------
-// K BatchProof images (structs.rs:266-291) of m instances each under a tuple of m keys of one type, domain and open key.  Every instance
-// has the same W and type, so its records sit at base + j * stride; the decoder alone takes a table, in COLUMN order:
-//   key columns    position 0's block (selectors, sigmas, Ultra: range, key, table_dom_sep, q_dom_sep), position 1's, .., then open_key.g
-//   proof columns  j < m: wires_j (W), prod_perm_j | split_quot (W), opening, shifted_opening | Ultra, j < m: h_1, h_2, prod_lookup
-//   Aa vfy_agg_decode_kernel      one thread per G1 record, offsets and field names from device memory
-//   Ba vfy_agg_transcript_kernel  one thread per BatchProof: compute_challenges over m keys (verifier.rs:256-321)
-//   Ca vfy_agg_scalars_kernel     one thread per (proof, instance): that instance's share of prepare_pcs_info (verifier.rs:68-184)
-//   Fa vfy_agg_fold_kernel        one thread per proof: the m shares summed in instance order, the scalars that belong to the whole proof
-// Errors: atomicMin over (proof << 40 | instance << 33 | field << 4 | reason); what belongs to the whole proof counts as instance m.
-constexpr uint32_t VFY_MAX_INSTANCES = 64;                       // MZK_VERIFIER_MAX_INSTANCES
-struct VfyAggShape {
-    uint32_t m, W, nsel, ultra, np, nkey, nkey1, log_n, compressed, g1_bytes, proof_len, total_inputs;   // nkey1: one position's block
-    uint32_t wires_off, wires_stride;                            // instance j's first wire commitment
-    uint32_t prod_off;                                           // prod_perm_poly_comms_vec[0]; stride g1_bytes
-    uint32_t evals_off, evals_stride;                            // instance j's ProofEvaluations, at the count of wires_evals
-    uint32_t plk_off, plk_stride;                                // instance j's Option<PlookupProof>, at its tag
-    uint32_t quot_off;                                           // split_quot_poly_comms[0]; opening_proof and shifted_opening_proof follow the W records
-    unsigned long long n;
-};
-// pos_tab, 3 (m + 1) words: per position { byte offset of its script, items of its script, first public input }, then the totals
-
-MZK_D void vfy_agg_report(unsigned long long* err, unsigned long long proof, uint32_t inst, uint32_t field, uint32_t reason) {
-    atomicMin(err, (proof << 40) | ((unsigned long long)inst << 33) | ((unsigned long long)field << 4) | reason);
-}
-
-template <class X, bool COMPRESSED, bool VALIDATE>
-__global__ __launch_bounds__(VFY_THREADS) void vfy_agg_decode_kernel(const uint8_t* __restrict__ images, unsigned long long n_images, uint32_t np, uint32_t stride,
-                                                                     const uint32_t* __restrict__ off, const uint32_t* __restrict__ fld /* instance << 8 | field */,
-                                                                     uint32_t open_idx, uint32_t* __restrict__ bases, uint32_t* __restrict__ inf_flags,
-                                                                     uint32_t* __restrict__ a_bases, uint32_t* __restrict__ a_inf, unsigned long long* __restrict__ err) {
-    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_images * np) return;
-    const unsigned long long i = t / np;
-    const uint32_t j = (uint32_t)(t % np);
-    uint32_t xy[2 * X::N];
-    const int rc = srs_decode_point<X, COMPRESSED, VALIDATE, true>(images + i * stride + off[j], xy);
-    if (rc >= 0) vfy_agg_report(err, i, fld[j] >> 8, fld[j] & 0xFFu, (uint32_t)rc);
-    const bool inf = rc != -1;
-    if (inf) {
-#pragma unroll
-        for (int k = 0; k < X::N; k++) { xy[k] = X::GEN_X[k]; xy[X::N + k] = X::GEN_Y[k]; }
-    }
-    uint32_t* out = bases + t * 2 * X::N;
-#pragma unroll
-    for (int k = 0; k < 2 * X::N; k++) out[k] = xy[k];
-    inf_flags[t] = inf;
-    if (j == open_idx || j == open_idx + 1) {                     // the two opening columns also go to the MSM A
-        const unsigned long long a = 2 * i + (j - open_idx);
-#pragma unroll
-        for (int k = 0; k < 2 * X::N; k++) a_bases[a * 2 * X::N + k] = xy[k];
-        a_inf[a] = inf;
-    }
-}
-
+// Proof i: label, its extra message, per position the key's script and the instance's public inputs, then the image's own records
 template <class P, class X, class T = merlin::Transcript>
 __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_transcript_kernel(const uint8_t* __restrict__ images, unsigned long long K, VfyAggShape sh,
                                                                          const uint8_t* __restrict__ script, const uint32_t* __restrict__ pos_tab,
@@ -559,6 +269,7 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_transcript_kernel(const u
     vfy_store_challenges<P>(t, ch, 7, challenges + i * 7 * 8ull);
 }
 
+// ---- C -------------------------------------------------------------------------------------------------------------------------------
 // an Fr record of the image: its range check (stage C makes one pass over an instance's records) and its value
 template <class P>
 MZK_D void vfy_agg_check_eval(const uint8_t* __restrict__ p, unsigned long long* err, unsigned long long proof, uint32_t inst, uint32_t index) {
@@ -746,12 +457,69 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_agg_fold_kernel(unsigned long
     store_fp<P>(key_rows + (i * sh.nkey + sh.nkey - 1) * 8ull, F::zero());
 }
 
+// ---- finish --------------------------------------------------------------------------------------------------------------------------
+// proof rows *= r_i (0 at a flagged base); A's scalars (r_i, r_i u_i).  NA: A bases per group member -- 2 for a proof (W, W'), 1 for a
+// proof link (its opening proof, scalar r_i alone: `challenges` is not read)
+template <class P, uint32_t NA = 2>
+__global__ __launch_bounds__(256) void vfy_weight_kernel(unsigned long long K, uint32_t np, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ challenges,
+                                                         const uint32_t* __restrict__ inf_flags /* K x np */, const uint32_t* __restrict__ a_inf,
+                                                         uint32_t* __restrict__ proof_rows, uint32_t* __restrict__ a_scalars) {
+    const unsigned long long t = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= K * (np + NA)) return;
+    const unsigned long long i = t / (np + NA);
+    const uint32_t j = (uint32_t)(t % (np + NA));
+    const Fp<P> r = load_fp<P>(weights + i * 8ull);
+    if (j < np) {
+        const Fp<P> s = inf_flags[i * np + j] ? Fp<P>::zero() : r * load_fp<P>(proof_rows + (i * np + j) * 8ull);
+        store_fp<P>(proof_rows + (i * np + j) * 8ull, s);
+    } else {
+        const unsigned long long a = NA * i + (j - np);
+        Fp<P> s = (NA == 1 || j == np) ? r : r * load_fp<P>(challenges + (i * 7 + 6) * 8ull);
+        if (a_inf[a]) s = Fp<P>::zero();
+        store_fp<P>(a_scalars + a * 8ull, s);
+    }
+}
+// column c < nkey - 1: sum_i r_i key_rows[i][c]; the last column (open_key.g): -sum_i r_i evals[i].  One block per column; thread t adds
+// rows t, t + 256, .. in order and the 256 partial sums meet in a fixed tree: the same sum on every run, no atomics.
+template <class P>
+__global__ __launch_bounds__(256) void vfy_colsum_kernel(unsigned long long K, uint32_t nkey, const uint32_t* __restrict__ weights, const uint32_t* __restrict__ key_rows,
+                                                         const uint32_t* __restrict__ evals, const uint32_t* __restrict__ key_inf, uint32_t* __restrict__ out) {
+    __shared__ uint32_t part[256 * 8];
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    const bool last = c == nkey - 1;
+    Fp<P> acc = Fp<P>::zero();
+    for (unsigned long long i = tid; i < K; i += 256)
+        acc = acc + load_fp<P>(weights + i * 8ull) * (last ? load_fp<P>(evals + i * 8ull) : load_fp<P>(key_rows + (i * nkey + c) * 8ull));
+#pragma unroll
+    for (int k = 0; k < 8; k++) part[tid * 8 + k] = acc.l[k];
+    __syncthreads();
+    for (uint32_t half = 128; half; half >>= 1) {
+        if (tid < half) {
+            Fp<P> a, b;
+#pragma unroll
+            for (int k = 0; k < 8; k++) { a.l[k] = part[tid * 8 + k]; b.l[k] = part[(tid + half) * 8 + k]; }
+            a = a + b;
+#pragma unroll
+            for (int k = 0; k < 8; k++) part[tid * 8 + k] = a.l[k];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        Fp<P> s;
+#pragma unroll
+        for (int k = 0; k < 8; k++) s.l[k] = part[k];
+        if (last) s = neg(s);
+        if (key_inf[c]) s = Fp<P>::zero();
+        store_fp<P>(out + c * 8ull, s);
+    }
+}
+
 // ---- proof links ---------------------------------------------------------------------------------------------------------------------
 // PlonkKzgSnark::verify_link_proof (proof_linking.rs:240-286) for K links, each staged as 4 G1 records back to back: lhs.wires_poly_comms[0],
 // rhs.wires_poly_comms[0], quotient_commitment, opening_proof.  A link is the KZG opening of a_1 - a_2 - Z_D(eta) q at eta with value 0
 // (univariate_kzg/mod.rs:194-216), so it ends in the pair  A = pi,  B = a_1 - a_2 - Z_D(eta) Q + eta pi  and joins the groups above:
 //   key bases    open_key.g alone, scalar zero (NKEY = 1)        proof points  the 4 records, row (1, -1, -Z_D(eta), eta) (NP = 4)
-//   A  vfy_decode_kernel          over a 4-record VfyPoints (infinity flagged: two proofs of one circuit link with Q = pi = O)
+//   A  vfy_decode_kernel          over the 4 records, no opening columns (infinity flagged: two proofs of one circuit link with Q = pi = O)
 //   Bl vfy_link_transcript_kernel one thread per link: eta (proof_linking.rs:185-197)
 //   Cl vfy_link_vanishing_kernel  one wave per link: Z_D(eta) (:162-176) and the link's row
 //   finish                        vfy_weight_kernel<P, 1> (one A base per link), vfy_colsum_kernel over the one key column

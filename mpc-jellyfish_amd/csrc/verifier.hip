@@ -2,7 +2,8 @@
 // verify_batch_proof for aggregated BatchProofs under a tuple of keys (snark.rs:117-138; mzk_verifier_aggregate_*), verify_link_proof for
 // proof links under an open key (proof_linking.rs:240-286; mzk_verifier_create_open_key, mzk_verifier_link_*).  The per-proof
 // work runs on the device (verifier.cuh: decode, Fiat-Shamir, linearisation scalars), the two MSMs through the variable-base path over a base
-// array registered per batch, the two pairings on the host (hostpairing.hpp behind mzk_pairing_product_is_one).
+// array registered per batch, the two pairings on the host (hostpairing.hpp behind mzk_pairing_product_is_one).  A single proof is an
+// aggregate of one instance under a tuple of one key: both containers go through proofs_begin, each with the layout of its image.
 #include "internal.hpp"
 #include "hostfp.hpp"
 #include "verifier.cuh"
@@ -15,13 +16,16 @@ namespace {
 
 struct Verifier {
     int curve = 0, device = -1;                                   // device: the logical device it was created on, where its memory lives
-    VfyShape sh{};                                                // (sh.compressed: the mode of the key image and of every proof under it)
+    VfyAggShape sh{};                                             // a `Proof` image under this key: one instance, total_inputs the key's num_inputs
+                                                                  // (sh.compressed: the mode of the key image and of every proof under it)
     DevOwned key_xy, key_inf, k_mont, script;
+    DevOwned cols, pos_tab, link_cols;                            // the column tables of a `Proof` image and of a link's records, the one-position table (verifier.cuh)
     uint32_t n_items = 0, script_len = 0;
     std::vector<uint64_t> h, beta_h;                              // mzk_g2_decode's output
     std::vector<uint64_t> g;                                      // open_key.g as decoded (host copy: an aggregate's tuple compares open keys)
     bool open_only = false;                                       // mzk_verifier_create_open_key: no verifying key, key_xy holds open_key.g alone
     uint32_t g_index() const { return open_only ? 0 : sh.nkey - 1; }   // open_key.g in key_xy / key_inf
+    uint32_t num_inputs() const { return sh.total_inputs; }       // this key's public inputs: the total of a tuple of one
 };
 enum class BatchKind { Proofs, Links };                           // Proofs: single proofs and aggregates (two A bases each); Links: one A base each
 struct Batch {
@@ -31,7 +35,7 @@ struct Batch {
     uint64_t K = 0;
     uint32_t np = 0, nkey = 0;                                    // columns of one proof's row and of the key row (an aggregate: NP(m), NKEY(m); links: 4, 1)
     DevOwned images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
-    DevOwned col_off, col_fld, script, pos_tab, k_mont, partials;   // an aggregate's tables (verifier.cuh)
+    DevOwned script, pos_tab, k_mont;                             // a tuple's tables, gathered per position (a tuple of one key reads its verifier's)
     DevOwned layouts, vanish;                                     // links: K x (alignment, offset, size); Z_D(eta_i) (eta_i: the first K values of chal)
     std::vector<uint8_t> open_recs;                               // links: the K opening-proof records as staged (mzk_verifier_link_weights)
     bool holds(const std::shared_ptr<Verifier>& x) const { return v == x || std::find(more.begin(), more.end(), x) != more.end(); }
@@ -46,70 +50,78 @@ uint64_t g_next_verifier = 1, g_next_batch = 1;
 
 uint32_t g1_bytes(int curve, bool compressed) { return (uint32_t)srs_record_bytes(curve, compressed); }
 
-// the layout of a `Proof` image (structs.rs:59-84) under this key's type and mode
-void proof_shape(VfyShape& sh) {
+// the layout of a `Proof` image (structs.rs:59-84) under this key's type and mode: the shape of one instance, its records where the
+// stages look for instance 0's (verifier.cuh), the strides unused
+void proof_shape(VfyAggShape& sh) {
     const uint32_t W = sh.W, G = sh.g1_bytes;
-    uint32_t o = 8, p = 0;
-    for (uint32_t k = 0; k < W; k++, o += G) sh.pt_off[p++] = o;                  // wires_poly_comms
-    sh.pt_off[p++] = o; o += G;                                                  // prod_perm_poly_comm
-    o += 8;
-    for (uint32_t k = 0; k < W; k++, o += G) sh.pt_off[p++] = o;                  // split_quot_poly_comms
-    sh.pt_off[p++] = o; o += G;                                                  // opening_proof
-    sh.pt_off[p++] = o; o += G;                                                  // shifted_opening_proof
-    sh.wires_evals_off = o + 8; o += 8 + 32 * W;
-    sh.sigma_evals_off = o + 8; o += 8 + 32 * (W - 1);
-    sh.perm_next_off = o; o += 32;
-    o += 1;                                                                      // Option<PlookupProof> tag
-    if (sh.ultra) {
-        o += 8;
-        sh.pt_off[p++] = o; o += G;                                              // h_poly_comms
-        sh.pt_off[p++] = o; o += G;
-        sh.pt_off[p++] = o; o += G;                                              // prod_lookup_poly_comm
-        sh.plookup_evals_off = o; o += 32 * 15;
-    }
-    sh.np = p;
-    sh.proof_len = o;
+    sh.m = 1, sh.nkey1 = sh.nsel + W + (sh.ultra ? 4 : 0), sh.nkey = sh.nkey1 + 1, sh.np = 2 * W + 3 + (sh.ultra ? 3 : 0);
+    sh.wires_off = 8;                                                            // wires_poly_comms, after its count
+    sh.prod_off = sh.wires_off + W * G;                                          // prod_perm_poly_comm
+    sh.quot_off = sh.prod_off + G + 8;                                           // split_quot_poly_comms, opening_proof, shifted_opening_proof
+    sh.evals_off = sh.quot_off + (W + 2) * G;                                    // wires_evals' count .. perm_next_eval
+    sh.plk_off = sh.evals_off + 16 + 32 * 2 * W;                                 // Option<PlookupProof>: tag, count, h (2), prod_lookup, 15 evaluations
+    sh.proof_len = sh.plk_off + 1 + (sh.ultra ? 8 + 3 * G + 32 * 15 : 0);
 }
-const char* proof_point_name(const VfyShape& sh, uint32_t j, std::string& buf) {
-    const uint32_t W = sh.W;
-    if (j < W) buf = "wires_poly_comms[" + std::to_string(j) + "]";
-    else if (j == W) buf = "prod_perm_poly_comm";
-    else if (j < 2 * W + 1) buf = "split_quot_poly_comms[" + std::to_string(j - W - 1) + "]";
-    else if (j == 2 * W + 1) buf = "opening_proof";
-    else if (j == 2 * W + 2) buf = "shifted_opening_proof";
-    else if (j < 2 * W + 5) buf = "plookup_proof.h_poly_comms[" + std::to_string(j - 2 * W - 3) + "]";
-    else buf = "plookup_proof.prod_lookup_poly_comm";
-    return buf.c_str();
+std::vector<uint32_t> proof_columns(const VfyAggShape& sh) {      // its G1 records in image order, which is the column order
+    const uint32_t W = sh.W, G = sh.g1_bytes;
+    std::vector<uint32_t> off;
+    for (uint32_t k = 0; k < W + 1; k++) off.push_back(sh.wires_off + k * G);
+    for (uint32_t k = 0; k < W + 2; k++) off.push_back(sh.quot_off + k * G);
+    for (uint32_t k = 0; k < (sh.ultra ? 3u : 0u); k++) off.push_back(sh.plk_off + 9 + k * G);
+    return off;
 }
-const char* proof_eval_name(const VfyShape& sh, uint32_t e, std::string& buf) {
+std::string proof_point_name(uint32_t W, uint32_t j) {
+    if (j < W) return "wires_poly_comms[" + std::to_string(j) + "]";
+    if (j == W) return "prod_perm_poly_comm";
+    if (j < 2 * W + 1) return "split_quot_poly_comms[" + std::to_string(j - W - 1) + "]";
+    if (j == 2 * W + 1) return "opening_proof";
+    if (j == 2 * W + 2) return "shifted_opening_proof";
+    if (j < 2 * W + 5) return "plookup_proof.h_poly_comms[" + std::to_string(j - 2 * W - 3) + "]";
+    return "plookup_proof.prod_lookup_poly_comm";
+}
+std::string proof_eval_name(uint32_t W, uint32_t e) {
     static const char* const PLOOKUP[15] = {"range_table_eval", "key_table_eval", "table_dom_sep_eval", "q_dom_sep_eval", "h_1_eval", "q_lookup_eval",
                                             "prod_next_eval", "range_table_next_eval", "key_table_next_eval", "table_dom_sep_next_eval", "h_1_next_eval",
                                             "h_2_next_eval", "q_lookup_next_eval", "w_3_next_eval", "w_4_next_eval"};
-    const uint32_t W = sh.W;
-    if (e < W) buf = "wires_evals[" + std::to_string(e) + "]";
-    else if (e < 2 * W - 1) buf = "wire_sigma_evals[" + std::to_string(e - W) + "]";
-    else if (e == 2 * W - 1) buf = "perm_next_eval";
-    else buf = std::string("plookup_proof.") + PLOOKUP[(e - 2 * W) % 15];
-    return buf.c_str();
+    if (e < W) return "wires_evals[" + std::to_string(e) + "]";
+    if (e < 2 * W - 1) return "wire_sigma_evals[" + std::to_string(e - W) + "]";
+    if (e == 2 * W - 1) return "perm_next_eval";
+    return std::string("plookup_proof.") + PLOOKUP[(e - 2 * W) % 15];
 }
 const char* reason_text(uint32_t reason) { return reason == VFY_REASON_NOT_BELOW_R ? "not below the modulus" : srs_bad_reason((int)reason); }
+struct VfyError { uint64_t index; uint32_t inst, field, reason; };   // the stages' error word (vfy_agg_report), taken apart
+VfyError error_fields(unsigned long long bad) { return {bad >> 40, (uint32_t)(bad >> 33) & 0x7F, (uint32_t)(bad >> 4) & 0x1FFFFFFF, (uint32_t)bad & 0xF}; }
 
+// Stage A over n_images images `stride` bytes apart.  cols: the np records' offsets, then their field codes, on the device (upload_columns);
+// open_idx: the first of the two opening columns, which also go to a_bases -- np where there are none.
 template <class X>
-void launch_decode(bool compressed, bool validate, const uint8_t* images, uint64_t n_images, const VfyPoints& pts, uint32_t* bases, uint32_t* inf, uint32_t* a_bases,
-                   uint32_t* a_inf, unsigned long long* err) {
-    const dim3 grid((unsigned)((n_images * pts.n + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+void launch_decode(bool compressed, bool validate, const uint8_t* images, uint64_t n_images, uint32_t stride, const uint32_t* cols, uint32_t np, uint32_t open_idx,
+                   uint32_t* bases, uint32_t* inf, uint32_t* a_bases, uint32_t* a_inf, unsigned long long* err) {
+    const dim3 grid((unsigned)((n_images * np + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+#define MZK_DECODE(C, V)                                                                                                                                \
+    hipLaunchKernelGGL((vfy_decode_kernel<X, C, V>), grid, block, 0, nullptr, images, (unsigned long long)n_images, np, stride, cols, cols + np, open_idx, bases, inf, \
+                       a_bases, a_inf, err)
     if (compressed) {
-        if (validate) hipLaunchKernelGGL((vfy_decode_kernel<X, true, true>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
-        else hipLaunchKernelGGL((vfy_decode_kernel<X, true, false>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
+        if (validate) MZK_DECODE(true, true);
+        else MZK_DECODE(true, false);
     } else {
-        if (validate) hipLaunchKernelGGL((vfy_decode_kernel<X, false, true>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
-        else hipLaunchKernelGGL((vfy_decode_kernel<X, false, false>), grid, block, 0, nullptr, images, (unsigned long long)n_images, pts, bases, inf, a_bases, a_inf, err);
+        if (validate) MZK_DECODE(false, true);
+        else MZK_DECODE(false, false);
     }
+#undef MZK_DECODE
 }
-void decode_points(int curve, bool compressed, bool validate, const uint8_t* images, uint64_t n_images, const VfyPoints& pts, uint32_t* bases, uint32_t* inf,
-                   uint32_t* a_bases, uint32_t* a_inf, unsigned long long* err) {
-    if (curve == MZK_CURVE_BLS12_381) launch_decode<BlsFqX>(compressed, validate, images, n_images, pts, bases, inf, a_bases, a_inf, err);
-    else launch_decode<BnFqX>(compressed, validate, images, n_images, pts, bases, inf, a_bases, a_inf, err);
+void decode_points(int curve, bool compressed, bool validate, const uint8_t* images, uint64_t n_images, uint32_t stride, const uint32_t* cols, uint32_t np,
+                   uint32_t open_idx, uint32_t* bases, uint32_t* inf, uint32_t* a_bases, uint32_t* a_inf, unsigned long long* err) {
+    if (curve == MZK_CURVE_BLS12_381) launch_decode<BlsFqX>(compressed, validate, images, n_images, stride, cols, np, open_idx, bases, inf, a_bases, a_inf, err);
+    else launch_decode<BnFqX>(compressed, validate, images, n_images, stride, cols, np, open_idx, bases, inf, a_bases, a_inf, err);
+}
+// a column table on the device: the offsets, then the field codes instance << 8 | field (none given: record j is field j of instance 0)
+int32_t upload_columns(DevOwned& cols, std::vector<uint32_t> off, const std::vector<uint32_t>& fld = {}) {
+    const uint32_t n = (uint32_t)off.size();
+    for (uint32_t j = 0; j < n; j++) off.push_back(fld.empty() ? j : fld[j]);
+    MZK_TRY(cols.alloc(off.size() * 4));
+    HIP_TRY(hipMemcpy(cols.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    return MZK_OK;
 }
 
 void script_item(std::vector<uint8_t>& s, uint32_t& n_items, const char* label, const uint8_t* msg, size_t len) {
@@ -164,48 +176,79 @@ int32_t guard_status(const DeviceGuard& g) {
     const auto obj = find(h);            \
     if (!obj) return MZK_ERR_BAD_HANDLE
 
+// One staged image's G1 records (a verifying key's commitments, an open key's g) decoded into the verifier's key_xy / key_inf, no opening
+// columns; bad: the error word, ~0 when every record is sound
+int32_t decode_key_image(Verifier& v, bool validate, const uint8_t* image, uint64_t len, const std::vector<uint32_t>& off, unsigned long long& bad) {
+    const uint32_t n = (uint32_t)off.size();
+    DevOwned staged, cols, err;
+    MZK_TRY(staged.alloc(len));
+    MZK_TRY(err.alloc(8));
+    MZK_TRY(upload_columns(cols, off));
+    MZK_TRY(v.key_xy.alloc((size_t)n * 2 * fq_words(v.curve) * 4));
+    MZK_TRY(v.key_inf.alloc((size_t)n * 4));
+    HIP_TRY(hipMemcpy(staged.p, image, len, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(err.p, 0xFF, 8));
+    decode_points(v.curve, v.sh.compressed, validate, staged.as<uint8_t>(), 1, (uint32_t)len, cols.as<uint32_t>(), n, n, v.key_xy.as<uint32_t>(), v.key_inf.as<uint32_t>(),
+                  nullptr, nullptr, err.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&bad, err.p, 8, hipMemcpyDeviceToHost));
+    return MZK_OK;
+}
+// h, beta_h: decoded on the host, where the pairing runs; a refusal names them under the caller's prefix
+int32_t decode_g2_pair(Verifier& v, uint32_t flags, const uint8_t* h, const uint8_t* beta_h, const char* prefix) {
+    const struct { const char* name; const uint8_t* rec; std::vector<uint64_t>& out; } points[2] = {{"h", h, v.h}, {"beta_h", beta_h, v.beta_h}};
+    for (const auto& pt : points) {
+        pt.out.resize(4 * fq_words(v.curve) / 2);
+        if (mzk_g2_decode(v.curve, pt.rec, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), pt.out.data()) != MZK_OK) {
+            set_error(std::string(prefix) + pt.name + ": " + mzk_last_error());
+            return MZK_ERR_ENCODING;
+        }
+    }
+    return MZK_OK;
+}
+// A link's four records stand back to back: their column table, kept on every verifier (either kind verifies links) so that link_begin
+// uploads nothing
+int32_t upload_link_columns(Verifier& v) {
+    const uint32_t G = v.sh.g1_bytes;
+    return upload_columns(v.link_cols, {0, G, 2 * G, 3 * G});
+}
+int32_t publish_verifier(std::shared_ptr<Verifier> v, uint64_t* out_handle) {
+    std::lock_guard<std::mutex> lk(g_vfy_lock);
+    *out_handle = handle_make(v->device, g_next_verifier++);
+    g_verifiers[*out_handle] = std::move(v);
+    return MZK_OK;
+}
+
 int32_t verifier_create(int32_t curve, int device, const uint8_t* vk, uint64_t len, uint32_t flags, uint64_t* out_handle) {
-    const bool compressed = flags & MZK_SER_COMPRESSED, validate = flags & MZK_SER_VALIDATE;
+    const bool compressed = flags & MZK_SER_COMPRESSED;
     mzk_key_layout_t lay;
     MZK_TRY(mzk_key_layout(curve, vk, len, (flags & MZK_SER_COMPRESSED) | MZK_KEY_VK_ONLY, &lay));
     if (lay.is_merged) { set_error("merged verifying keys are not supported"); return MZK_ERR_UNSUPPORTED; }
     if (len >= (1ull << 31)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     auto v = std::make_shared<Verifier>();
     v->curve = curve, v->device = device;
-    VfyShape& sh = v->sh;
-    sh.W = lay.num_wire_types, sh.nsel = lay.num_selectors, sh.ultra = lay.has_plookup_vk, sh.n = lay.domain_size, sh.num_inputs = (uint32_t)lay.num_inputs;
+    VfyAggShape& sh = v->sh;
+    sh.W = lay.num_wire_types, sh.nsel = lay.num_selectors, sh.ultra = lay.has_plookup_vk, sh.n = lay.domain_size, sh.total_inputs = (uint32_t)lay.num_inputs;
     if (lay.num_inputs > lay.domain_size) { set_error("num_inputs: larger than the domain"); return MZK_ERR_ENCODING; }
     for (sh.log_n = 0; (1ull << sh.log_n) < sh.n; sh.log_n++) {}
     sh.compressed = compressed, sh.g1_bytes = g1_bytes(curve, compressed);
-    sh.nkey = sh.nsel + sh.W + (sh.ultra ? 4 : 0) + 1;
     proof_shape(sh);
     const uint32_t G = sh.g1_bytes, nkey = sh.nkey, fqw = fq_words(curve);
     // the key's commitments, decoded on the device; infinity is a normal value here (an unused selector commits to nothing)
-    VfyPoints pts{};
-    pts.n = nkey, pts.stride = (uint32_t)len, pts.open_idx = -1;
-    uint32_t p = 0;
+    std::vector<uint32_t> off;
     std::vector<std::string> names;
-    for (uint32_t j = 0; j < sh.nsel; j++) { pts.off[p++] = (uint32_t)(lay.selector_comms_off + j * G); names.push_back("selector_comms[" + std::to_string(j) + "]"); }
-    for (uint32_t j = 0; j < sh.W; j++) { pts.off[p++] = (uint32_t)(lay.sigma_comms_off + j * G); names.push_back("sigma_comms[" + std::to_string(j) + "]"); }
+    for (uint32_t j = 0; j < sh.nsel; j++) { off.push_back((uint32_t)(lay.selector_comms_off + j * G)); names.push_back("selector_comms[" + std::to_string(j) + "]"); }
+    for (uint32_t j = 0; j < sh.W; j++) { off.push_back((uint32_t)(lay.sigma_comms_off + j * G)); names.push_back("sigma_comms[" + std::to_string(j) + "]"); }
     static const char* const PLK[4] = {"range_table_comm", "key_table_comm", "table_dom_sep_comm", "q_dom_sep_comm"};
     if (sh.ultra)
-        for (uint32_t j = 0; j < 4; j++) { pts.off[p++] = (uint32_t)(lay.plookup_comms_off + j * G); names.push_back(std::string("plookup_vk.") + PLK[j]); }
-    pts.off[p++] = (uint32_t)lay.g_off;
+        for (uint32_t j = 0; j < 4; j++) { off.push_back((uint32_t)(lay.plookup_comms_off + j * G)); names.push_back(std::string("plookup_vk.") + PLK[j]); }
+    off.push_back((uint32_t)lay.g_off);
     names.push_back("open_key.g");
-    DevOwned image, err;
-    MZK_TRY(image.alloc(len));
-    MZK_TRY(err.alloc(8));
-    MZK_TRY(v->key_xy.alloc((size_t)nkey * 2 * fqw * 4));
-    MZK_TRY(v->key_inf.alloc((size_t)nkey * 4));
-    HIP_TRY(hipMemcpy(image.p, vk, len, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(err.p, 0xFF, 8));
-    decode_points(curve, compressed, validate, image.as<uint8_t>(), 1, pts, v->key_xy.as<uint32_t>(), v->key_inf.as<uint32_t>(), nullptr, nullptr,
-                  err.as<unsigned long long>());
-    HIP_TRY(hipGetLastError());
     unsigned long long bad = 0;
-    HIP_TRY(hipMemcpy(&bad, err.p, 8, hipMemcpyDeviceToHost));
+    MZK_TRY(decode_key_image(*v, flags & MZK_SER_VALIDATE, vk, len, off, bad));
     if (bad != ~0ull) {
-        set_error("vk." + names[(bad >> 8) & 0xFFFFFF] + ": " + reason_text((uint32_t)(bad & 0xFF)));
+        const VfyError e = error_fields(bad);
+        set_error("vk." + names[e.field] + ": " + reason_text(e.reason));
         return MZK_ERR_ENCODING;
     }
     // the byte script of append_vk_and_pub_input (transcript/mod.rs:45-104), commitments in their compressed form
@@ -238,170 +281,99 @@ int32_t verifier_create(int32_t curve, int device, const uint8_t* vk, uint64_t l
     MZK_TRY(v->k_mont.alloc(k_mont.size() * 8));
     HIP_TRY(hipMemcpy(v->script.p, script.data(), script.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(v->k_mont.p, k_mont.data(), k_mont.size() * 8, hipMemcpyHostToDevice));
-    // h, beta_h: decoded on the host, where the pairing runs
-    v->h.resize(4 * fqw / 2);
-    v->beta_h.resize(4 * fqw / 2);
-    if (mzk_g2_decode(curve, vk + lay.h_off, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->h.data()) != MZK_OK) {
-        set_error(std::string("vk.open_key.h: ") + mzk_last_error());
-        return MZK_ERR_ENCODING;
-    }
-    if (mzk_g2_decode(curve, vk + lay.beta_h_off, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->beta_h.data()) != MZK_OK) {
-        set_error(std::string("vk.open_key.beta_h: ") + mzk_last_error());
-        return MZK_ERR_ENCODING;
-    }
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_handle = handle_make(device, g_next_verifier++);
-    g_verifiers[*out_handle] = std::move(v);
-    return MZK_OK;
+    // what stages A to C read of a tuple, for the tuple of this key alone: a `Proof` image's columns, one position's { script, items, inputs }
+    const uint32_t pos_tab[6] = {0, v->n_items, 0, v->script_len, 0, v->num_inputs()};
+    MZK_TRY(upload_columns(v->cols, proof_columns(sh)));
+    MZK_TRY(v->pos_tab.alloc(sizeof pos_tab));
+    HIP_TRY(hipMemcpy(v->pos_tab.p, pos_tab, sizeof pos_tab, hipMemcpyHostToDevice));
+    MZK_TRY(decode_g2_pair(*v, flags, vk + lay.h_off, vk + lay.beta_h_off, "vk.open_key."));
+    MZK_TRY(upload_link_columns(*v));
+    return publish_verifier(std::move(v), out_handle);
 }
 
 // the container of proof i on the host: Vec counts and the Option tag against the key's type
-bool proof_container_ok(const VfyShape& sh, const uint8_t* img, std::string& why) {
+bool proof_container_ok(const VfyAggShape& sh, const uint8_t* img, std::string& why) {
     const auto count = [&](uint32_t off) { uint64_t c; std::memcpy(&c, img + off, 8); return c; };
     const auto expect = [&](const char* field, uint32_t off, uint64_t want) {
         if (count(off) == want) return true;
         why = std::string(field) + ".len: " + std::to_string(count(off)) + ", expected " + std::to_string(want);
         return false;
     };
-    const uint32_t W = sh.W, G = sh.g1_bytes;
-    if (!expect("wires_poly_comms", 0, W) || !expect("split_quot_poly_comms", sh.pt_off[W] + G, W) || !expect("wires_evals", sh.wires_evals_off - 8, W) ||
-        !expect("wire_sigma_evals", sh.sigma_evals_off - 8, W - 1))
+    const uint32_t W = sh.W;
+    if (!expect("wires_poly_comms", 0, W) || !expect("split_quot_poly_comms", sh.quot_off - 8, W) || !expect("wires_evals", sh.evals_off, W) ||
+        !expect("wire_sigma_evals", sh.evals_off + 8 + 32 * W, W - 1))
         return false;
-    const uint8_t tag = img[sh.perm_next_off + 32];
+    const uint8_t tag = img[sh.plk_off];
     if (tag != (sh.ultra ? 1 : 0)) {
         why = tag > 1 ? "plookup_proof: invalid Option tag" : sh.ultra ? "plookup_proof: absent under an UltraPlonk key" : "plookup_proof: present under a TurboPlonk key";
         return false;
     }
-    return !sh.ultra || expect("plookup_proof.h_poly_comms", sh.perm_next_off + 33, 2);
+    return !sh.ultra || expect("plookup_proof.h_poly_comms", sh.plk_off + 1, 2);
 }
 
 // Stage B under MZK_TRANSCRIPT_SOLIDITY keeps each transcript in a slot of device memory (verifier.cuh, vfy_transcript_init): the 64 bytes of
 // the state, at most `transcript_bytes` of transcript and the recorded challenge points, for every thread of the ceil(K / 64) blocks.
-uint64_t longest_extra(const uint64_t* extra_ranges, uint64_t K) {
-    uint64_t longest = 0;
-    if (extra_ranges)
-        for (uint64_t i = 0; i < K; i++)
-            if (extra_ranges[2 * i] != ~0ull) longest = std::max(longest, extra_ranges[2 * i + 1] - extra_ranges[2 * i]);
-    return longest;
-}
 int32_t alloc_slots(DevOwned& slots, uint64_t K, uint64_t transcript_bytes, uint32_t& slot_words) {
     slot_words = keccak::SolidityTranscript::slot_words(transcript_bytes);
     return slots.alloc((K + VFY_THREADS - 1) / VFY_THREADS * VFY_THREADS * slot_words * 8);
 }
-
-int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub, const uint8_t* extra,
-                    const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags, uint64_t* out_batch, uint64_t* out_u, uint64_t* out_bad) {
-    const Verifier& v = *vp;
-    const VfyShape& sh = v.sh;
-    if (out_bad) *out_bad = ~0ull;
-    if (proof_len != sh.proof_len) {
-        if (out_bad) *out_bad = 0;
-        set_error("proof 0: length: " + std::to_string(proof_len) + " bytes, expected " + std::to_string(sh.proof_len) + " under this key");
-        return MZK_ERR_ENCODING;
-    }
-    for (uint64_t i = 0; i < K; i++) {
-        std::string why;
-        if (!proof_container_ok(sh, proofs + i * proof_len, why)) {
-            if (out_bad) *out_bad = i;
-            set_error("proof " + std::to_string(i) + ": " + why);
-            return MZK_ERR_ENCODING;
-        }
-    }
-    uint64_t extra_len = 0;
+// the curve and the transcript kind of a stage B launch: f(StageB<Fr, FqX, T>{})
+template <class A, class B, class C>
+struct StageB { using Fr = A; using FqX = B; using T = C; };
+template <class F>
+void with_transcript(int curve, bool solidity, F&& f) {
+    if (curve == MZK_CURVE_BLS12_381) solidity ? f(StageB<BlsFr, BlsFqX, keccak::SolidityTranscript>{}) : f(StageB<BlsFr, BlsFqX, merlin::Transcript>{});
+    else solidity ? f(StageB<BnFr, BnFqX, keccak::SolidityTranscript>{}) : f(StageB<BnFr, BnFqX, merlin::Transcript>{});
+}
+// the proofs' extra messages: `end` of the blob their ranges need, and the longest message
+int32_t check_extra(const uint8_t* extra, const uint64_t* extra_ranges, uint64_t K, uint64_t& end, uint64_t& longest) {
+    end = longest = 0;
     if (extra_ranges)
         for (uint64_t i = 0; i < K; i++) {
             const uint64_t b = extra_ranges[2 * i], e = extra_ranges[2 * i + 1];
             if (b == ~0ull) continue;
             if (e < b || e - b >= (1ull << 31) || !extra) { set_error("bad extra message range"); return MZK_ERR_INVALID_ARG; }
-            extra_len = std::max(extra_len, e);
+            end = std::max(end, e), longest = std::max(longest, e - b);
         }
-    const int curve = v.curve;
-    const uint32_t np = sh.np, nkey = sh.nkey, fqw = fq_words(curve);
-    const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
-    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
-    b->v = vp, b->K = K, b->np = np, b->nkey = nkey;
-    MZK_TRY(b->images.alloc(K * proof_len));
-    MZK_TRY(b->pub.alloc(K * sh.num_inputs * 32));
-    MZK_TRY(b->extra.alloc(extra_len));
-    MZK_TRY(b->extra_range.alloc(K * 16));
-    MZK_TRY(b->bases.alloc(n_bases * pt_bytes));
-    MZK_TRY(b->inf.alloc(n_bases * 4));
-    MZK_TRY(b->a_bases.alloc(2 * K * pt_bytes));
-    MZK_TRY(b->a_inf.alloc(2 * K * 4));
-    MZK_TRY(b->chal.alloc(K * 7 * 32));
-    MZK_TRY(b->key_rows.alloc(K * nkey * 32));
-    MZK_TRY(b->b_scal.alloc(n_bases * 32));
-    MZK_TRY(b->evals.alloc(K * 32));
-    MZK_TRY(b->a_scal.alloc(2 * K * 32));
-    MZK_TRY(b->weights.alloc(K * 32));
-    MZK_TRY(b->err.alloc(8));
-    HIP_TRY(hipMemcpy(b->images.p, proofs, K * proof_len, hipMemcpyHostToDevice));           // the K images in one copy
-    if (sh.num_inputs) HIP_TRY(hipMemcpy(b->pub.p, pub, K * sh.num_inputs * 32, hipMemcpyHostToDevice));
-    if (extra_len) HIP_TRY(hipMemcpy(b->extra.p, extra, extra_len, hipMemcpyHostToDevice));
-    if (extra_ranges) HIP_TRY(hipMemcpy(b->extra_range.p, extra_ranges, K * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(b->err.p, 0xFF, 8));
-    HIP_TRY(hipMemcpy(b->bases.p, v.key_xy.p, nkey * pt_bytes, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(b->inf.p, v.key_inf.p, nkey * 4, hipMemcpyDeviceToDevice));
-    unsigned long long* err = b->err.as<unsigned long long>();
-    // A
-    VfyPoints pts{};
-    pts.n = np, pts.stride = sh.proof_len, pts.open_idx = (int32_t)(2 * sh.W + 1);
-    for (uint32_t j = 0; j < np; j++) pts.off[j] = sh.pt_off[j];
-    decode_points(curve, sh.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, pts, b->bases.as<uint32_t>() + (size_t)nkey * 2 * fqw,
-                  b->inf.as<uint32_t>() + nkey, b->a_bases.as<uint32_t>(), b->a_inf.as<uint32_t>(), err);
-    HIP_TRY(hipGetLastError());
-    // B, or the caller's challenges
-    const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
-    DevOwned slots;                                                   // Solidity: the transcripts' memory, freed when the stages are through
-    if (challenges) {
-        HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
-    } else {
-        ProfScope ps("vfy_transcript", nullptr, v.device);
-        const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
-        const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
-        uint32_t slot_words = 0;
-        // (the script's length bounds its messages; the proof's own: np commitments in compressed form, 2 W (+ 6) evaluations)
-        if (solidity)
-            MZK_TRY(alloc_slots(slots, K, longest_extra(extra_ranges, K) + v.script_len + 32ull * sh.num_inputs + (uint64_t)np * g1_bytes(curve, true) +
-                                              32ull * (2 * sh.W + 6), slot_words));
-#define MZK_VFY_TRANSCRIPT(Fr, FqX, T)                                                                                                                        \
-    hipLaunchKernelGGL((vfy_transcript_kernel<Fr, FqX, T>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.script.as<uint8_t>(), \
-                       v.n_items, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), err, slots.as<uint64_t>(), slot_words)
-        if (curve == MZK_CURVE_BLS12_381) {
-            if (solidity) MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, keccak::SolidityTranscript);
-            else MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, merlin::Transcript);
-        } else {
-            if (solidity) MZK_VFY_TRANSCRIPT(BnFr, BnFqX, keccak::SolidityTranscript);
-            else MZK_VFY_TRANSCRIPT(BnFr, BnFqX, merlin::Transcript);
-        }
-#undef MZK_VFY_TRANSCRIPT
-        HIP_TRY(hipGetLastError());
-    }
-    // C
-    uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
-    if (curve == MZK_CURVE_BLS12_381)
-        hipLaunchKernelGGL((vfy_scalars_kernel<BlsFr>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.k_mont.as<uint32_t>(),
-                           b->pub.as<uint32_t>(), b->chal.as<uint32_t>(), b->key_rows.as<uint32_t>(), proof_rows, b->evals.as<uint32_t>(), err);
-    else
-        hipLaunchKernelGGL((vfy_scalars_kernel<BnFr>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, sh, v.k_mont.as<uint32_t>(),
-                           b->pub.as<uint32_t>(), b->chal.as<uint32_t>(), b->key_rows.as<uint32_t>(), proof_rows, b->evals.as<uint32_t>(), err);
-    HIP_TRY(hipGetLastError());
+    return MZK_OK;
+}
+// What every batch has: its K images staged in one copy, the base and scalar arrays of its np + nkey columns, n_chal values of 32 bytes
+// in chal and n_a bases of the MSM A per member, the error word set.  (b.v, b.K, b.np and b.nkey are the caller's.)
+int32_t stage_batch(Batch& b, const uint8_t* images, uint64_t image_len, uint32_t n_chal, uint32_t n_a) {
+    const uint64_t K = b.K;
+    const size_t pt_bytes = (size_t)2 * fq_words(b.v->curve) * 4, n_bases = b.nkey + K * b.np;
+    MZK_TRY(b.images.alloc(K * image_len));
+    MZK_TRY(b.bases.alloc(n_bases * pt_bytes));
+    MZK_TRY(b.inf.alloc(n_bases * 4));
+    MZK_TRY(b.a_bases.alloc(n_a * K * pt_bytes));
+    MZK_TRY(b.a_inf.alloc(n_a * K * 4));
+    MZK_TRY(b.chal.alloc(K * n_chal * 32));
+    MZK_TRY(b.key_rows.alloc(K * b.nkey * 32));
+    MZK_TRY(b.b_scal.alloc(n_bases * 32));
+    MZK_TRY(b.evals.alloc(K * 32));
+    MZK_TRY(b.a_scal.alloc(n_a * K * 32));
+    MZK_TRY(b.weights.alloc(K * 32));
+    MZK_TRY(b.err.alloc(8));
+    HIP_TRY(hipMemcpy(b.images.p, images, K * image_len, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b.err.p, 0xFF, 8));
+    return MZK_OK;
+}
+// The end of every begin: the error word, whose copy synchronises the stages -- `<member> <i>: <name(instance, field)>: <reason>` for the
+// lowest bad member -- else the batch hands out one value of chal per member (32 bytes at `first`, every `pitch` bytes) and is
+// published under the lock, last.
+template <class Name>
+int32_t publish_batch(std::shared_ptr<Batch> b, const char* member, Name name, uint64_t* out_values, size_t first, size_t pitch, uint64_t* out_batch, uint64_t* out_bad) {
     unsigned long long bad = 0;
-    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));                             // (synchronises the three stages)
+    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));
     if (bad != ~0ull) {
-        const uint64_t i = bad >> 32;
-        const uint32_t field = (uint32_t)(bad >> 8) & 0xFFFFFF, reason = (uint32_t)bad & 0xFF;
-        std::string buf;
-        const std::string name = field >= VFY_FIELD_PUB_INPUT ? "public_input[" + std::to_string(field - VFY_FIELD_PUB_INPUT) + "]"
-                                 : field >= VFY_FIELD_EVAL    ? proof_eval_name(sh, field - VFY_FIELD_EVAL, buf)
-                                                              : proof_point_name(sh, field, buf);
-        if (out_bad) *out_bad = i;
-        set_error("proof " + std::to_string(i) + ": " + name + ": " + reason_text(reason));
+        const VfyError e = error_fields(bad);
+        if (out_bad) *out_bad = e.index;
+        set_error(std::string(member) + " " + std::to_string(e.index) + ": " + name(e.inst, e.field) + ": " + reason_text(e.reason));
         return MZK_ERR_ENCODING;
     }
-    if (out_u) HIP_TRY(hipMemcpy2D(out_u, 32, b->chal.as<uint8_t>() + 6 * 32, 7 * 32, 32, K, hipMemcpyDeviceToHost));
+    if (out_values) HIP_TRY(hipMemcpy2D(out_values, 32, b->chal.as<uint8_t>() + first, pitch, 32, b->K, hipMemcpyDeviceToHost));
     std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_batch = handle_make(v.device, g_next_batch++);
+    *out_batch = handle_make(b->v->device, g_next_batch++);
     g_batches[*out_batch] = std::move(b);
     return MZK_OK;
 }
@@ -516,14 +488,13 @@ int32_t tuple_shape(const std::vector<std::shared_ptr<Verifier>>& vs, VfyAggShap
         if (v.sh.n != v0.sh.n) { set_error("the domain size of the " + std::to_string(j) + "-th verification key is different"); return MZK_ERR_INVALID_ARG; }
         if (v.g != v0.g || v.h != v0.h || v.beta_h != v0.beta_h) { set_error("the verification keys have different open keys"); return MZK_ERR_INVALID_ARG; }
         if (v.sh.ultra != v0.sh.ultra) { set_error("a tuple of TurboPlonk and UltraPlonk keys is not supported"); return MZK_ERR_UNSUPPORTED; }
-        total_inputs += v.sh.num_inputs;
+        total_inputs += v.num_inputs();
     }
     if (total_inputs >= (1ull << 28)) { set_error("too many public inputs"); return MZK_ERR_UNSUPPORTED; }
-    const VfyShape& s = v0.sh;
+    const VfyAggShape& s = v0.sh;
     batch_proof_layout(s.g1_bytes, s.ultra, m, L);
-    ag = VfyAggShape{};
-    ag.m = m, ag.W = s.W, ag.nsel = s.nsel, ag.ultra = s.ultra, ag.log_n = s.log_n, ag.compressed = s.compressed, ag.g1_bytes = s.g1_bytes, ag.n = s.n;
-    ag.nkey1 = s.nkey - 1, ag.nkey = m * ag.nkey1 + 1;
+    ag = s;                                                                          // the type, the mode and the domain; then what m instances change
+    ag.m = m, ag.nkey = m * s.nkey1 + 1;
     ag.np = m * (s.W + 1) + s.W + 2 + (s.ultra ? 3 * m : 0);
     ag.proof_len = (uint32_t)L.total_len, ag.total_inputs = (uint32_t)total_inputs;
     ag.wires_off = (uint32_t)L.wires_off[0], ag.wires_stride = 8 + s.W * s.g1_bytes;
@@ -549,47 +520,138 @@ int32_t tuple_args(const uint64_t* handles, uint32_t m) {
 }
 std::string agg_field_name(const VfyAggShape& ag, uint32_t inst, uint32_t field) {
     const uint32_t W = ag.W;
-    std::string buf;
     if (field >= VFY_FIELD_PUB_INPUT) return "public_input[" + std::to_string(field - VFY_FIELD_PUB_INPUT) + "]";
-    if (field >= VFY_FIELD_EVAL) {
-        VfyShape one{};
-        one.W = W;
-        return proof_eval_name(one, field - VFY_FIELD_EVAL, buf);
-    }
+    if (field >= VFY_FIELD_EVAL) return proof_eval_name(W, field - VFY_FIELD_EVAL);
     if (inst == ag.m) return field < W ? "split_quot_poly_comms[" + std::to_string(field) + "]" : field == W ? "opening_proof" : "shifted_opening_proof";
     if (field < W) return "wires_poly_comms[" + std::to_string(field) + "]";
     if (field == W) return "prod_perm_poly_comm";
     return field < W + 3 ? "plookup_proof.h_poly_comms[" + std::to_string(field - W - 1) + "]" : "plookup_proof.prod_lookup_poly_comm";
 }
 
-template <class X>
-void launch_agg_decode(bool compressed, bool validate, const uint8_t* images, uint64_t K, const VfyAggShape& ag, const Batch& b, uint32_t* bases, uint32_t* inf,
-                       unsigned long long* err) {
-    const dim3 grid((unsigned)((K * ag.np + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
-    const uint32_t open_idx = ag.m * (ag.W + 1) + ag.W;
-#define MZK_AGG_DECODE(C, V)                                                                                                                             \
-    hipLaunchKernelGGL((vfy_agg_decode_kernel<X, C, V>), grid, block, 0, nullptr, images, (unsigned long long)K, ag.np, ag.proof_len, b.col_off.as<uint32_t>(), \
-                       b.col_fld.as<uint32_t>(), open_idx, bases, inf, b.a_bases.as<uint32_t>(), b.a_inf.as<uint32_t>(), err)
-    if (compressed) {
-        if (validate) MZK_AGG_DECODE(true, true);
-        else MZK_AGG_DECODE(true, false);
-    } else {
-        if (validate) MZK_AGG_DECODE(false, true);
-        else MZK_AGG_DECODE(false, false);
-    }
-#undef MZK_AGG_DECODE
-}
 template <class Fr>
-void launch_agg_scalars(const Batch& b, uint64_t K, const VfyAggShape& ag, uint32_t* proof_rows, unsigned long long* err) {
+void launch_agg_scalars(const Batch& b, uint64_t K, const VfyAggShape& ag, const uint32_t* k_mont, const uint32_t* pos_tab, uint32_t* proof_rows, unsigned long long* err) {
     const dim3 grid((unsigned)((K * ag.m + VFY_THREADS - 1) / VFY_THREADS)), fold((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+    uint32_t* partials = b.chal.as<uint32_t>() + K * 7 * 8;           // K x m, behind the K x 7 challenges (proofs_begin)
     if (ag.ultra)
-        hipLaunchKernelGGL((vfy_agg_scalars_kernel<Fr, true>), grid, block, 0, nullptr, b.images.as<uint8_t>(), (unsigned long long)K, ag, b.k_mont.as<uint32_t>(),
-                           b.pos_tab.as<uint32_t>(), b.pub.as<uint32_t>(), b.chal.as<uint32_t>(), b.key_rows.as<uint32_t>(), proof_rows, b.partials.as<uint32_t>(), err);
+        hipLaunchKernelGGL((vfy_agg_scalars_kernel<Fr, true>), grid, block, 0, nullptr, b.images.as<uint8_t>(), (unsigned long long)K, ag, k_mont, pos_tab,
+                           b.pub.as<uint32_t>(), b.chal.as<uint32_t>(), b.key_rows.as<uint32_t>(), proof_rows, partials, err);
     else
-        hipLaunchKernelGGL((vfy_agg_scalars_kernel<Fr, false>), grid, block, 0, nullptr, b.images.as<uint8_t>(), (unsigned long long)K, ag, b.k_mont.as<uint32_t>(),
-                           b.pos_tab.as<uint32_t>(), b.pub.as<uint32_t>(), b.chal.as<uint32_t>(), b.key_rows.as<uint32_t>(), proof_rows, b.partials.as<uint32_t>(), err);
-    hipLaunchKernelGGL((vfy_agg_fold_kernel<Fr>), fold, block, 0, nullptr, (unsigned long long)K, ag, b.chal.as<uint32_t>(), b.partials.as<uint32_t>(),
+        hipLaunchKernelGGL((vfy_agg_scalars_kernel<Fr, false>), grid, block, 0, nullptr, b.images.as<uint8_t>(), (unsigned long long)K, ag, k_mont, pos_tab,
+                           b.pub.as<uint32_t>(), b.chal.as<uint32_t>(), b.key_rows.as<uint32_t>(), proof_rows, partials, err);
+    hipLaunchKernelGGL((vfy_agg_fold_kernel<Fr>), fold, block, 0, nullptr, (unsigned long long)K, ag, b.chal.as<uint32_t>(), partials,
                        b.key_rows.as<uint32_t>(), proof_rows, b.evals.as<uint32_t>());
+}
+
+// Stages A, B and C over K images under the tuple vs.  ag and cols (on the device) describe the image: a `Proof` under its verifier's own
+// table, whose refusals read `proof i: <field>`, or a BatchProof (batch_proofs), `proof i: instance j: <field>`.  A tuple of one key reads
+// that verifier's script, k and position table where they are -- the batch keeps its verifiers alive -- and its key block is the head of
+// the base array as it stands; a longer tuple gathers them per POSITION: a repeated key repeats its block, its script and its k.
+int32_t proofs_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const VfyAggShape& ag, const uint32_t* cols, bool batch_proofs, const uint8_t* proofs,
+                     uint64_t K, const uint64_t* pub, const uint8_t* extra, const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags,
+                     uint64_t* out_batch, uint64_t* out_u, uint64_t* out_bad) {
+    const Verifier& v0 = *vs[0];
+    const uint32_t m = ag.m, W = ag.W, np = ag.np, nkey = ag.nkey, nkey1 = ag.nkey1;
+    uint64_t extra_len, longest_extra;
+    MZK_TRY(check_extra(extra, extra_ranges, K, extra_len, longest_extra));
+    const int curve = v0.curve;
+    const uint32_t fqw = fq_words(curve);
+    const size_t pt_bytes = (size_t)2 * fqw * 4;
+    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
+    b->v = vs[0], b->more.assign(vs.begin() + 1, vs.end()), b->K = K, b->np = np, b->nkey = nkey;
+    MZK_TRY(stage_batch(*b, proofs, ag.proof_len, 7 + m, 2));        // chal: the K x 7 challenges, then stage C's K x m partial evaluations
+    MZK_TRY(b->pub.alloc(K * ag.total_inputs * 32));
+    MZK_TRY(b->extra.alloc(extra_len));
+    MZK_TRY(b->extra_range.alloc(K * 16));
+    if (ag.total_inputs) HIP_TRY(hipMemcpy(b->pub.p, pub, K * ag.total_inputs * 32, hipMemcpyHostToDevice));
+    if (extra_len) HIP_TRY(hipMemcpy(b->extra.p, extra, extra_len, hipMemcpyHostToDevice));
+    if (extra_ranges) HIP_TRY(hipMemcpy(b->extra_range.p, extra_ranges, K * 16, hipMemcpyHostToDevice));
+    const uint8_t* script = v0.script.as<uint8_t>();
+    const uint32_t *pos_tab = v0.pos_tab.as<uint32_t>(), *k_mont = v0.k_mont.as<uint32_t>();
+    uint32_t script_len = v0.script_len;
+    if (m == 1) {
+        HIP_TRY(hipMemcpyAsync(b->bases.p, v0.key_xy.p, nkey * pt_bytes, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(b->inf.p, v0.key_inf.p, nkey * 4, hipMemcpyDeviceToDevice, nullptr));
+    } else {
+        std::vector<uint32_t> tab;
+        uint32_t inputs = 0;
+        script_len = 0;
+        for (uint32_t j = 0; j < m; j++) {
+            tab.insert(tab.end(), {script_len, vs[j]->n_items, inputs});
+            script_len += vs[j]->script_len, inputs += vs[j]->num_inputs();
+        }
+        tab.insert(tab.end(), {script_len, 0u, inputs});
+        MZK_TRY(b->script.alloc(script_len));
+        MZK_TRY(b->pos_tab.alloc(tab.size() * 4));
+        MZK_TRY(b->k_mont.alloc((size_t)m * W * 32));
+        HIP_TRY(hipMemcpy(b->pos_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        for (uint32_t j = 0; j < m; j++) {
+            const Verifier& v = *vs[j];
+            HIP_TRY(hipMemcpyAsync(b->bases.as<uint8_t>() + (size_t)j * nkey1 * pt_bytes, v.key_xy.p, nkey1 * pt_bytes, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(b->inf.as<uint32_t>() + (size_t)j * nkey1, v.key_inf.p, nkey1 * 4, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(b->script.as<uint8_t>() + tab[3 * j], v.script.p, v.script_len, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(b->k_mont.as<uint8_t>() + (size_t)j * W * 32, v.k_mont.p, (size_t)W * 32, hipMemcpyDeviceToDevice, nullptr));
+        }
+        HIP_TRY(hipMemcpyAsync(b->bases.as<uint8_t>() + (size_t)(nkey - 1) * pt_bytes, v0.key_xy.as<uint8_t>() + (size_t)nkey1 * pt_bytes, pt_bytes, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(b->inf.as<uint32_t>() + (nkey - 1), v0.key_inf.as<uint32_t>() + nkey1, 4, hipMemcpyDeviceToDevice, nullptr));
+        script = b->script.as<uint8_t>(), pos_tab = b->pos_tab.as<uint32_t>(), k_mont = b->k_mont.as<uint32_t>();
+    }
+    unsigned long long* err = b->err.as<unsigned long long>();
+    uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
+    // A
+    decode_points(curve, ag.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, ag.proof_len, cols, np, m * (W + 1) + W,
+                  b->bases.as<uint32_t>() + (size_t)nkey * 2 * fqw, b->inf.as<uint32_t>() + nkey, b->a_bases.as<uint32_t>(), b->a_inf.as<uint32_t>(), err);
+    HIP_TRY(hipGetLastError());
+    // B, or the caller's challenges
+    DevOwned slots;                                                   // Solidity: the transcripts' memory, freed when the stages are through
+    if (challenges) {
+        HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
+    } else {
+        ProfScope ps("vfy_transcript", nullptr, v0.device);
+        const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+        const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
+        const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
+        uint32_t slot_words = 0;
+        // (the scripts' length bounds their messages; the proof's own: np commitments in compressed form, 2 W (+ 6) evaluations an instance)
+        if (solidity)
+            MZK_TRY(alloc_slots(slots, K, longest_extra + script_len + 32ull * ag.total_inputs + (uint64_t)np * g1_bytes(curve, true) + 32ull * m * (2 * W + 6),
+                                slot_words));
+        with_transcript(curve, solidity, [&](auto k) {
+            using S = decltype(k);
+            hipLaunchKernelGGL((vfy_agg_transcript_kernel<typename S::Fr, typename S::FqX, typename S::T>), grid, block, 0, nullptr, b->images.as<uint8_t>(),
+                               (unsigned long long)K, ag, script, pos_tab, b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(),
+                               slots.as<uint64_t>(), slot_words);
+        });
+        HIP_TRY(hipGetLastError());
+    }
+    // C and the fold
+    if (curve == MZK_CURVE_BLS12_381) launch_agg_scalars<BlsFr>(*b, K, ag, k_mont, pos_tab, proof_rows, err);
+    else launch_agg_scalars<BnFr>(*b, K, ag, k_mont, pos_tab, proof_rows, err);
+    HIP_TRY(hipGetLastError());
+    const auto name = [&](uint32_t inst, uint32_t field) {
+        if (batch_proofs) return "instance " + std::to_string(inst) + ": " + agg_field_name(ag, inst, field);
+        return field < VFY_FIELD_EVAL ? proof_point_name(W, field) : agg_field_name(ag, inst, field);
+    };
+    return publish_batch(std::move(b), "proof", name, out_u, 6 * 32, 7 * 32, out_batch, out_bad);
+}
+
+int32_t batch_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub, const uint8_t* extra,
+                    const uint64_t* extra_ranges, const uint64_t* challenges, uint32_t flags, uint64_t* out_batch, uint64_t* out_u, uint64_t* out_bad) {
+    const VfyAggShape& sh = vp->sh;
+    if (out_bad) *out_bad = ~0ull;
+    if (proof_len != sh.proof_len) {
+        if (out_bad) *out_bad = 0;
+        set_error("proof 0: length: " + std::to_string(proof_len) + " bytes, expected " + std::to_string(sh.proof_len) + " under this key");
+        return MZK_ERR_ENCODING;
+    }
+    for (uint64_t i = 0; i < K; i++) {
+        std::string why;
+        if (!proof_container_ok(sh, proofs + i * proof_len, why)) {
+            if (out_bad) *out_bad = i;
+            set_error("proof " + std::to_string(i) + ": " + why);
+            return MZK_ERR_ENCODING;
+        }
+    }
+    return proofs_begin({vp}, sh, vp->cols.as<uint32_t>(), false, proofs, K, pub, extra, extra_ranges, challenges, flags, out_batch, out_u, out_bad);
 }
 
 int32_t aggregate_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const uint8_t* proofs, uint64_t proof_len, uint64_t K, const uint64_t* pub,
@@ -599,8 +661,7 @@ int32_t aggregate_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const 
     mzk_batch_proof_layout_t L;
     MZK_TRY(tuple_shape(vs, ag, L));
     if (ag.total_inputs && !pub) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
-    const Verifier& v0 = *vs[0];
-    const uint32_t m = ag.m, W = ag.W, np = ag.np, nkey = ag.nkey, nkey1 = ag.nkey1;
+    const uint32_t m = ag.m, W = ag.W, G = ag.g1_bytes;
     if (out_bad) *out_bad = ~0ull;
     for (uint64_t i = 0; i < K; i++) {                               // (a wrong length is every proof's: reported for proof 0, as the single-proof path does)
         std::string why;
@@ -611,152 +672,38 @@ int32_t aggregate_begin(const std::vector<std::shared_ptr<Verifier>>& vs, const 
             return MZK_ERR_ENCODING;
         }
     }
-    uint64_t extra_len = 0;
-    if (extra_ranges)
-        for (uint64_t i = 0; i < K; i++) {
-            const uint64_t b = extra_ranges[2 * i], e = extra_ranges[2 * i + 1];
-            if (b == ~0ull) continue;
-            if (e < b || e - b >= (1ull << 31) || !extra) { set_error("bad extra message range"); return MZK_ERR_INVALID_ARG; }
-            extra_len = std::max(extra_len, e);
-        }
-    // the tables: columns of stage A (offset; instance << 8 | field), the positions' scripts and public-input ranges
-    std::vector<uint32_t> col_off, col_fld, pos_tab;
+    // the columns of stage A (offset; instance << 8 | field): what belongs to the whole proof counts as instance m
+    std::vector<uint32_t> col_off, col_fld;
     const auto col = [&](uint64_t off, uint32_t inst, uint32_t field) { col_off.push_back((uint32_t)off); col_fld.push_back(inst << 8 | field); };
     for (uint32_t j = 0; j < m; j++) {
-        for (uint32_t k = 0; k < W; k++) col(L.wires_off[j] + (uint64_t)k * ag.g1_bytes, j, k);
+        for (uint32_t k = 0; k < W; k++) col(L.wires_off[j] + (uint64_t)k * G, j, k);
         col(L.prod_perm_off[j], j, W);
     }
-    for (uint32_t k = 0; k < W; k++) col(L.split_quot_off + (uint64_t)k * ag.g1_bytes, m, k);
+    for (uint32_t k = 0; k < W; k++) col(L.split_quot_off + (uint64_t)k * G, m, k);
     col(L.opening_off, m, W);
     col(L.shifted_opening_off, m, W + 1);
     if (ag.ultra)
         for (uint32_t j = 0; j < m; j++) {
             col(L.h_off[j], j, W + 1);
-            col(L.h_off[j] + ag.g1_bytes, j, W + 2);
+            col(L.h_off[j] + G, j, W + 2);
             col(L.prod_lookup_off[j], j, W + 3);
         }
-    uint32_t script_len = 0, inputs = 0;
-    for (uint32_t j = 0; j < m; j++) {
-        pos_tab.insert(pos_tab.end(), {script_len, vs[j]->n_items, inputs});
-        script_len += vs[j]->script_len, inputs += vs[j]->sh.num_inputs;
-    }
-    pos_tab.insert(pos_tab.end(), {script_len, 0u, inputs});
-    const int curve = v0.curve;
-    const uint32_t fqw = fq_words(curve);
-    const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
-    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
-    b->v = vs[0], b->more.assign(vs.begin() + 1, vs.end()), b->K = K, b->np = np, b->nkey = nkey;
-    MZK_TRY(b->images.alloc(K * proof_len));
-    MZK_TRY(b->pub.alloc(K * ag.total_inputs * 32));
-    MZK_TRY(b->extra.alloc(extra_len));
-    MZK_TRY(b->extra_range.alloc(K * 16));
-    MZK_TRY(b->bases.alloc(n_bases * pt_bytes));
-    MZK_TRY(b->inf.alloc(n_bases * 4));
-    MZK_TRY(b->a_bases.alloc(2 * K * pt_bytes));
-    MZK_TRY(b->a_inf.alloc(2 * K * 4));
-    MZK_TRY(b->chal.alloc(K * 7 * 32));
-    MZK_TRY(b->key_rows.alloc(K * nkey * 32));
-    MZK_TRY(b->b_scal.alloc(n_bases * 32));
-    MZK_TRY(b->evals.alloc(K * 32));
-    MZK_TRY(b->a_scal.alloc(2 * K * 32));
-    MZK_TRY(b->weights.alloc(K * 32));
-    MZK_TRY(b->err.alloc(8));
-    MZK_TRY(b->col_off.alloc((size_t)np * 4));
-    MZK_TRY(b->col_fld.alloc((size_t)np * 4));
-    MZK_TRY(b->script.alloc(script_len));
-    MZK_TRY(b->pos_tab.alloc(pos_tab.size() * 4));
-    MZK_TRY(b->k_mont.alloc((size_t)m * W * 32));
-    MZK_TRY(b->partials.alloc(K * m * 32));
-    HIP_TRY(hipMemcpy(b->images.p, proofs, K * proof_len, hipMemcpyHostToDevice));
-    if (ag.total_inputs) HIP_TRY(hipMemcpy(b->pub.p, pub, K * ag.total_inputs * 32, hipMemcpyHostToDevice));
-    if (extra_len) HIP_TRY(hipMemcpy(b->extra.p, extra, extra_len, hipMemcpyHostToDevice));
-    if (extra_ranges) HIP_TRY(hipMemcpy(b->extra_range.p, extra_ranges, K * 16, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->col_off.p, col_off.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->col_fld.p, col_fld.data(), (size_t)np * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b->pos_tab.p, pos_tab.data(), pos_tab.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(b->err.p, 0xFF, 8));
-    for (uint32_t j = 0; j < m; j++) {                                // per POSITION: a repeated key repeats its block, its script and its k
-        const Verifier& v = *vs[j];
-        HIP_TRY(hipMemcpyAsync(b->bases.as<uint8_t>() + (size_t)j * nkey1 * pt_bytes, v.key_xy.p, nkey1 * pt_bytes, hipMemcpyDeviceToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(b->inf.as<uint32_t>() + (size_t)j * nkey1, v.key_inf.p, nkey1 * 4, hipMemcpyDeviceToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(b->script.as<uint8_t>() + pos_tab[3 * j], v.script.p, v.script_len, hipMemcpyDeviceToDevice, nullptr));
-        HIP_TRY(hipMemcpyAsync(b->k_mont.as<uint8_t>() + (size_t)j * W * 32, v.k_mont.p, (size_t)W * 32, hipMemcpyDeviceToDevice, nullptr));
-    }
-    HIP_TRY(hipMemcpyAsync(b->bases.as<uint8_t>() + (size_t)(nkey - 1) * pt_bytes, v0.key_xy.as<uint8_t>() + (size_t)nkey1 * pt_bytes, pt_bytes, hipMemcpyDeviceToDevice, nullptr));
-    HIP_TRY(hipMemcpyAsync(b->inf.as<uint32_t>() + (nkey - 1), v0.key_inf.as<uint32_t>() + nkey1, 4, hipMemcpyDeviceToDevice, nullptr));
-    unsigned long long* err = b->err.as<unsigned long long>();
-    uint32_t* bases = b->bases.as<uint32_t>() + (size_t)nkey * 2 * fqw;
-    uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
-    const bool validate = flags & MZK_SER_VALIDATE;
-    if (curve == MZK_CURVE_BLS12_381) launch_agg_decode<BlsFqX>(ag.compressed, validate, b->images.as<uint8_t>(), K, ag, *b, bases, b->inf.as<uint32_t>() + nkey, err);
-    else launch_agg_decode<BnFqX>(ag.compressed, validate, b->images.as<uint8_t>(), K, ag, *b, bases, b->inf.as<uint32_t>() + nkey, err);
-    HIP_TRY(hipGetLastError());
-    DevOwned slots;                                                   // Solidity: the transcripts' memory, freed when the stages are through
-    if (challenges) {
-        HIP_TRY(hipMemcpy(b->chal.p, challenges, K * 7 * 32, hipMemcpyHostToDevice));
-    } else {
-        const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
-        const unsigned long long* ranges = extra_ranges ? b->extra_range.as<unsigned long long>() : nullptr;
-        const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
-        uint32_t slot_words = 0;
-        if (solidity)
-            MZK_TRY(alloc_slots(slots, K, longest_extra(extra_ranges, K) + script_len + 32ull * ag.total_inputs + (uint64_t)np * g1_bytes(curve, true) +
-                                              32ull * m * (2 * W + 6), slot_words));
-#define MZK_VFY_TRANSCRIPT(Fr, FqX, T)                                                                                                                           \
-    hipLaunchKernelGGL((vfy_agg_transcript_kernel<Fr, FqX, T>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, ag, b->script.as<uint8_t>(), \
-                       b->pos_tab.as<uint32_t>(), b->pub.as<uint32_t>(), b->extra.as<uint8_t>(), ranges, b->chal.as<uint32_t>(), slots.as<uint64_t>(), slot_words)
-        if (curve == MZK_CURVE_BLS12_381) {
-            if (solidity) MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, keccak::SolidityTranscript);
-            else MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, merlin::Transcript);
-        } else {
-            if (solidity) MZK_VFY_TRANSCRIPT(BnFr, BnFqX, keccak::SolidityTranscript);
-            else MZK_VFY_TRANSCRIPT(BnFr, BnFqX, merlin::Transcript);
-        }
-#undef MZK_VFY_TRANSCRIPT
-        HIP_TRY(hipGetLastError());
-    }
-    if (curve == MZK_CURVE_BLS12_381) launch_agg_scalars<BlsFr>(*b, K, ag, proof_rows, err);
-    else launch_agg_scalars<BnFr>(*b, K, ag, proof_rows, err);
-    HIP_TRY(hipGetLastError());
-    unsigned long long bad = 0;
-    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));                             // (synchronises the stages)
-    if (bad != ~0ull) {
-        const uint64_t i = bad >> 40;
-        const uint32_t inst = (uint32_t)(bad >> 33) & 0x7F, field = (uint32_t)(bad >> 4) & 0x1FFFFFFF, reason = (uint32_t)bad & 0xF;
-        if (out_bad) *out_bad = i;
-        set_error("proof " + std::to_string(i) + ": instance " + std::to_string(inst) + ": " + agg_field_name(ag, inst, field) + ": " + reason_text(reason));
-        return MZK_ERR_ENCODING;
-    }
-    if (out_u) HIP_TRY(hipMemcpy2D(out_u, 32, b->chal.as<uint8_t>() + 6 * 32, 7 * 32, 32, K, hipMemcpyDeviceToHost));
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_batch = handle_make(v0.device, g_next_batch++);
-    g_batches[*out_batch] = std::move(b);
-    return MZK_OK;
+    DevOwned cols;                                                    // (the stages are through when proofs_begin returns)
+    MZK_TRY(upload_columns(cols, col_off, col_fld));
+    return proofs_begin(vs, ag, cols.as<uint32_t>(), true, proofs, K, pub, extra, extra_ranges, challenges, flags, out_batch, out_u, out_bad);
 }
 
 // ---- proof links (proof_linking.rs:240-286; verifier.cuh "proof links") ---------------------------------------------------------------------
 int32_t open_key_create(int32_t curve, int device, const uint8_t* g_bytes, const uint8_t* h_bytes, const uint8_t* beta_h_bytes, uint32_t flags, uint64_t* out_handle) {
-    const bool compressed = flags & MZK_SER_COMPRESSED, validate = flags & MZK_SER_VALIDATE;
+    const bool compressed = flags & MZK_SER_COMPRESSED;
     auto v = std::make_shared<Verifier>();
     v->curve = curve, v->device = device, v->open_only = true;
     v->sh.compressed = compressed, v->sh.g1_bytes = g1_bytes(curve, compressed);       // np = nkey = proof_len = 0: no verifying key
-    const uint32_t G = v->sh.g1_bytes, fqw = fq_words(curve);
-    VfyPoints pts{};
-    pts.n = 1, pts.stride = G, pts.open_idx = -1;
-    DevOwned image, err;
-    MZK_TRY(image.alloc(G));
-    MZK_TRY(err.alloc(8));
-    MZK_TRY(v->key_xy.alloc((size_t)2 * fqw * 4));
-    MZK_TRY(v->key_inf.alloc(4));
-    HIP_TRY(hipMemcpy(image.p, g_bytes, G, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(err.p, 0xFF, 8));
-    decode_points(curve, compressed, validate, image.as<uint8_t>(), 1, pts, v->key_xy.as<uint32_t>(), v->key_inf.as<uint32_t>(), nullptr, nullptr,
-                  err.as<unsigned long long>());
-    HIP_TRY(hipGetLastError());
+    const uint32_t fqw = fq_words(curve);
     unsigned long long bad = 0;
-    HIP_TRY(hipMemcpy(&bad, err.p, 8, hipMemcpyDeviceToHost));
+    MZK_TRY(decode_key_image(*v, flags & MZK_SER_VALIDATE, g_bytes, v->sh.g1_bytes, {0u}, bad));
     if (bad != ~0ull) {
-        set_error(std::string("open_key.g: ") + reason_text((uint32_t)(bad & 0xFF)));
+        set_error(std::string("open_key.g: ") + reason_text(error_fields(bad).reason));
         return MZK_ERR_ENCODING;
     }
     uint32_t inf = 0;
@@ -764,20 +711,9 @@ int32_t open_key_create(int32_t curve, int device, const uint8_t* g_bytes, const
     HIP_TRY(hipMemcpy(v->g.data(), v->key_xy.p, (size_t)2 * fqw * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&inf, v->key_inf.p, 4, hipMemcpyDeviceToHost));
     if (inf) std::fill(v->g.begin(), v->g.end(), 0);                 // (0, 0): as verifier_create keeps a flagged g
-    v->h.resize(4 * fqw / 2);
-    v->beta_h.resize(4 * fqw / 2);
-    if (mzk_g2_decode(curve, h_bytes, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->h.data()) != MZK_OK) {
-        set_error(std::string("open_key.h: ") + mzk_last_error());
-        return MZK_ERR_ENCODING;
-    }
-    if (mzk_g2_decode(curve, beta_h_bytes, flags & (MZK_SER_COMPRESSED | MZK_SER_VALIDATE), v->beta_h.data()) != MZK_OK) {
-        set_error(std::string("open_key.beta_h: ") + mzk_last_error());
-        return MZK_ERR_ENCODING;
-    }
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_handle = handle_make(device, g_next_verifier++);
-    g_verifiers[*out_handle] = std::move(v);
-    return MZK_OK;
+    MZK_TRY(decode_g2_pair(*v, flags, h_bytes, beta_h_bytes, "open_key."));
+    MZK_TRY(upload_link_columns(*v));
+    return publish_verifier(std::move(v), out_handle);
 }
 
 constexpr uint64_t LINK_MAX_SIZE = 1ull << 27;                       // the largest domain of the library (mzk_ntt)
@@ -800,40 +736,24 @@ int32_t link_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, 
         }
     }
     const uint32_t G = v.sh.g1_bytes, np = 4, nkey = 1, fqw = fq_words(curve);
-    const size_t pt_bytes = (size_t)2 * fqw * 4, n_bases = nkey + K * np;
+    const size_t pt_bytes = (size_t)2 * fqw * 4;
     auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
     b->v = vp, b->kind = BatchKind::Links, b->K = K, b->np = np, b->nkey = nkey;
     b->open_recs.resize(K * G);
     for (uint64_t i = 0; i < K; i++) std::memcpy(&b->open_recs[i * G], records + (i * 4 + 3) * G, G);
-    MZK_TRY(b->images.alloc(K * 4 * G));
+    MZK_TRY(stage_batch(*b, records, 4 * G, 1, 1));
     MZK_TRY(b->layouts.alloc(K * 24));
-    MZK_TRY(b->bases.alloc(n_bases * pt_bytes));
-    MZK_TRY(b->inf.alloc(n_bases * 4));
-    MZK_TRY(b->a_bases.alloc(K * pt_bytes));
-    MZK_TRY(b->a_inf.alloc(K * 4));
-    MZK_TRY(b->chal.alloc(K * 32));
     MZK_TRY(b->vanish.alloc(K * 32));
-    MZK_TRY(b->key_rows.alloc(K * nkey * 32));
-    MZK_TRY(b->b_scal.alloc(n_bases * 32));
-    MZK_TRY(b->evals.alloc(K * 32));
-    MZK_TRY(b->a_scal.alloc(K * 32));
-    MZK_TRY(b->weights.alloc(K * 32));
-    MZK_TRY(b->err.alloc(8));
-    HIP_TRY(hipMemcpy(b->images.p, records, K * 4 * G, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->layouts.p, layouts, K * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(b->err.p, 0xFF, 8));
     HIP_TRY(hipMemset(b->key_rows.p, 0, K * nkey * 32));              // open_key.g: scalar zero, and the opened value is 0
     HIP_TRY(hipMemset(b->evals.p, 0, K * 32));
     HIP_TRY(hipMemcpy(b->bases.p, v.key_xy.as<uint8_t>() + (size_t)v.g_index() * pt_bytes, pt_bytes, hipMemcpyDeviceToDevice));
     HIP_TRY(hipMemcpy(b->inf.p, v.key_inf.as<uint32_t>() + v.g_index(), 4, hipMemcpyDeviceToDevice));
     unsigned long long* err = b->err.as<unsigned long long>();
-    // A: the existing decoder over a 4-record image; the opening proofs (column 3) are then gathered as the bases of the MSM A
-    VfyPoints pts{};
-    pts.n = np, pts.stride = 4 * G, pts.open_idx = -1;
-    for (uint32_t j = 0; j < np; j++) pts.off[j] = j * G;
+    // A: no opening columns; the opening proofs (column 3) are then gathered as the bases of the MSM A
     uint8_t* own_bases = b->bases.as<uint8_t>() + (size_t)nkey * pt_bytes;
-    decode_points(curve, v.sh.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, pts, reinterpret_cast<uint32_t*>(own_bases), b->inf.as<uint32_t>() + nkey,
-                  nullptr, nullptr, err);
+    decode_points(curve, v.sh.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, 4 * G, v.link_cols.as<uint32_t>(), np, np, reinterpret_cast<uint32_t*>(own_bases),
+                  b->inf.as<uint32_t>() + nkey, nullptr, nullptr, err);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy2DAsync(b->a_bases.p, pt_bytes, own_bases + 3 * pt_bytes, 4 * pt_bytes, pt_bytes, K, hipMemcpyDeviceToDevice, nullptr));
     HIP_TRY(hipMemcpy2DAsync(b->a_inf.p, 4, b->inf.as<uint32_t>() + nkey + 3, 16, 4, K, hipMemcpyDeviceToDevice, nullptr));
@@ -847,17 +767,11 @@ int32_t link_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, 
         const bool solidity = flags & MZK_TRANSCRIPT_SOLIDITY;
         uint32_t slot_words = 0;
         if (solidity) MZK_TRY(alloc_slots(slots, K, 3ull * g1_bytes(curve, true), slot_words));
-#define MZK_VFY_TRANSCRIPT(Fr, FqX, T)                                                                                                                      \
-    hipLaunchKernelGGL((vfy_link_transcript_kernel<Fr, FqX, T>), grid, block, 0, nullptr, b->images.as<uint8_t>(), (unsigned long long)K, G, v.sh.compressed, \
-                       b->chal.as<uint32_t>(), slots.as<uint64_t>(), slot_words)
-        if (curve == MZK_CURVE_BLS12_381) {
-            if (solidity) MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, keccak::SolidityTranscript);
-            else MZK_VFY_TRANSCRIPT(BlsFr, BlsFqX, merlin::Transcript);
-        } else {
-            if (solidity) MZK_VFY_TRANSCRIPT(BnFr, BnFqX, keccak::SolidityTranscript);
-            else MZK_VFY_TRANSCRIPT(BnFr, BnFqX, merlin::Transcript);
-        }
-#undef MZK_VFY_TRANSCRIPT
+        with_transcript(curve, solidity, [&](auto k) {
+            using S = decltype(k);
+            hipLaunchKernelGGL((vfy_link_transcript_kernel<typename S::Fr, typename S::FqX, typename S::T>), grid, block, 0, nullptr, b->images.as<uint8_t>(),
+                               (unsigned long long)K, G, v.sh.compressed, b->chal.as<uint32_t>(), slots.as<uint64_t>(), slot_words);
+        });
         HIP_TRY(hipGetLastError());
     }
     // Cl
@@ -873,19 +787,7 @@ int32_t link_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, 
                                b->vanish.as<uint32_t>(), proof_rows);
         HIP_TRY(hipGetLastError());
     }
-    unsigned long long bad = 0;
-    HIP_TRY(hipMemcpy(&bad, b->err.p, 8, hipMemcpyDeviceToHost));                             // (synchronises the stages)
-    if (bad != ~0ull) {
-        const uint64_t i = bad >> 32;
-        if (out_bad) *out_bad = i;
-        set_error("link " + std::to_string(i) + ": " + LINK_FIELDS[(bad >> 8) & 3] + ": " + reason_text((uint32_t)bad & 0xFF));
-        return MZK_ERR_ENCODING;
-    }
-    if (out_eta) HIP_TRY(hipMemcpy(out_eta, b->chal.p, K * 32, hipMemcpyDeviceToHost));
-    std::lock_guard<std::mutex> lk(g_vfy_lock);
-    *out_batch = handle_make(v.device, g_next_batch++);
-    g_batches[*out_batch] = std::move(b);
-    return MZK_OK;
+    return publish_batch(std::move(b), "link", [](uint32_t, uint32_t field) { return std::string(LINK_FIELDS[field & 3]); }, out_eta, 0, 32, out_batch, out_bad);
 }
 
 // 64 challenge bytes mod r, Montgomery: vfy_reduce_challenge on the host (lo + 2^256 hi, each half below r by subtraction: 2^256 < 6 r)
@@ -964,11 +866,11 @@ extern "C" int32_t mzk_verifier_shape(uint64_t verifier, uint32_t* out_n_proof_p
     std::lock_guard<std::mutex> lk(g_vfy_lock);                       // host-only, no device bound: reads under the lock and holds no reference,
     auto it = g_verifiers.find(verifier);                             // so it is never the last holder (mzk_verifier_check likewise)
     if (it == g_verifiers.end()) { set_error("unknown verifier handle"); return MZK_ERR_BAD_HANDLE; }
-    const VfyShape& sh = it->second->sh;
+    const VfyAggShape& sh = it->second->sh;
     if (out_n_proof_points) *out_n_proof_points = sh.np;
     if (out_n_key_bases) *out_n_key_bases = sh.nkey;
     if (out_proof_len) *out_proof_len = sh.proof_len;
-    if (out_num_inputs) *out_num_inputs = sh.num_inputs;
+    if (out_num_inputs) *out_num_inputs = it->second->num_inputs();
     return MZK_OK;
 }
 
@@ -977,7 +879,7 @@ extern "C" int32_t mzk_verifier_batch_begin(uint64_t verifier, const uint8_t* pr
                                             uint64_t* out_batch, uint64_t* out_u_mont, uint64_t* out_bad_index) {
     ON_DEVICE_OF(verifier, v, find_verifier);
     if (v->open_only) { set_error("the verifier holds no verifying key"); return MZK_ERR_INVALID_ARG; }
-    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->sh.num_inputs && !public_inputs_canonical) || (flags & ~(MZK_SER_VALIDATE | MZK_TRANSCRIPT_SOLIDITY))) {
+    if (!proofs || !K || K >= (1ull << 24) || !out_batch || (v->num_inputs() && !public_inputs_canonical) || (flags & ~(MZK_SER_VALIDATE | MZK_TRANSCRIPT_SOLIDITY))) {
         set_error("bad argument");
         return MZK_ERR_INVALID_ARG;
     }
