@@ -402,6 +402,31 @@ MZK_API int32_t mzk_verifier_link_begin(uint64_t verifier, const uint8_t* record
 MZK_API int32_t mzk_verifier_link_values(uint64_t batch, uint64_t* out_eta_mont, uint64_t* out_vanishing_mont);
 MZK_API int32_t mzk_verifier_link_weights(uint64_t batch, const uint64_t* r_mont, uint64_t* out_weights_mont);
 
+/* ---- KZG openings: UnivariateKzgPCS::verify and batch_verify (univariate_kzg/mod.rs:195-271; DESIGN.md section 4.14, "KZG openings").  The
+ * opening of a commitment C at the point z to the value v with proof pi holds iff e(C - v g + z pi, h) = e(pi, beta_h): it ends in the pair
+ * A = pi, B = C + z pi - v g.  K openings go through the device in one pass and leave an ordinary batch handle, whose (A, B) sums with the
+ * (A, B) of proof, aggregate and link groups under the same open key into ONE check of two pairings.
+ *
+ * mzk_verifier_open_begin: `verifier` is ANY verifier handle, a full key or an open key: its curve, device and image mode are used.
+ * records: K x 2 G1 records of that mode, per opening the commitment, then the opening proof.  points_canonical, values_canonical: K x 4
+ * limbs each.  flags: MZK_SER_VALIDATE only (subgroup checks of the records).  On the host, before anything is staged: K = 0 and any other
+ * flag bit: MZK_ERR_INVALID_ARG.  On the device: A decode (the decoder of the proofs), Co one thread per opening: z and v range-checked
+ * against r and brought to Montgomery form.  A malformed opening: MZK_ERR_ENCODING, *out_bad_index (nullable) the LOWEST bad opening -- one
+ * 64-bit atomicMin, the same answer on every run -- and mzk_last_error() "opening <i>: <field>: <reason>", the field one of commitment |
+ * proof | point | value (the first of them that is bad), the reasons of a record those of mzk_srs_register_serialized, of a scalar "not
+ * below the modulus"; no batch is left open then.  Infinity is flagged, not refused: the zero polynomial commits to O, and a constant
+ * polynomial opens with pi = O.
+ * The batch: mzk_verifier_batch_scalars, _finish (discard too) and mzk_verifier_check take it under their contracts above with NKEY = 1
+ * (open_key.g), NP = 2 with the unweighted row (1, z_i), evaluation v_i, A = sum w_i pi_i and B = sum w_i (C_i + z_i pi_i) - (sum w_i v_i) g.
+ * mzk_verifier_batch_challenges, mzk_verifier_link_values and mzk_verifier_link_weights: MZK_ERR_INVALID_ARG, the message names the kind.
+ * The handle rules above hold (destroy of the verifier refused while the batch is open, released by mzk_shutdown).
+ * Weights are the caller's (r_weights_mont of mzk_verifier_batch_finish).  The reference's batch_verify takes w_0 = 1 and a random 128-bit
+ * w_i for every further opening; one opening with weight 1 is the reference's verify.  MIXED CHECKS: when an openings group is summed with
+ * other groups in one mzk_verifier_check, none of its weights may be 1 -- the first Plonk proof has weight r^0 = 1, and two members of
+ * one sum under equal weights can be chosen jointly so that their errors cancel (the reason given for links above). */
+MZK_API int32_t mzk_verifier_open_begin(uint64_t verifier, const uint8_t* records, uint64_t K, const uint64_t* points_canonical,
+                                        const uint64_t* values_canonical, uint32_t flags, uint64_t* out_batch, uint64_t* out_bad_index);
+
 /* ---- MSM: replaces <E::G1 as VariableBaseMSM>::msm_bigint(bases, bigints)
  *      at univariate_kzg/mod.rs:109-111 (commit) and :151-155 (open).
  * Computes sum_{i<n} scalars[i] * srs[base_offset + i]; base_offset = num_leading_zeros of
@@ -666,6 +691,19 @@ MZK_API int32_t mzk_poly_degree_dev(const void* d_poly, uint64_t len, uint64_t* 
  * coefficients either way.  d_out must not alias d_poly.  The call synchronises the stream (it reads p at the roots). */
 MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uint64_t len, uint32_t log_order, uint64_t first, uint64_t count,
                                        void* d_out, void* stream);
+/* UnivariateKzgPCS::batch_open (univariate_kzg/mod.rs:163-190, "a naive approach" there) in one pass: K polynomials resident on the device
+ * (d_polys[i]: lens[i] Montgomery Fr coefficients, low order first; ragged) opened at points_mont[i] (host, K x 4 limbs) ->
+ * out_proofs_xy_mont (host, K affine points x || y, Montgomery, (0, 0) = infinity) and out_evals_mont (host, K x 4 limbs, p_i(z_i)).
+ * For all K at once one kernel family (grid.y = polynomial) computes the witness coefficients q_k = c_{k+1} + z q_{k+1} and
+ * p(z) = c_0 + z q_0 as a scan of affine maps that share the multiplier z -- no inverse of z and no power tables, so z = 0 is no special
+ * case -- and the K witnesses go through ONE batch MSM (as mzk_msm_batch_dev: len - 1 points from base offset 0 each; zero
+ * coefficients, leading ones included, contribute nothing), the only place where the call waits: once per fused group of that MSM -- up to
+ * six polynomials of one window size -- and not once per polynomial.  The witness scratch comes from the shared
+ * workspace; past the budget (1 GiB, or MZK_OPEN_BATCH_BUDGET bytes, read at every call) the polynomials are processed in chunks, each
+ * with its own MSM and wait.  lens[i] = 0: proof O, evaluation 0; lens[i] = 1: proof O, evaluation c_0.
+ * lens[i] - 1 above the SRS: MZK_ERR_INVALID_ARG, the degree guard of mzk_msm.  Synchronises the stream. */
+MZK_API int32_t mzk_kzg_open_batch_dev(uint64_t srs_handle, uint32_t K, const void* const* d_polys, const uint64_t* lens, const uint64_t* points_mont,
+                                       uint64_t* out_proofs_xy_mont, uint64_t* out_evals_mont, void* stream);
 
 /* ---- the prover's rounds on device-resident state: replaces the BODIES of Prover::run_1st_round .. compute_opening_proofs
  *      (plonk/src/proof_system/prover.rs:72-419) as PlonkKzgSnark::batch_prove_internal calls them (snark.rs:263-431).

@@ -237,6 +237,9 @@ int32_t poly_eval_dispatch(int curve, const uint32_t* d_coeffs, uint64_t stride,
 struct EvalJob { const uint32_t* d; uint64_t len, stride; uint32_t batch, which_x; };
 int32_t poly_eval_many_dispatch(int curve, const EvalJob* jobs, uint32_t n_jobs, const uint32_t* x_mont /* 2 x 8 words */, uint32_t* out_host, hipStream_t st);
 int32_t poly_div_dispatch(int curve, const uint32_t* d_poly, uint64_t len, const uint32_t* z_mont, uint32_t* d_out, uint32_t* d_rem /* nullable: p(z) */, hipStream_t st);
+// K openings in one pass: proofs to out_xy (host, affine), evaluations to out_evals (host); waits for the stream (its MSMs do)
+int32_t kzg_open_batch_dispatch(const Srs& s, uint32_t K, const uint32_t* const* d_polys, const uint64_t* lens, const uint32_t* points_mont, uint64_t* out_xy,
+                                uint32_t* out_evals, hipStream_t st);
 int32_t poly_div_roots_dispatch(int curve, const uint32_t* d_poly, uint64_t len, uint32_t log_order, uint64_t first, uint64_t count, uint32_t* d_out,
                                 hipStream_t st);
 int32_t poly_lincomb_dispatch(int curve, uint32_t n_terms, const uint32_t* const* d_polys, const uint64_t* lens, const uint32_t* scalars, uint32_t* d_out,

@@ -1111,6 +1111,15 @@ int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uint64_t le
     return poly_div_roots_dispatch(curve_id, reinterpret_cast<const uint32_t*>(d_poly), len, log_order, first, count, reinterpret_cast<uint32_t*>(d_out),
                                    (hipStream_t)stream);
 }
+int32_t mzk_kzg_open_batch_dev(uint64_t srs_handle, uint32_t K, const void* const* d_polys, const uint64_t* lens, const uint64_t* points_mont,
+                               uint64_t* out_proofs_xy_mont, uint64_t* out_evals_mont, void* stream) {
+    ENTER_HANDLE(srs_handle);
+    const Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    if (K && (!d_polys || !lens || !points_mont || !out_proofs_xy_mont || !out_evals_mont)) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    return kzg_open_batch_dispatch(*s, K, reinterpret_cast<const uint32_t* const*>(d_polys), lens, reinterpret_cast<const uint32_t*>(points_mont),
+                                   out_proofs_xy_mont, reinterpret_cast<uint32_t*>(out_evals_mont), (hipStream_t)stream);
+}
 
 // ---- page-locked host memory for the host-pointer entry points ------------------------------------------
 int32_t mzk_host_alloc(uint64_t bytes, void** out_ptr) {

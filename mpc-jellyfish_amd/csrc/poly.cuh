@@ -263,6 +263,142 @@ __global__ __launch_bounds__(POLY_THREADS) void poly_div_finish_kernel(const uin
     store_fp<P>(q + k * 8, s * load_fp<P>(zinvpow + (k + 1) * 8));
 }
 
+// ---- batched KZG opening (univariate_kzg/mod.rs:135-190): for K polynomials at once, s_j = sum_{i >= j} c_i z^(i - j) -----------------
+// The witness of p at z has the coefficients q_k = c_{k+1} + z q_{k+1} = s_{k+1}, and p(z) = c_0 + z q_0 = s_0: a scan of the affine maps
+// x -> c_j + z x, which all share the multiplier z, so composing 2^l of them needs the one power z^(2^l) and no inverse of z (z = 0 is no
+// special case) and no table of powers in HBM.  Structured as the suffix sum above, grid.y = polynomial:
+//   kzg_open_block_kernel   a thread runs Horner over its DIV_E coefficients, the workgroup scans in LDS with z^(E 2^l) at level l;
+//                           s of the BLOCK alone -> s, the block's value at its first index -> totals
+//   kzg_open_carry_kernel   one workgroup per polynomial: totals[b] <- s at the first index of block b + 1 (the same scan over blocks,
+//                           multiplier z^DIV_BLOCK); p(z) -> evals
+//   kzg_open_finish_kernel  s_j += carry_b z^((b + 1) DIV_BLOCK - j) in every block but a polynomial's last
+// A polynomial is an OpenJob in device memory; blocks past its length leave at once (ragged batches share one grid).
+struct OpenJob {
+    const uint32_t* c;                          // len coefficients, Montgomery
+    unsigned long long len, s_off, tot_off;     // elements: its s in the s array, its first block in totals
+    uint32_t z[8];
+};
+static_assert(DIV_E == 8, "kzg_open_*: z^DIV_E is three squarings");
+constexpr int DIV_BLOCK_LOG = 11;
+static_assert(DIV_BLOCK == 1 << DIV_BLOCK_LOG, "kzg_open_carry_kernel: z^DIV_BLOCK by squarings");
+
+template <class P>
+__global__ __launch_bounds__(POLY_THREADS) void kzg_open_block_kernel(const OpenJob* __restrict__ jobs, uint32_t* __restrict__ s_all, uint32_t* __restrict__ totals_all) {
+    using F = Fp<P>;
+    __shared__ uint4 sh[2 * POLY_THREADS];
+    auto put = [&](int i, const F& x) { sh[2 * i] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]); sh[2 * i + 1] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]); };
+    auto get = [&](int i) { F x; uint4 p = sh[2 * i], q = sh[2 * i + 1]; x.l[0] = p.x; x.l[1] = p.y; x.l[2] = p.z; x.l[3] = p.w; x.l[4] = q.x; x.l[5] = q.y; x.l[6] = q.z; x.l[7] = q.w; return x; };
+    const OpenJob& jb = jobs[blockIdx.y];
+    const unsigned long long n = jb.len;
+    if ((unsigned long long)blockIdx.x * DIV_BLOCK >= n) return;            // (the whole workgroup: nothing below is reached by part of one)
+    const uint32_t* __restrict__ c = jb.c;
+    uint32_t* __restrict__ s = s_all + jb.s_off * 8;
+    const F z = load_fp<P>(jb.z);
+    const int r = POLY_THREADS - 1 - threadIdx.x;                           // r = 0 owns the highest indices
+    const unsigned long long base = (unsigned long long)blockIdx.x * DIV_BLOCK + (unsigned long long)threadIdx.x * DIV_E;
+    F v[DIV_E];
+    F run = F::zero();
+#pragma unroll
+    for (int q = DIV_E - 1; q >= 0; q--) {
+        const F x = base + q < n ? load_fp<P>(c + (base + q) * 8) : F::zero();
+        run = run * z + x;
+        v[q] = run;
+    }
+    F incl = run, pw = sqr(sqr(sqr(z)));                                    // z^E: from a thread's first index to the next thread's
+    put(r, incl);
+    __syncthreads();
+    for (int d = 1; d < POLY_THREADS; d <<= 1) {
+        F other = F::zero();
+        const bool has = r >= d;
+        if (has) other = get(r - d);
+        __syncthreads();
+        if (has) incl = incl + pw * other;
+        put(r, incl);
+        __syncthreads();
+        pw = sqr(pw);
+    }
+    F above = r ? get(r - 1) : F::zero();                                   // the block's s at the next thread's first index
+#pragma unroll
+    for (int q = DIV_E - 1; q >= 0; q--) {
+        above = above * z;
+        if (base + q < n) store_fp<P>(s + (base + q) * 8, v[q] + above);
+    }
+    if (r == POLY_THREADS - 1) store_fp<P>(totals_all + (jb.tot_off + blockIdx.x) * 8, incl);
+}
+template <class P>
+__global__ __launch_bounds__(POLY_THREADS) void kzg_open_carry_kernel(const OpenJob* __restrict__ jobs, uint32_t* __restrict__ totals_all, uint32_t* __restrict__ evals) {
+    using F = Fp<P>;
+    __shared__ uint4 sh[2 * POLY_THREADS];
+    auto put = [&](int i, const F& x) { sh[2 * i] = make_uint4(x.l[0], x.l[1], x.l[2], x.l[3]); sh[2 * i + 1] = make_uint4(x.l[4], x.l[5], x.l[6], x.l[7]); };
+    auto get = [&](int i) { F x; uint4 p = sh[2 * i], q = sh[2 * i + 1]; x.l[0] = p.x; x.l[1] = p.y; x.l[2] = p.z; x.l[3] = p.w; x.l[4] = q.x; x.l[5] = q.y; x.l[6] = q.z; x.l[7] = q.w; return x; };
+    const OpenJob& jb = jobs[blockIdx.x];
+    const unsigned long long n_blocks = (jb.len + DIV_BLOCK - 1) / DIV_BLOCK;
+    if (n_blocks == 0) {                                                    // the empty polynomial evaluates to 0
+        if (threadIdx.x == 0) store_fp<P>(evals + (size_t)blockIdx.x * 8, F::zero());
+        return;
+    }
+    uint32_t* __restrict__ totals = totals_all + jb.tot_off * 8;
+    F zb = load_fp<P>(jb.z);
+#pragma unroll 1
+    for (int k = 0; k < DIV_BLOCK_LOG; k++) zb = sqr(zb);                   // z^DIV_BLOCK: from a block's first index to the next block's
+    const unsigned long long per = (n_blocks + POLY_THREADS - 1) / POLY_THREADS;
+    const int r = POLY_THREADS - 1 - (int)threadIdx.x;                      // r = 0 owns the highest blocks
+    const unsigned long long lo = min(n_blocks, threadIdx.x * per), hi = min(n_blocks, lo + per);
+    F mine = F::zero();
+    for (unsigned long long b = hi; b-- > lo;) mine = mine * zb + load_fp<P>(totals + b * 8);
+    F pw = F::one();                                                        // zb^per: from a thread's first block to the next thread's
+    {
+        F sq = zb;
+        for (unsigned long long e = per; e; e >>= 1) {
+            if (e & 1) pw = pw * sq;
+            sq = sqr(sq);
+        }
+    }
+    F incl = mine;
+    put(r, incl);
+    __syncthreads();
+    const int live = (int)((n_blocks + per - 1) / per);                     // threads that own blocks: what lies further away is zero
+    for (int d = 1; d < live; d <<= 1) {
+        F other = F::zero();
+        const bool has = r >= d;
+        if (has) other = get(r - d);
+        __syncthreads();
+        if (has) incl = incl + pw * other;
+        put(r, incl);
+        __syncthreads();
+        pw = sqr(pw);
+    }
+    F run = r ? get(r - 1) : F::zero();                                     // s at the first index of block hi
+    for (unsigned long long b = hi; b-- > lo;) {
+        const F t = load_fp<P>(totals + b * 8);
+        store_fp<P>(totals + b * 8, run);
+        run = t + zb * run;
+    }
+    if (threadIdx.x == 0) store_fp<P>(evals + (size_t)blockIdx.x * 8, run);  // s_0 = p(z)
+}
+template <class P>
+__global__ __launch_bounds__(POLY_THREADS) void kzg_open_finish_kernel(const OpenJob* __restrict__ jobs, uint32_t* __restrict__ s_all, const uint32_t* __restrict__ totals_all) {
+    using F = Fp<P>;
+    const OpenJob& jb = jobs[blockIdx.y];
+    if (((unsigned long long)blockIdx.x + 1) * DIV_BLOCK >= jb.len) return;  // a polynomial's last block has nothing above it; every other block is full
+    uint32_t* __restrict__ s = s_all + jb.s_off * 8;
+    const F z = load_fp<P>(jb.z);
+    const unsigned r = POLY_THREADS - 1 - threadIdx.x;
+    const unsigned long long base = (unsigned long long)blockIdx.x * DIV_BLOCK + (unsigned long long)threadIdx.x * DIV_E;
+    F p = load_fp<P>(totals_all + (jb.tot_off + blockIdx.x) * 8);           // carry z^(E r), then one more z per index down
+    F sq = sqr(sqr(sqr(z)));
+#pragma unroll 1
+    for (unsigned e = r; e; e >>= 1) {
+        if (e & 1) p = p * sq;
+        sq = sqr(sq);
+    }
+#pragma unroll
+    for (int q = DIV_E - 1; q >= 0; q--) {
+        p = p * z;
+        store_fp<P>(s + (base + q) * 8, load_fp<P>(s + (base + q) * 8) + p);
+    }
+}
+
 // ---- mask_polynomial (prover.rs:463-486): p += (b_0 + b_1 X + .. + b_{h}) (X^n - 1), for up to 8 polynomials at once.
 // p has n coefficients (an iNTT output) in a row of at least n + h + 1 slots: p[j] -= b_j, p[n + j] = b_j.
 constexpr int MASK_MAX_ROWS = 8;

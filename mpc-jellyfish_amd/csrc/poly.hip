@@ -114,6 +114,77 @@ int32_t div_run(const uint32_t* d_poly, uint64_t len, const uint32_t* z_mont, ui
     return MZK_OK;
 }
 
+// The quotient scratch of one chunk of a batched opening: MZK_OPEN_BATCH_BUDGET bytes when set (read at every call), else 1 GiB
+uint64_t open_batch_budget() {
+    const char* b = std::getenv("MZK_OPEN_BATCH_BUDGET");
+    return b ? std::strtoull(b, nullptr, 10) : 1ull << 30;
+}
+constexpr uint32_t OPEN_BATCH_MAX_POLYS = 32768;                   // grid.y of one chunk
+
+// K openings (poly.cuh, "batched KZG opening").  Polynomials are taken in order; a chunk closes before the polynomial whose s array would
+// take its scratch past the budget (one polynomial larger than the budget is a chunk of its own) or after OPEN_BATCH_MAX_POLYS.  Per chunk:
+// the jobs uploaded, three launches, the evaluations' copy queued, ONE msm_batch_dispatch over the chunk's quotients -- the only place where
+// the chunk waits (once per fused group of MSMs).
+template <class P>
+int32_t open_batch_run(const Srs& srs, uint32_t K, const uint32_t* const* d_polys, const uint64_t* lens, const uint32_t* points_mont, uint64_t* out_xy,
+                       uint32_t* out_evals, hipStream_t st) {
+    const size_t fw = fq_words(srs.curve);
+    const auto blocks_of = [](uint64_t len) { return (len + DIV_BLOCK - 1) / DIV_BLOCK; };
+    const auto bytes_of = [&](uint64_t len) { return (len + blocks_of(len)) * 32 + sizeof(OpenJob) + 32; };
+    const uint64_t budget = open_batch_budget();
+    std::vector<uint32_t> ends;                                    // chunk c: polynomials [ends[c - 1], ends[c])
+    uint64_t largest = 0, used = 0;
+    for (uint32_t i = 0, first = 0; i < K; i++) {
+        if (i > first && (used + bytes_of(lens[i]) > budget || i - first == OPEN_BATCH_MAX_POLYS)) { ends.push_back(i); first = i; used = 0; }
+        used += bytes_of(lens[i]);
+        largest = std::max(largest, used);
+    }
+    ends.push_back(K);
+    WsHold ws; MZK_TRY(ws.acquire(st));
+    MZK_TRY(ws->poly_tmp.reserve(largest));
+    std::vector<OpenJob> jobs;
+    std::vector<const uint32_t*> quot;
+    std::vector<uint64_t> quot_len;
+    std::vector<uint32_t> xyz;
+    const auto chunk = [&](uint32_t i0, uint32_t i1) -> int32_t {
+        const uint32_t kc = i1 - i0;
+        uint64_t n_s = 0, n_tot = 0, max_blocks = 0;
+        jobs.resize(kc), quot.resize(kc), quot_len.resize(kc), xyz.resize((size_t)kc * 3 * fw);
+        for (uint32_t j = 0; j < kc; j++) {
+            OpenJob& jb = jobs[j];
+            jb.c = d_polys[i0 + j], jb.len = lens[i0 + j], jb.s_off = n_s, jb.tot_off = n_tot;
+            std::memcpy(jb.z, points_mont + (size_t)(i0 + j) * 8, 32);
+            n_s += jb.len, n_tot += blocks_of(jb.len);
+            max_blocks = std::max<uint64_t>(max_blocks, blocks_of(jb.len));
+        }
+        uint32_t* s = ws->poly_tmp.as<uint32_t>();
+        uint32_t* totals = s + n_s * 8;
+        uint32_t* d_evals = totals + n_tot * 8;
+        OpenJob* d_jobs = reinterpret_cast<OpenJob*>(d_evals + (size_t)kc * 8);
+        HIP_TRY(hipMemcpyAsync(d_jobs, jobs.data(), kc * sizeof(OpenJob), hipMemcpyHostToDevice, st));
+        if (max_blocks) hipLaunchKernelGGL((kzg_open_block_kernel<P>), dim3((unsigned)max_blocks, kc), dim3(POLY_THREADS), 0, st, d_jobs, s, totals);
+        hipLaunchKernelGGL((kzg_open_carry_kernel<P>), dim3(kc), dim3(POLY_THREADS), 0, st, d_jobs, totals, d_evals);
+        if (max_blocks > 1) hipLaunchKernelGGL((kzg_open_finish_kernel<P>), dim3((unsigned)max_blocks - 1, kc), dim3(POLY_THREADS), 0, st, d_jobs, s, totals);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out_evals + (size_t)i0 * 8, d_evals, (size_t)kc * 32, hipMemcpyDeviceToHost, st));
+        bool any = false;
+        for (uint32_t j = 0; j < kc; j++) {                           // the witness: s_1 .. s_(len - 1) over the first len - 1 points
+            quot[j] = s + (jobs[j].s_off + 1) * 8;
+            quot_len[j] = jobs[j].len ? jobs[j].len - 1 : 0;
+            any |= quot_len[j] != 0;
+        }
+        MZK_TRY(msm_batch_dispatch(srs, kc, quot.data(), quot_len.data(), nullptr, 1, xyz.data(), st));
+        if (!any) HIP_TRY(hipStreamSynchronize(st));                  // (no MSM ran: the evaluations are still on their way)
+        jac_to_affine_host_dispatch(srs.curve, reinterpret_cast<const uint64_t*>(xyz.data()), kc, out_xy + (size_t)i0 * fw);
+        return MZK_OK;
+    };
+    for (size_t c = 0, i0 = 0; c < ends.size(); i0 = ends[c++]) {
+        const int32_t rc = chunk((uint32_t)i0, ends[c]);
+        if (rc != MZK_OK) { (void)hipStreamSynchronize(st); return rc; }   // the queued copies read the host vectors above
+    }
+    return MZK_OK;
+}
+
 template <class P> struct FrXOf;
 template <> struct FrXOf<BlsFr> { using type = BlsFrX; };
 template <> struct FrXOf<BnFr> { using type = BnFrX; };
@@ -247,6 +318,19 @@ int32_t poly_div_dispatch(int curve, const uint32_t* d_poly, uint64_t len, const
     if (curve == 1) return div_run<BnFr>(d_poly, len, z_mont, d_out, d_rem, st);
     set_error("unknown curve_id");
     return MZK_ERR_INVALID_ARG;
+}
+int32_t kzg_open_batch_dispatch(const Srs& s, uint32_t K, const uint32_t* const* d_polys, const uint64_t* lens, const uint32_t* points_mont, uint64_t* out_xy,
+                                uint32_t* out_evals, hipStream_t st) {
+    for (uint32_t i = 0; i < K; i++) {
+        if (lens[i] && !d_polys[i]) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+        if (lens[i] > s.n + 1) {                                       // the witness has len - 1 coefficients
+            set_error("MSM longer than the registered SRS (poly degree larger than allowed)");
+            return MZK_ERR_INVALID_ARG;
+        }
+    }
+    if (K == 0) return MZK_OK;
+    if (s.curve == MZK_CURVE_BLS12_381) return open_batch_run<BlsFr>(s, K, d_polys, lens, points_mont, out_xy, out_evals, st);
+    return open_batch_run<BnFr>(s, K, d_polys, lens, points_mont, out_xy, out_evals, st);
 }
 int32_t poly_div_roots_dispatch(int curve, const uint32_t* d_poly, uint64_t len, uint32_t log_order, uint64_t first, uint64_t count, uint32_t* d_out, hipStream_t st) {
     if (curve == 0) return div_roots_run<BlsFr>(curve, d_poly, len, log_order, first, count, d_out, st);

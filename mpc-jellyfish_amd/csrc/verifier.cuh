@@ -1,7 +1,7 @@
 // verifier.cuh -- the per-proof work of PlonkKzgSnark::batch_verify and verify_batch_proof on the device: K images
 // of proof_len bytes, each of m instances under a tuple of m keys of one type, domain and open key.  ONE set of stages serves two image
 // layouts, both described by a VfyAggShape and a column table: a `Proof` (structs.rs:59-84; m = 1, the strides unused) and a `BatchProof`
-// (structs.rs:266-291; instance j's records at base + j * stride).  Proof links (verify_link_proof): the last section.
+// (structs.rs:266-291; instance j's records at base + j * stride).  Proof links (verify_link_proof) and KZG openings (UnivariateKzgPCS::verify): the last two sections.
 //   A  vfy_decode_kernel          one thread per G1 record: the decoder of srs_io.cuh in its infinity-tolerant mode -> the base array;
 //                                 offsets and field names from device memory (a key image and a link's four records go through it too)
 //   B  vfy_agg_transcript_kernel  one thread per proof: compute_challenges over m keys (verifier.rs:256-321) -> 7 challenges; T is
@@ -598,6 +598,36 @@ __global__ __launch_bounds__(VFY_THREADS) void vfy_link_vanishing_kernel(const u
         store_fp<P>(row + 16, neg(z));
         store_fp<P>(row + 24, x);
     }
+}
+
+// ---- KZG openings --------------------------------------------------------------------------------------------------------------------
+// UnivariateKzgPCS::verify / batch_verify (univariate_kzg/mod.rs:195-271) for K openings, each staged as 2 G1 records back to back -- the
+// commitment C, the opening proof pi -- with its point z and value v as canonical limbs.  e(C - v g + z pi, h) = e(pi, beta_h), so an
+// opening ends in the pair  A = pi,  B = C + z pi - v g  and joins the groups above:
+//   key bases    open_key.g alone (NKEY = 1), its column the evaluations' (-sum w_i v_i)    proof points  the 2 records, row (1, z) (NP = 2)
+//   A  vfy_decode_kernel     over the 2 records, no opening columns (infinity flagged: the zero polynomial commits to O, a constant opens with pi = O)
+//   Co vfy_open_rows_kernel  one thread per opening: z, v range-checked against r (fields 2, 3 after the records' 0, 1) and brought to
+//                            Montgomery form; the unweighted row (1, z), the evaluation v, z itself, the proof's infinity flag for the MSM A
+//   finish                   vfy_weight_kernel<P, 1> (one A base per opening), vfy_colsum_kernel over the one key column
+constexpr uint32_t VFY_OPEN_FIELD_POINT = 2, VFY_OPEN_FIELD_VALUE = 3;
+template <class P>
+__global__ __launch_bounds__(VFY_THREADS) void vfy_open_rows_kernel(unsigned long long K, const uint32_t* __restrict__ points, const uint32_t* __restrict__ values,
+                                                                    const uint32_t* __restrict__ inf_flags /* K x 2 */, uint32_t* __restrict__ a_inf,
+                                                                    uint32_t* __restrict__ z_mont, uint32_t* __restrict__ key_rows, uint32_t* __restrict__ proof_rows,
+                                                                    uint32_t* __restrict__ evals, unsigned long long* __restrict__ err) {
+    using F = Fp<P>;
+    const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= K) return;
+    const F z = load_fp<P>(points + i * 8ull), v = load_fp<P>(values + i * 8ull);
+    if (!ser_below_modulus<P>(z.l)) vfy_agg_report(err, i, 0, VFY_OPEN_FIELD_POINT, VFY_REASON_NOT_BELOW_R);
+    if (!ser_below_modulus<P>(v.l)) vfy_agg_report(err, i, 0, VFY_OPEN_FIELD_VALUE, VFY_REASON_NOT_BELOW_R);
+    const F zm = to_mont(z);
+    store_fp<P>(z_mont + i * 8ull, zm);
+    store_fp<P>(proof_rows + i * 16ull, F::one());
+    store_fp<P>(proof_rows + i * 16ull + 8, zm);
+    store_fp<P>(evals + i * 8ull, to_mont(v));
+    store_fp<P>(key_rows + i * 8ull, F::zero());                  // open_key.g: its scalar is the evaluations' column sum (vfy_colsum_kernel)
+    a_inf[i] = inf_flags[2 * i + 1];
 }
 
 }  // namespace mzk

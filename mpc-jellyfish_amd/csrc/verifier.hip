@@ -1,6 +1,7 @@
 // verifier.hip -- mzk_verifier_*: PlonkKzgSnark::batch_verify for single-instance proofs (snark.rs:141-190, verifier.rs:68-251) and
 // verify_batch_proof for aggregated BatchProofs under a tuple of keys (snark.rs:117-138; mzk_verifier_aggregate_*), verify_link_proof for
-// proof links under an open key (proof_linking.rs:240-286; mzk_verifier_create_open_key, mzk_verifier_link_*).  The per-proof
+// proof links under an open key (proof_linking.rs:240-286; mzk_verifier_create_open_key, mzk_verifier_link_*), UnivariateKzgPCS::verify /
+// batch_verify for KZG openings (univariate_kzg/mod.rs:195-271; mzk_verifier_open_begin).  The per-proof
 // work runs on the device (verifier.cuh: decode, Fiat-Shamir, linearisation scalars), the two MSMs through the variable-base path over a base
 // array registered per batch, the two pairings on the host (hostpairing.hpp behind mzk_pairing_product_is_one).  A single proof is an
 // aggregate of one instance under a tuple of one key: both containers go through proofs_begin, each with the layout of its image.
@@ -19,7 +20,7 @@ struct Verifier {
     VfyAggShape sh{};                                             // a `Proof` image under this key: one instance, total_inputs the key's num_inputs
                                                                   // (sh.compressed: the mode of the key image and of every proof under it)
     DevOwned key_xy, key_inf, k_mont, script;
-    DevOwned cols, pos_tab, link_cols;                            // the column tables of a `Proof` image and of a link's records, the one-position table (verifier.cuh)
+    DevOwned cols, pos_tab, link_cols, open_cols;                 // the column tables of a `Proof` image, of a link's and of an opening's records, the one-position table (verifier.cuh)
     uint32_t n_items = 0, script_len = 0;
     std::vector<uint64_t> h, beta_h;                              // mzk_g2_decode's output
     std::vector<uint64_t> g;                                      // open_key.g as decoded (host copy: an aggregate's tuple compares open keys)
@@ -27,13 +28,13 @@ struct Verifier {
     uint32_t g_index() const { return open_only ? 0 : sh.nkey - 1; }   // open_key.g in key_xy / key_inf
     uint32_t num_inputs() const { return sh.total_inputs; }       // this key's public inputs: the total of a tuple of one
 };
-enum class BatchKind { Proofs, Links };                           // Proofs: single proofs and aggregates (two A bases each); Links: one A base each
+enum class BatchKind { Proofs, Links, Openings };                 // Proofs: single proofs and aggregates (two A bases each); Links, Openings: one A base each
 struct Batch {
     std::shared_ptr<Verifier> v;                                  // an open batch keeps its verifier alive ...
     std::vector<std::shared_ptr<Verifier>> more;                  // ... and an aggregate batch the verifiers at positions 1 .. m - 1 of its tuple too
     BatchKind kind = BatchKind::Proofs;
     uint64_t K = 0;
-    uint32_t np = 0, nkey = 0;                                    // columns of one proof's row and of the key row (an aggregate: NP(m), NKEY(m); links: 4, 1)
+    uint32_t np = 0, nkey = 0;                                    // columns of one proof's row and of the key row (an aggregate: NP(m), NKEY(m); links: 4, 1; openings: 2, 1)
     DevOwned images, pub, extra, extra_range, bases, inf, a_bases, a_inf, chal, key_rows, b_scal, evals, a_scal, weights, err;
     DevOwned script, pos_tab, k_mont;                             // a tuple's tables, gathered per position (a tuple of one key reads its verifier's)
     DevOwned layouts, vanish;                                     // links: K x (alignment, offset, size); Z_D(eta_i) (eta_i: the first K values of chal)
@@ -206,10 +207,11 @@ int32_t decode_g2_pair(Verifier& v, uint32_t flags, const uint8_t* h, const uint
     }
     return MZK_OK;
 }
-// A link's four records stand back to back: their column table, kept on every verifier (either kind verifies links) so that link_begin
-// uploads nothing
+// A link's four records stand back to back, an opening's two: their column tables, kept on every verifier (either kind verifies links
+// and openings) so that link_begin and open_begin upload nothing
 int32_t upload_link_columns(Verifier& v) {
     const uint32_t G = v.sh.g1_bytes;
+    MZK_TRY(upload_columns(v.open_cols, {0, G}));
     return upload_columns(v.link_cols, {0, G, 2 * G, 3 * G});
 }
 int32_t publish_verifier(std::shared_ptr<Verifier> v, uint64_t* out_handle) {
@@ -392,12 +394,12 @@ int32_t batch_finish(Batch& b, const uint64_t* weights, uint64_t* out_A, uint64_
     const uint64_t K = b.K;
     const uint32_t np = b.np, nkey = b.nkey;
     HIP_TRY(hipMemcpy(b.weights.p, weights, K * 32, hipMemcpyHostToDevice));
-    const bool links = b.kind == BatchKind::Links;
+    const bool links = b.kind != BatchKind::Proofs;                   // a link, an opening: A over its one opening proof
     if (v.curve == MZK_CURVE_BLS12_381) links ? launch_finish<BlsFr, 1>(b, K, np, nkey) : launch_finish<BlsFr, 2>(b, K, np, nkey);
     else links ? launch_finish<BnFr, 1>(b, K, np, nkey) : launch_finish<BnFr, 2>(b, K, np, nkey);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    // the two MSMs of verifier.rs:217-247 through the variable-base path (links: A over the K opening proofs)
+    // the two MSMs of verifier.rs:217-247 through the variable-base path (links, openings: A over the K opening proofs)
     const struct { void* bases; void* scalars; uint64_t n; uint64_t* out; } jobs[2] = {{b.a_bases.p, b.a_scal.p, links ? K : 2 * K, out_A},
                                                                                       {b.bases.p, b.b_scal.p, nkey + K * np, out_B}};
     for (const auto& j : jobs) {
@@ -790,6 +792,49 @@ int32_t link_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, 
     return publish_batch(std::move(b), "link", [](uint32_t, uint32_t field) { return std::string(LINK_FIELDS[field & 3]); }, out_eta, 0, 32, out_batch, out_bad);
 }
 
+// ---- KZG openings (univariate_kzg/mod.rs:195-271; verifier.cuh "KZG openings") ----------------------------------------------------------------
+const char* const OPEN_FIELDS[4] = {"commitment", "proof", "point", "value"};
+const char* kind_name(BatchKind k) { return k == BatchKind::Links ? "a link batch" : k == BatchKind::Openings ? "an openings batch" : "a proof batch"; }
+
+int32_t open_begin(const std::shared_ptr<Verifier>& vp, const uint8_t* records, uint64_t K, const uint64_t* points, const uint64_t* values, uint32_t flags,
+                   uint64_t* out_batch, uint64_t* out_bad) {
+    const Verifier& v = *vp;
+    const int curve = v.curve;
+    if (out_bad) *out_bad = ~0ull;
+    const uint32_t G = v.sh.g1_bytes, np = 2, nkey = 1, fqw = fq_words(curve);
+    const size_t pt_bytes = (size_t)2 * fqw * 4;
+    auto b = std::make_shared<Batch>();                               // (a failure below frees it here, under the caller's guard)
+    b->v = vp, b->kind = BatchKind::Openings, b->K = K, b->np = np, b->nkey = nkey;
+    MZK_TRY(stage_batch(*b, records, 2 * G, 1, 1));                   // chal: z_i in Montgomery form
+    MZK_TRY(b->pub.alloc(K * 64));                                    // the K points, then the K values, as they came
+    HIP_TRY(hipMemcpy(b->pub.p, points, K * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->pub.as<uint8_t>() + K * 32, values, K * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->bases.p, v.key_xy.as<uint8_t>() + (size_t)v.g_index() * pt_bytes, pt_bytes, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(b->inf.p, v.key_inf.as<uint32_t>() + v.g_index(), 4, hipMemcpyDeviceToDevice));
+    unsigned long long* err = b->err.as<unsigned long long>();
+    // A: no opening columns; the opening proofs (column 1) are then gathered as the bases of the MSM A
+    uint8_t* own_bases = b->bases.as<uint8_t>() + (size_t)nkey * pt_bytes;
+    decode_points(curve, v.sh.compressed, flags & MZK_SER_VALIDATE, b->images.as<uint8_t>(), K, 2 * G, v.open_cols.as<uint32_t>(), np, np, reinterpret_cast<uint32_t*>(own_bases),
+                  b->inf.as<uint32_t>() + nkey, nullptr, nullptr, err);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy2DAsync(b->a_bases.p, pt_bytes, own_bases + pt_bytes, 2 * pt_bytes, pt_bytes, K, hipMemcpyDeviceToDevice, nullptr));
+    // Co
+    {
+        ProfScope ps("vfy_open_rows", nullptr, v.device);
+        uint32_t* proof_rows = b->b_scal.as<uint32_t>() + (size_t)nkey * 8;
+        const uint32_t *pts = b->pub.as<uint32_t>(), *vals = pts + K * 8;
+        const dim3 grid((unsigned)((K + VFY_THREADS - 1) / VFY_THREADS)), block(VFY_THREADS);
+        if (curve == MZK_CURVE_BLS12_381)
+            hipLaunchKernelGGL((vfy_open_rows_kernel<BlsFr>), grid, block, 0, nullptr, (unsigned long long)K, pts, vals, b->inf.as<uint32_t>() + nkey, b->a_inf.as<uint32_t>(),
+                               b->chal.as<uint32_t>(), b->key_rows.as<uint32_t>(), proof_rows, b->evals.as<uint32_t>(), err);
+        else
+            hipLaunchKernelGGL((vfy_open_rows_kernel<BnFr>), grid, block, 0, nullptr, (unsigned long long)K, pts, vals, b->inf.as<uint32_t>() + nkey, b->a_inf.as<uint32_t>(),
+                               b->chal.as<uint32_t>(), b->key_rows.as<uint32_t>(), proof_rows, b->evals.as<uint32_t>(), err);
+        HIP_TRY(hipGetLastError());
+    }
+    return publish_batch(std::move(b), "opening", [](uint32_t, uint32_t field) { return std::string(OPEN_FIELDS[field & 3]); }, nullptr, 0, 32, out_batch, out_bad);
+}
+
 // 64 challenge bytes mod r, Montgomery: vfy_reduce_challenge on the host (lo + 2^256 hi, each half below r by subtraction: 2^256 < 6 r)
 template <class FrP>
 Fp64<FrP> reduce_challenge_host(const uint8_t* ch) {
@@ -941,6 +986,7 @@ extern "C" int32_t mzk_verifier_batch_challenges(uint64_t batch, uint64_t* out) 
     ON_DEVICE_OF(batch, b, find_batch);
     if (!out) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     if (b->kind == BatchKind::Links) { set_error("a link batch has no challenges: mzk_verifier_link_values"); return MZK_ERR_INVALID_ARG; }
+    if (b->kind == BatchKind::Openings) { set_error("an openings batch has no challenges"); return MZK_ERR_INVALID_ARG; }
     return hip_status(hipMemcpy(out, b->chal.p, b->K * 7 * 32, hipMemcpyDeviceToHost), "hipMemcpy of the challenges");
 }
 
@@ -1003,7 +1049,7 @@ extern "C" int32_t mzk_verifier_link_begin(uint64_t verifier, const uint8_t* rec
 
 extern "C" int32_t mzk_verifier_link_values(uint64_t batch, uint64_t* out_eta_mont, uint64_t* out_vanishing_mont) {
     ON_DEVICE_OF(batch, b, find_batch);
-    if (b->kind != BatchKind::Links) { set_error("not a link batch"); return MZK_ERR_INVALID_ARG; }
+    if (b->kind != BatchKind::Links) { set_error(std::string("not a link batch: ") + kind_name(b->kind)); return MZK_ERR_INVALID_ARG; }
     if (out_eta_mont) HIP_TRY(hipMemcpy(out_eta_mont, b->chal.p, b->K * 32, hipMemcpyDeviceToHost));
     if (out_vanishing_mont) HIP_TRY(hipMemcpy(out_vanishing_mont, b->vanish.p, b->K * 32, hipMemcpyDeviceToHost));
     return MZK_OK;
@@ -1011,11 +1057,18 @@ extern "C" int32_t mzk_verifier_link_values(uint64_t batch, uint64_t* out_eta_mo
 
 extern "C" int32_t mzk_verifier_link_weights(uint64_t batch, const uint64_t* r_mont, uint64_t* out_weights_mont) {
     ON_DEVICE_OF(batch, b, find_batch);
-    if (b->kind != BatchKind::Links) { set_error("not a link batch"); return MZK_ERR_INVALID_ARG; }
+    if (b->kind != BatchKind::Links) { set_error(std::string("not a link batch: ") + kind_name(b->kind)); return MZK_ERR_INVALID_ARG; }
     if (!out_weights_mont) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
     std::vector<uint64_t> eta(b->K * 4);
     HIP_TRY(hipMemcpy(eta.data(), b->chal.p, b->K * 32, hipMemcpyDeviceToHost));
     if (b->v->curve == MZK_CURVE_BLS12_381) link_weights_t<BlsFr>(r_mont, eta.data(), b->open_recs, b->K, out_weights_mont);
     else link_weights_t<BnFr>(r_mont, eta.data(), b->open_recs, b->K, out_weights_mont);
     return MZK_OK;
+}
+
+extern "C" int32_t mzk_verifier_open_begin(uint64_t verifier, const uint8_t* records, uint64_t K, const uint64_t* points_canonical, const uint64_t* values_canonical,
+                                           uint32_t flags, uint64_t* out_batch, uint64_t* out_bad_index) {
+    ON_DEVICE_OF(verifier, v, find_verifier);
+    if (!records || !K || K >= (1ull << 24) || !points_canonical || !values_canonical || !out_batch || (flags & ~MZK_SER_VALIDATE)) { set_error("bad argument"); return MZK_ERR_INVALID_ARG; }
+    return open_begin(v, records, K, points_canonical, values_canonical, flags, out_batch, out_bad_index);
 }

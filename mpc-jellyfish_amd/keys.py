@@ -121,6 +121,9 @@ class OpenKey:
     def begin_links(self, links, eta=None, validate: bool = True, transcript: str = "merlin") -> "VerifierBatch":
         return self.verifier().begin_links(links, eta, validate, transcript)
 
+    def begin_openings(self, commitments, points, values, proofs, validate: bool = True) -> "VerifierBatch":
+        return self.verifier().begin_openings(commitments, points, values, proofs, validate)
+
     def check(self, A_xyz, B_xyz) -> bool:
         return self.verifier().check(A_xyz, B_xyz)
 
@@ -146,6 +149,7 @@ class ProofEncodingError(SerializationError):
 _PROOF_MSG = re.compile(r"^proof (\d+): ([^:]+): ")
 _BATCH_PROOF_MSG = re.compile(r"^(?:proof (\d+): )?instance (\d+): ([^:]+): ")
 _LINK_MSG = re.compile(r"^link (\d+): ([^:]+): ")
+_OPENING_MSG = re.compile(r"^opening (\d+): ([^:]+): ")
 
 
 def _begin_arrays(proofs, flat_inputs, extra_msgs, challenges):
@@ -251,6 +255,40 @@ class Verifier:
             raise ProofEncodingError(msg, bad.value, m.group(2) if m else None)
         _lib.check(rc, "mzk_verifier_link_begin")
         return VerifierBatch(self, batch.value, K, out, shape=(1, 4))
+
+    def begin_openings(self, commitments, points, values, proofs, validate: bool = True) -> "VerifierBatch":
+        """mzk_verifier_open_begin: K KZG openings (univariate_kzg/mod.rs:195-271) as one batch.  commitments, proofs: kzg.Commitment objects
+        (written as records of this verifier's mode) or G1 records, staged as they are; points, values: canonical integers, staged as they are
+        -- the device range-checks them against r.  Returns a VerifierBatch whose rows are (1, z_i) over the two records, whose evaluations
+        are the v_i and whose .u holds nothing; finish(weights) -> (A, B).  Raises ProofEncodingError naming the lowest bad opening (.index)
+        and its field (commitment | proof | point | value)."""
+        L = _lib.load()
+        K = len(commitments)
+        if K == 0 or len(points) != K or len(values) != K or len(proofs) != K:
+            raise ValueError("the number of commitments / points / values / proofs differ, or no opening")
+        G = kzg.g1_record_bytes(self.curve, self.vk.compressed)
+        rec = lambda x: kzg.g1_record(self.curve, x, self.vk.compressed) if isinstance(x, kzg.Commitment) else bytes(x)
+        pairs = [(rec(cm), rec(pf)) for cm, pf in zip(commitments, proofs)]
+        for i, pair in enumerate(pairs):
+            for name, r in zip(("commitment", "proof"), pair):
+                if len(r) != G:
+                    raise ProofEncodingError(f"opening {i}: {name}: {len(r)} bytes, expected {G} on this curve and in this mode", i, name)
+        for name, xs in (("point", points), ("value", values)):
+            for i, x in enumerate(xs):
+                if not 0 <= int(x) < 1 << 256:
+                    raise ProofEncodingError(f"opening {i}: {name}: not below the modulus", i, name)
+        records = np.frombuffer(b"".join(cm + pf for cm, pf in pairs), dtype=np.uint8)
+        limbs = lambda xs: np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in xs), dtype=np.uint64)
+        z, v = limbs(points), limbs(values)
+        batch, bad = C.c_uint64(), C.c_uint64()
+        rc = L.mzk_verifier_open_begin(self.handle, C.c_void_p(records.ctypes.data), K, C.c_void_p(z.ctypes.data), C.c_void_p(v.ctypes.data),
+                                       _SER_VALIDATE if validate else 0, C.byref(batch), C.byref(bad))
+        if rc == _ERR_ENCODING:
+            msg = L.mzk_last_error().decode()
+            m = _OPENING_MSG.match(msg)
+            raise ProofEncodingError(msg, bad.value, m.group(2) if m else None)
+        _lib.check(rc, "mzk_verifier_open_begin")
+        return VerifierBatch(self, batch.value, K, np.zeros((K, 4), dtype=np.uint64), shape=(1, 2))
 
     def check(self, A_xyz, B_xyz) -> bool:
         """mzk_verifier_check over the (A, B) of one or more groups with this key's open key: e(sum A, beta_h) e(-sum B, h) == 1."""

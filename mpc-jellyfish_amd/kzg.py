@@ -1,10 +1,13 @@
-"""UnivariateKzgPCS -- mirror of primitives/src/pcs/univariate_kzg/{mod,srs}.rs for the commit path:
+"""UnivariateKzgPCS -- mirror of primitives/src/pcs/univariate_kzg/{mod,srs}.rs: commit, open and verify, single and batched:
 
     UnivariateProverParam{powers_of_g}      srs.rs:36-40   -> an SRS resident in HBM (handle)
     gen_srs_for_testing                     srs.rs:118-153 -> UnivariateProverParam.gen_srs_for_testing
     trim                                    srs.rs:77-93   -> UnivariateProverParam.trim
     commit / batch_commit                   mod.rs:90-131  -> UnivariateKzgPCS.commit / batch_commit
     <G1 as VariableBaseMSM>::msm_bigint     mod.rs:109-111 -> msm_bigint
+    open / batch_open                       mod.rs:135-190 -> UnivariateKzgPCS.open / batch_open (one pass: mzk_kzg_open_batch_dev)
+    verify / batch_verify                   mod.rs:195-271 -> UnivariateKzgPCS.verify / batch_verify (keys.OpenKey.begin_openings)
+    UnivariateVerifierParam, trim's 2nd half srs.rs:48-55, 77-93 -> keys.OpenKey, UnivariateUniversalParams.verifier_param
     CanonicalSerialize / Deserialize        srs.rs:18-40   -> UnivariateProverParam.serialize / deserialize,
                                                               UnivariateUniversalParams (points decoded on the GPU)
 
@@ -19,7 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _lib
-from .params import CurveParams, curve as _curve, fq_to_mont, int_to_limbs
+from .params import CurveParams, curve as _curve, fq_from_mont, fq_to_mont, fr_from_mont, fr_to_mont, int_to_limbs
 
 
 class PCSError(Exception):
@@ -42,6 +45,27 @@ _ERR_ENCODING = -11
 def g1_record_bytes(curve, compress: bool = True) -> int:
     """Bytes of one G1 point in ark-serialize 0.4: 48 / 96 on BLS12-381, 32 / 64 on BN254 (compressed / uncompressed)."""
     return (48 if _curve(curve).curve_id == 0 else 32) * (1 if compress else 2)
+
+
+def g1_record(curve, commitment, compress: bool = True) -> bytes:
+    """A Commitment as the G1 record ark-serialize writes (transcript.g1_bytes for the compressed form; uncompressed: x || y, BLS12-381
+    big-endian, BN254 little-endian with y's sign flag in the last byte; infinity: the flag byte alone)."""
+    from . import transcript as _transcript
+    c = _curve(curve)
+    pt = None if commitment.is_infinity() else tuple(fq_from_mont(c, commitment.xy))
+    if compress:
+        return _transcript.g1_bytes(c, pt)
+    n = g1_record_bytes(c)
+    if pt is None:
+        rec = bytearray(2 * n)
+        rec[0 if c.curve_id == 0 else -1] |= 0x40
+        return bytes(rec)
+    x, y = pt
+    if c.curve_id == 0:
+        return x.to_bytes(n, "big") + y.to_bytes(n, "big")
+    rec = bytearray(x.to_bytes(n, "little") + y.to_bytes(n, "little"))
+    rec[-1] |= 0x80 if y > c.q - y else 0
+    return bytes(rec)
 
 
 def g2_record_bytes(curve, compress: bool = True) -> int:
@@ -245,6 +269,13 @@ class UnivariateUniversalParams:
     def serialize(self) -> bytes:
         return self.powers_of_g.serialize(self.compressed) + self.h + self.beta_h
 
+    def verifier_param(self):
+        """The second half of `trim` (srs.rs:77-93): UnivariateVerifierParam { g: powers_of_g[0], h, beta_h } as a keys.OpenKey of this
+        container's mode -- what UnivariateKzgPCS.verify / batch_verify take."""
+        from . import keys as _keys
+        g = g1_record(self.powers_of_g.curve, Commitment(self.powers_of_g.curve, self.powers_of_g.powers_of_g(0, 1)[0]), self.compressed)
+        return _keys.OpenKey(self.powers_of_g.curve, g, self.h, self.beta_h, self.compressed)
+
     def release(self):
         self.powers_of_g.release()
 
@@ -353,11 +384,83 @@ class UnivariateKzgPCS:
 
     @staticmethod
     def batch_open(prover_param: UnivariateProverParam, polynomials, points):
-        """mod.rs:163-190 ("a naive approach"): open every polynomial at its own point."""
+        """mod.rs:163-190 ("a naive approach" there: a loop over open): every polynomial opened at its own point in ONE pass of the device
+        (mzk_kzg_open_batch_dev) -- the K witness polynomials and evaluations from one kernel family, the K commitments from one fused batch
+        MSM, which waits once per group of six and not twice per polynomial.  polynomials: (len, 4) Montgomery coefficient arrays (numpy or CUDA tensors, ragged); host arrays are staged in one
+        upload.  Returns ([Commitment proofs], [evaluation ints]) as the loop over open did."""
         if len(polynomials) != len(points):
             raise PCSError("InvalidParameters: poly length %d is different from points length %d" % (len(polynomials), len(points)))
-        out = [UnivariateKzgPCS.open(prover_param, p, z) for p, z in zip(polynomials, points)]
-        return [o[0] for o in out], [o[1] for o in out]
+        pp = prover_param
+        K = len(polynomials)
+        if K == 0:
+            return [], []
+        import torch
+        polys, one_by_one = [], bool(pp.offset)                            # (a view that does not start at its registration's first point: the loop)
+        for p in polynomials:
+            if _is_torch(p) and p.shape[0] - 1 <= pp.length:
+                polys.append(p)
+                continue
+            a = p.cpu().numpy().view(np.uint64) if _is_torch(p) else np.ascontiguousarray(p, dtype=np.uint64)
+            a = a.reshape(-1, 4)
+            if a.shape[0] - 1 > pp.length:                                 # the witness array is longer than the key: its true degree decides (mod.rs:98)
+                degree, _ = _degree_and_leading_zeros(a)
+                if degree - 1 > pp.length:
+                    raise PCSError(f"InvalidParameters: poly degree {degree - 1} is larger than allowed {pp.length}")
+                one_by_one |= degree - 1 == pp.length                      # passes the reference's guard, then ark-ec truncates: commit's own edge
+                a = a[:degree + 1]
+            polys.append(a)
+        if one_by_one:
+            out = [UnivariateKzgPCS.open(pp, p, z) for p, z in zip(polynomials, points)]
+            return [o[0] for o in out], [o[1] for o in out]
+        host = [i for i, p in enumerate(polys) if not _is_torch(p)]
+        if host:                                                           # one slab, one upload
+            slab = torch.from_numpy(np.concatenate([polys[i] for i in host]).view(np.int64)).cuda()
+            at = 0
+            for i in host:
+                n = polys[i].shape[0]
+                polys[i] = slab[at:at + n]
+                at += n
+        polys = [p.contiguous() for p in polys]
+        for p in polys:
+            if p.dtype != torch.int64 or not p.is_cuda or p.dim() != 2 or p.shape[1] != 4:
+                raise ValueError("expected (len, 4) int64 CUDA tensors or uint64 host arrays")
+        c = pp.curve
+        ptrs = (C.c_void_p * K)(*[p.data_ptr() if p.shape[0] else None for p in polys])
+        lens = (C.c_uint64 * K)(*[p.shape[0] for p in polys])
+        z = fr_to_mont(c, [int(x) % c.r for x in points])
+        proofs, evals = np.zeros((K, 2, c.fq_limbs), dtype=np.uint64), np.zeros((K, 4), dtype=np.uint64)
+        st = torch.cuda.current_stream(polys[0].device).cuda_stream
+        _lib.check(_lib.ensure_init().mzk_kzg_open_batch_dev(pp.handle, K, ptrs, lens, C.c_void_p(z.ctypes.data), C.c_void_p(proofs.ctypes.data),
+                                                             C.c_void_p(evals.ctypes.data), C.c_void_p(st)), "mzk_kzg_open_batch_dev")
+        return [Commitment(c, proofs[i]) for i in range(K)], fr_from_mont(c, evals)
+
+    @staticmethod
+    def verify(verifier_param, commitment, point: int, value: int, proof) -> bool:
+        """mod.rs:195-216: e(C - [v]g + [z]pi, h) == e(pi, beta_h).  verifier_param: a keys.OpenKey (UnivariateVerifierParam; jf-plonk's
+        OpenKey); commitment, proof: Commitment objects or G1 records of the key's mode.  A batch of one with weight 1, on the device
+        (keys.OpenKey.begin_openings); a malformed record or scalar raises the SerializationError family."""
+        c = verifier_param.curve
+        b = verifier_param.begin_openings([commitment], [point], [value], [proof])
+        return verifier_param.check(*b.finish(fr_to_mont(c, [1])))
+
+    @staticmethod
+    def batch_verify(verifier_param, commitments, points, values, proofs, rng) -> bool:
+        """mod.rs:223-271: the K openings under random weights in one check of two pairings.  Weights as the reference draws them: 1, then
+        per further opening u128::rand(rng) -- rng.next_u64() for the low half, then for the high half (rng: an rng.ChaChaRng) -- so a
+        seeded caller gets the reference's randomizers.  Length mismatches raise PCSError; an empty batch is accepted (two pairings of O)."""
+        K = len(commitments)
+        for name, n in (("points", len(points)), ("values", len(values)), ("proofs", len(proofs))):
+            if n != K:
+                raise PCSError("InvalidParameters: commitments length %d is different from %s length %d" % (K, name, n))
+        if K == 0:
+            return True
+        c = verifier_param.curve
+        weights = [1]
+        for _ in range(K - 1):
+            lo = rng.next_u64()
+            weights.append(lo | rng.next_u64() << 64)
+        b = verifier_param.begin_openings(commitments, points, values, proofs)
+        return verifier_param.check(*b.finish(fr_to_mont(c, weights)))
 
 
 def jacobian_to_affine(curve, xyz: np.ndarray) -> np.ndarray:
