@@ -704,6 +704,26 @@ MZK_API int32_t mzk_poly_div_roots_dev(int32_t curve_id, const void* d_poly, uin
  * lens[i] - 1 above the SRS: MZK_ERR_INVALID_ARG, the degree guard of mzk_msm.  Synchronises the stream. */
 MZK_API int32_t mzk_kzg_open_batch_dev(uint64_t srs_handle, uint32_t K, const void* const* d_polys, const uint64_t* lens, const uint64_t* points_mont,
                                        uint64_t* out_proofs_xy_mont, uint64_t* out_evals_mont, void* stream);
+/* UnivariatePCS::multi_open_rou / _proofs / _evals (univariate_kzg/mod.rs:298-377, pcs/mod.rs:281-306): ONE polynomial resident on the device
+ * (d_poly: len Montgomery Fr coefficients, low order first) opened at the first num_points points w^0, w^1, .. of the radix-2 domain of
+ * N = 2^log_domain points -> out_proofs_xy_mont (host, affine points x || y, Montgomery, (0, 0) = infinity) and out_evals_mont (host, 4 limbs
+ * each, p(w^i)).  num_points above N is clamped to N (the reference's `take`).  Either output may be NULL: without proofs the call is one
+ * scalar NTT and touches no SRS point; without evaluations it is the proofs alone.
+ * The proofs come from FK23 as the reference's compute_h_poly_in_fk23 and ToeplitzMatrix::fast_vec_mul have it, in O(d log d) group
+ * operations: d = next_power_of_two(max(len, 1) - 1) with next_power_of_two(0) = 1, the coefficients padded to d + 1;
+ * the points S_k = point srs_offset + k of the SRS, k < d, as the vector [S_(d-1), .., S_0, O^d], whose group NTT of size 2d is kept on the SRS
+ * handle for the last (srs_offset, d) asked for -- built on the first call, counted as table bytes by mzk_srs_hbm_bytes, freed by
+ * mzk_srs_release --; then a scalar NTT of the circulant column [f_d, 0^(d-1), f_d, f_1, .., f_(d-1)], 2d scalar multiplications, the inverse
+ * group NTT, whose first d outputs are the coefficients h of the proof polynomial, and the group NTT of h over the N points.  Nothing is affine
+ * between the steps.  d follows len AS GIVEN: trailing zero coefficients are not trimmed -- the proofs are the same points either way, only
+ * the number of SRS points the call asks for differs.  len = 0 and len = 1: every proof O; evaluations 0 and c_0.
+ * Refused before any launch -- MZK_ERR_INVALID_ARG: fewer than d points from srs_offset on; d > N when proofs are asked for; len > N when
+ * evaluations are asked for (the reference: "can't be evaluated on a smaller domain").  MZK_ERR_UNSUPPORTED: log2(2d) (proofs) or log_domain
+ * above the two-adicity of Fr, or above 21.  The cap follows the scratch, which comes from the shared workspace and is handed back when
+ * the call had to grow it: 2d + N + 8 max(2d, N / 2) XYZZ points (224 B on BLS12-381, 144 B on BN254) for the two arrays and the window tables of
+ * the scalar multiplications -- 4.7 GB at 2d = N = 2^21 on BLS12-381, beside the 0.47 GB the handle keeps.  Synchronises the stream. */
+MZK_API int32_t mzk_kzg_multi_open_rou_dev(uint64_t srs_handle, uint64_t srs_offset, const void* d_poly, uint64_t len, uint32_t log_domain,
+                                           uint64_t num_points, uint64_t* out_proofs_xy_mont, uint64_t* out_evals_mont, void* stream);
 
 /* ---- the prover's rounds on device-resident state: replaces the BODIES of Prover::run_1st_round .. compute_opening_proofs
  *      (plonk/src/proof_system/prover.rs:72-419) as PlonkKzgSnark::batch_prove_internal calls them (snark.rs:263-431).
@@ -1019,7 +1039,8 @@ MZK_API int32_t mzk_msm_set_precompute(int32_t on);
 MZK_API int32_t mzk_srs_precompute(uint64_t srs_handle, uint32_t* out_window_bits, uint32_t* out_levels, uint64_t* out_table_bytes,
                                    double* out_build_ms);
 /* HBM accounting (bench.py reports it per leg).  An SRS: its points (boundary form + the MSM's internal form: 96 + 112 B per point on
- * BLS12-381, 64 + 72 B on BN254) and its fixed-base table (0 until built; the reference keeps the points only: srs.rs:36-40).  A proving
+ * BLS12-381, 64 + 72 B on BN254) and its tables: the fixed-base table and the transformed SRS vector of mzk_kzg_multi_open_rou_dev (0 until
+ * built; the reference keeps the points only: srs.rs:36-40).  A proving
  * key: the resident evaluations of the fixed polynomials and the per-point tables.  The device context: the shared scratch of the NTT /
  * MSM / quotient kernels (grow-only) and the buffers of the host-pointer I/O slots. */
 MZK_API int32_t mzk_srs_hbm_bytes(uint64_t srs_handle, uint64_t* out_points_bytes, uint64_t* out_table_bytes);

@@ -25,14 +25,17 @@
 //! exposes, Montgomery limbs) and proved by the reference.  The GPU tests feed that very file to `mzk_prove <curve> file`, to the
 //! round-level C ABI and to the Python mirror, the CPU tests to the schoolbook oracle: every host must emit the reference's bytes.
 //!
+//! `multi_open_cases.json` -> `ref_multi_open.json`: `UnivariatePCS::multi_open_rou` (FK23) of one polynomial over the domain that
+//! `multi_open_rou_eval_domain` picks, SRS rebuilt from (beta, G); `tests/test_kzg_multi_open_ref_gpu.py` holds the device to it.
+//!
 //! NOT COMPILED in this repository's build image (no Rust toolchain); see README.md.
 use ark_ec::{pairing::Pairing, AffineRepr, CurveGroup, VariableBaseMSM};
 use ark_ff::{BigInt, BigInteger, PrimeField, UniformRand, Zero};
-use ark_poly::{univariate::DensePolynomial, DenseUVPolynomial, EvaluationDomain, Radix2EvaluationDomain};
+use ark_poly::{univariate::DensePolynomial, DenseUVPolynomial, EvaluationDomain, Polynomial, Radix2EvaluationDomain};
 use ark_serialize::CanonicalSerialize;
 use jf_primitives::pcs::{
     prelude::{UnivariateKzgPCS, UnivariateProverParam, UnivariateUniversalParams},
-    PolynomialCommitmentScheme,
+    PolynomialCommitmentScheme, UnivariatePCS,
 };
 use mpc_plonk::{
     proof_system::{structs::ProvingKey, PlonkKzgSnark, UniversalSNARK},
@@ -129,6 +132,28 @@ macro_rules! curve_fixtures {
                 let com = UnivariateKzgPCS::<E>::commit(&pp, &poly).unwrap();
                 let mut out = case.clone();
                 out["commitment"] = point_json(&com.0);
+                out
+            }
+
+            /// `UnivariatePCS::{multi_open_rou_eval_domain, multi_open_rou}` (FK23) over powers_of_g[i] = beta^i G, G the standard generator
+            pub fn multi_open(case: &Value) -> Value {
+                let beta: Fr = fe(case["beta"].as_str().unwrap());
+                let coeffs: Vec<Fr> = strs(&case["coeffs"]).into_iter().map(fe::<Fr>).collect();
+                let num_points = case["num_points"].as_u64().unwrap() as usize;
+                let mut powers_of_g = Vec::with_capacity(coeffs.len() + 1);
+                let mut cur = G1::from(G1Affine::generator());
+                for _ in 0..=coeffs.len() {
+                    powers_of_g.push(cur.into_affine());
+                    cur *= beta;
+                }
+                let pp = UnivariateProverParam::<E> { powers_of_g };
+                let poly = DensePolynomial::from_coefficients_vec(coeffs);
+                let domain = UnivariateKzgPCS::<E>::multi_open_rou_eval_domain(poly.degree(), num_points).unwrap();
+                let (proofs, evals) = UnivariateKzgPCS::<E>::multi_open_rou(&pp, &poly, num_points, &domain).unwrap();
+                let mut out = case.clone();
+                out["domain_size"] = json!(domain.size());
+                out["proofs"] = json!(proofs.iter().map(|p| point_json(&p.proof)).collect::<Vec<_>>());
+                out["evals"] = json!(evals.iter().map(hx).collect::<Vec<_>>());
                 out
             }
 
@@ -420,5 +445,6 @@ fn main() {
     run(dir, "batch_vectors", bls::batch, bn::batch);
     run(dir, "link_vectors", bls::link, bn::link);
     run_to(dir, "general_ref_cases", "ref_general_circuits", bls::general, bn::general);
+    run_to(dir, "multi_open_cases", "ref_multi_open", bls::multi_open, bn::multi_open);
     let _ = BigInt::<4>::zero().is_zero();
 }

@@ -238,4 +238,71 @@ MZK_HD XYZZ<Fp<X>> xyzzx_to_boundary(const XYZZX<X>& p) {
     return r;
 }
 
+#if defined(__HIPCC__)
+// The EC back end on this arithmetic (the policy the bucket kernels of msm.cuh and the group NTT of ec_ntt.cuh are written against):
+// points in the reduced-radix form, the SRS converted once at registration and results converted back when they are collected.
+template <class X>
+struct EcFx {
+    using Field = X;
+    using Aff = AffineX<X>;
+    using Pt = XYZZX<X>;
+    using Fe = Fx<X>;
+    static constexpr int LIMBS = X::XN, SLOT_WORDS = X::XN;                // limbs of a coordinate / words between coordinates in memory
+    static constexpr int AFF_WORDS = 2 * X::XN, PT_WORDS = 4 * X::XN;      // BN254: 18 / 36 words
+    static_assert((4 * X::XN) % 4 == 0 && (2 * X::XN) % 2 == 0, "points are whole 16-byte / 8-byte words");
+    static __device__ __forceinline__ Aff load_aff(const uint32_t* __restrict__ bases, unsigned long long idx) {
+        uint32_t w[AFF_WORDS];
+        if constexpr (AFF_WORDS % 4 == 0) {
+            const uint4* src = reinterpret_cast<const uint4*>(bases + idx * AFF_WORDS);
+#pragma unroll
+            for (int i = 0; i < AFF_WORDS / 4; i++) {
+                const uint4 v = src[i];
+                w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+            }
+        } else {                                                           // 18 words (BN254 on 9 limbs): 72-byte points, 8-byte aligned
+            const uint2* src = reinterpret_cast<const uint2*>(bases + idx * AFF_WORDS);
+#pragma unroll
+            for (int i = 0; i < AFF_WORDS / 2; i++) {
+                const uint2 v = src[i];
+                w[2 * i] = v.x; w[2 * i + 1] = v.y;
+            }
+        }
+        Aff p;
+#pragma unroll
+        for (int i = 0; i < X::XN; i++) { p.x.l[i] = w[i]; p.y.l[i] = w[X::XN + i]; }
+        return p;
+    }
+    static __device__ __forceinline__ Pt load_pt(const uint32_t* __restrict__ buf, unsigned long long idx) {
+        uint32_t w[PT_WORDS];
+        const uint4* src = reinterpret_cast<const uint4*>(buf + idx * PT_WORDS);
+#pragma unroll
+        for (int i = 0; i < PT_WORDS / 4; i++) {
+            const uint4 v = src[i];
+            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+        Pt p;
+#pragma unroll
+        for (int i = 0; i < X::XN; i++) {
+            p.x.l[i] = w[i]; p.y.l[i] = w[X::XN + i]; p.zz.l[i] = w[2 * X::XN + i]; p.zzz.l[i] = w[3 * X::XN + i];
+        }
+        return p;
+    }
+    static __device__ __forceinline__ void store_pt(uint32_t* __restrict__ buf, unsigned long long idx, const Pt& p) {
+        uint32_t w[PT_WORDS];
+#pragma unroll
+        for (int i = 0; i < X::XN; i++) {
+            w[i] = p.x.l[i]; w[X::XN + i] = p.y.l[i]; w[2 * X::XN + i] = p.zz.l[i]; w[3 * X::XN + i] = p.zzz.l[i];
+        }
+        uint4* dst = reinterpret_cast<uint4*>(buf + idx * PT_WORDS);
+#pragma unroll
+        for (int i = 0; i < PT_WORDS / 4; i++) dst[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    }
+    static __device__ __forceinline__ Pt inf() { return Pt::inf(); }
+    static __device__ __forceinline__ Pt madd(const Pt& a, const Aff& q, bool negate) { return xyzzx_madd(a, q, negate); }
+    static __device__ __forceinline__ Pt add(const Pt& a, const Pt& b) { return xyzzx_add(a, b); }
+    static __device__ __forceinline__ XYZZ<Fp<X>> to_boundary(const Pt& p) { return xyzzx_to_boundary(p); }
+    static __device__ __forceinline__ Fe add_quad(const Fe& ca, const Fe& cb, int role) { return xyzzx_add_quad<X>(ca, cb, role); }
+};
+#endif
+
 }  // namespace mzk

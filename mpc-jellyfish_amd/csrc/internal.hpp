@@ -112,12 +112,15 @@ struct Srs {
     int pre_c = 0;              // window bits of d_pre; -1 = do not build
     int pre_levels = 0;         // W: levels of d_pre
     double pre_build_ms = 0;    // wall time of the build (pre_next_level launches, synchronised)
-    void free();                // releases the three tables (errors ignored) and nulls them; called explicitly, never from a destructor
+    uint32_t* d_fk = nullptr;   // FK23 (kzg_multi.hip): the group NTT of [S_(fk_off + fk_d - 1) .. S_(fk_off), O^fk_d], 2 fk_d XYZZ points (EcFx form,
+    uint64_t fk_off = 0, fk_d = 0;   // bit-reversed order) of the last (offset, d) a multi-opening asked for; built on first use
+    void free();                // releases the tables (errors ignored) and nulls them; called explicitly, never from a destructor
 };
 inline bool valid_curve(int curve) { return curve == MZK_CURVE_BLS12_381 || curve == MZK_CURVE_BN254; }
 inline int fq_words(int curve) { return curve == MZK_CURVE_BLS12_381 ? 12 : 8; }
 inline size_t srs_point_bytes(int curve) { return (size_t)2 * fq_words(curve) * 4; }                            // boundary form (d_xy)
 constexpr size_t srs_int_point_bytes(int curve) { return curve == MZK_CURVE_BLS12_381 ? 2 * 14 * 4 : 2 * 9 * 4; }  // internal form (d_int, d_pre): pinned to EcFz / EcFx::AFF_WORDS in msm.hip
+constexpr size_t ec_ntt_point_bytes(int curve) { return curve == MZK_CURVE_BLS12_381 ? 4 * 14 * 4 : 4 * 9 * 4; }   // an XYZZ point of the group NTT (d_fk): pinned to EcFx::PT_WORDS in msm.hip
 
 // ---- device contexts ---------------------------------------------------------------------------------
 // One context per LOGICAL device: the HIP device it runs on, its lock, workspace, I/O slots, SRS registry; the NTT plan cache,
@@ -212,6 +215,10 @@ int32_t srs_build_internal(Srs& s, hipStream_t st);
 int32_t srs_build_pre(Srs& s, hipStream_t st);
 int32_t srs_generate_dispatch(int curve, const uint32_t* beta_canon, const uint32_t* g_xy_mont /* NULL: the standard generator */, uint64_t n, uint32_t* d_out);
 int32_t srs_lagrange_from_points_dispatch(int curve, const uint32_t* d_xy, int log_n, uint32_t n_extra, uint32_t* d_out);
+// the group NTT (ec_ntt.cuh) of the 2^log_n XYZZ points at d_a (EcFx form), in place and asynchronous on st: natural order in, bit-reversed
+// out; inverse: the root is w^-1; scaled: times 2^-log_n; d_tab: 8 points of scratch per butterfly (4 * 2^log_n, 8 at least).  d_out_xy
+// (nullable): the finishing pass -- the first n_out elements in natural order as affine points in the boundary form, (0, 0) = infinity
+int32_t ec_ntt_dispatch(int curve, uint32_t* d_a, int log_n, bool inverse, bool scaled, uint32_t* d_tab, uint32_t* d_out_xy, uint64_t n_out, hipStream_t st);
 int32_t srs_lagrange_generate_dispatch(int curve, const uint32_t* beta_canon, const uint32_t* g_xy_mont /* nullable */, int log_n, uint32_t n_extra, uint32_t* d_out);
 void jac_to_affine_host_dispatch(int curve, const uint64_t* xyz, uint64_t n, uint64_t* xy);
 void jac_sum_host_dispatch(int curve, const uint64_t* xyz, uint64_t n, uint64_t* out);
@@ -242,6 +249,10 @@ int32_t kzg_open_batch_dispatch(const Srs& s, uint32_t K, const uint32_t* const*
                                 uint32_t* out_evals, hipStream_t st);
 int32_t poly_div_roots_dispatch(int curve, const uint32_t* d_poly, uint64_t len, uint32_t log_order, uint64_t first, uint64_t count, uint32_t* d_out,
                                 hipStream_t st);
+// kzg_multi.hip: mzk_kzg_multi_open_rou_dev behind its argument checks (either output nullable); waits for the stream
+constexpr int KZG_MULTI_MAX_LOG = 21;       // cap on log2(2d) and log_domain (include/mzk.h: the workspace formula)
+int32_t kzg_multi_open_dispatch(Srs& s, uint64_t srs_offset, const uint32_t* d_poly, uint64_t len, uint32_t log_domain, uint64_t num_points, uint64_t* out_xy,
+                                uint32_t* out_evals, hipStream_t st);
 int32_t poly_lincomb_dispatch(int curve, uint32_t n_terms, const uint32_t* const* d_polys, const uint64_t* lens, const uint32_t* scalars, uint32_t* d_out,
                               uint64_t out_len, hipStream_t st);
 int32_t poly_degree_dispatch(const uint32_t* d_poly, uint64_t len, unsigned long long* d_out, hipStream_t st);

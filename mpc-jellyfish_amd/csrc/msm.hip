@@ -714,6 +714,8 @@ int32_t msm_batch_dispatch(const Srs& s, uint32_t n_polys, const uint32_t* const
 
 static_assert(srs_int_point_bytes(MZK_CURVE_BLS12_381) == EcFz<BlsFqZ>::AFF_WORDS * 4 && srs_int_point_bytes(MZK_CURVE_BN254) == EcFx<BnFqX>::AFF_WORDS * 4,
               "srs_int_point_bytes (internal.hpp) is the size of an internal affine point");
+static_assert(ec_ntt_point_bytes(MZK_CURVE_BLS12_381) == EcFx<BlsFqX>::PT_WORDS * 4 && ec_ntt_point_bytes(MZK_CURVE_BN254) == EcFx<BnFqX>::PT_WORDS * 4,
+              "ec_ntt_point_bytes (internal.hpp) is the size of a point of the group NTT");
 // builds the internal (reduced-radix) copy of a freshly registered SRS
 template <class EC>
 static int32_t srs_build_internal_t(Srs& s, hipStream_t st, void (*to_internal)(const uint32_t*, unsigned long long, uint32_t*)) {
@@ -785,10 +787,32 @@ int32_t srs_lagrange_generate(const uint32_t* beta_canon, const uint32_t* g_xy_m
     return MZK_OK;
 }
 
-// ... and from the points of an SRS alone (no trapdoor): the inverse group-NTT of its first 2^log_n points (msm.cuh), then S_(n+j) - S_j
+// The group NTT (ec_ntt.cuh) of the n = 2^log_n points at `a`, in place and asynchronous on st: natural order in, bit-reversed out.
+// tab: 8 points of scratch for each of the n / 2 threads of a stage (8 at least).  d_out (nullable): the finishing pass -- the first n_out
+// elements of the transform in natural order, affine in the boundary form.
+template <class FR, class X>
+int32_t ecx_ntt(uint32_t* a, int log_n, bool inverse, bool scaled, uint32_t* tab, uint32_t* d_out, uint64_t n_out, hipStream_t st) {
+    using F = Fp<FR>;
+    const uint64_t n = 1ull << log_n;
+    F w = F::from_const(FR::ROOT);
+    for (int i = log_n; i < FR::TWO_ADICITY; i++) w = sqr(w);
+    const F root = from_mont(inverse ? inv(w) : w), ninv = from_mont(inv(from_u64<FR>(n)));
+    EcNttConsts c;
+    std::memcpy(c.w, root.l, 32);
+    std::memcpy(c.ninv, ninv.l, 32);
+    const unsigned gn = (unsigned)((n + EC_NTT_THREADS - 1) / EC_NTT_THREADS), gh = (unsigned)((n / 2 + EC_NTT_THREADS - 1) / EC_NTT_THREADS);
+    for (uint64_t h = n / 2; h >= 1; h >>= 1)
+        hipLaunchKernelGGL((ecx_ntt_stage_kernel<FR, X>), dim3(gh ? gh : 1), dim3(EC_NTT_THREADS), 0, st, a, n, h, c, tab, scaled);
+    if (d_out)
+        hipLaunchKernelGGL((ecx_ntt_finish_kernel<X>), dim3(gn), dim3(EC_NTT_THREADS), 0, st, a, n, log_n, c, tab, scaled, d_out,
+                           (unsigned long long)n_out);
+    HIP_TRY(hipGetLastError());
+    return MZK_OK;
+}
+
+// ... and from the points of an SRS alone (no trapdoor): the inverse group-NTT of its first 2^log_n points, scaled by 1/n, then S_(n+j) - S_j
 template <class FR, class FQ, class X>
 int32_t srs_lagrange_from_points(const uint32_t* d_xy, int log_n, uint32_t n_extra, uint32_t* d_out) {
-    using F = Fp<FR>;
     using EC = EcFx<X>;
     hipStream_t st = nullptr;
     const uint64_t n = 1ull << log_n;
@@ -798,20 +822,10 @@ int32_t srs_lagrange_from_points(const uint32_t* d_xy, int log_n, uint32_t n_ext
     // instead of staying in the grow-only workspace (an MSM's over-long-bucket scratch needs a small fraction of it)
     const size_t parts_before = ws->long_parts.cap, parts_need = (n * 5 + 8) * EC::PT_WORDS * 4;
     MZK_TRY(ws->long_parts.reserve(parts_need));
-    MZK_TRY(ws->misc.reserve(64));
     uint32_t* a = ws->long_parts.as<uint32_t>();
     uint32_t* tab = a + n * EC::PT_WORDS;
-    uint32_t* d_c = ws->misc.as<uint32_t>();
-    F w = F::from_const(FR::ROOT);
-    for (int i = log_n; i < FR::TWO_ADICITY; i++) w = sqr(w);
-    const F winv = from_mont(inv(w)), ninv = from_mont(inv(from_u64<FR>(n)));
-    HIP_TRY(hipMemcpyAsync(d_c, winv.l, 32, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_c + 8, ninv.l, 32, hipMemcpyHostToDevice, st));
-    const unsigned gn = (unsigned)((n + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS), gh = (unsigned)((n / 2 + MSM_ACC_THREADS - 1) / MSM_ACC_THREADS);
-    hipLaunchKernelGGL((ecx_ntt_load_kernel<X>), dim3(gn), dim3(MSM_ACC_THREADS), 0, st, d_xy, n, a);
-    for (uint64_t h = n / 2; h >= 1; h >>= 1)
-        hipLaunchKernelGGL((ecx_ntt_stage_kernel<FR, X>), dim3(gh ? gh : 1), dim3(MSM_ACC_THREADS), 0, st, a, n, h, d_c, tab);
-    hipLaunchKernelGGL((ecx_ntt_finish_kernel<X>), dim3(gn), dim3(MSM_ACC_THREADS), 0, st, a, n, log_n, d_c + 8, tab, d_out);
+    hipLaunchKernelGGL((ecx_ntt_load_kernel<X>), dim3((unsigned)((n + EC_NTT_THREADS - 1) / EC_NTT_THREADS)), dim3(EC_NTT_THREADS), 0, st, d_xy, n, a, n, false);
+    MZK_TRY((ecx_ntt<FR, X>(a, log_n, true, true, tab, d_out, n, st)));
     if (n_extra) hipLaunchKernelGGL((ec_ntt_extra_kernel<FQ>), dim3(1), dim3(64), 0, st, d_xy, n, n_extra, d_out + n * 2 * FQ::N);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -878,6 +892,10 @@ int32_t srs_generate_dispatch(int curve, const uint32_t* beta_canon, const uint3
 int32_t srs_lagrange_generate_dispatch(int curve, const uint32_t* beta_canon, const uint32_t* g_xy_mont, int log_n, uint32_t n_extra, uint32_t* d_out) {
     return curve == 0 ? srs_lagrange_generate<BlsFr, BlsFq>(beta_canon, g_xy_mont, log_n, n_extra, d_out)
                       : srs_lagrange_generate<BnFr, BnFq>(beta_canon, g_xy_mont, log_n, n_extra, d_out);
+}
+int32_t ec_ntt_dispatch(int curve, uint32_t* d_a, int log_n, bool inverse, bool scaled, uint32_t* d_tab, uint32_t* d_out_xy, uint64_t n_out, hipStream_t st) {
+    return curve == 0 ? ecx_ntt<BlsFr, BlsFqX>(d_a, log_n, inverse, scaled, d_tab, d_out_xy, n_out, st)
+                      : ecx_ntt<BnFr, BnFqX>(d_a, log_n, inverse, scaled, d_tab, d_out_xy, n_out, st);
 }
 int32_t srs_lagrange_from_points_dispatch(int curve, const uint32_t* d_xy, int log_n, uint32_t n_extra, uint32_t* d_out) {
     return curve == 0 ? srs_lagrange_from_points<BlsFr, BlsFq, BlsFqX>(d_xy, log_n, n_extra, d_out) : srs_lagrange_from_points<BnFr, BnFq, BnFqX>(d_xy, log_n, n_extra, d_out);

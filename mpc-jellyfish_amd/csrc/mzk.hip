@@ -48,7 +48,7 @@ const Workspace::Named Workspace::bufs[] = {
 static_assert(sizeof(Workspace) == sizeof(Workspace::bufs) / sizeof(Workspace::bufs[0]) * sizeof(DevBuf) + sizeof(void*) + sizeof(size_t) + sizeof(double) + sizeof(hipEvent_t),
               "a DevBuf of Workspace is missing from Workspace::bufs");
 void Srs::free() {
-    for (uint32_t** d : {&d_xy, &d_int, &d_pre}) {
+    for (uint32_t** d : {&d_xy, &d_int, &d_pre, &d_fk}) {
         if (*d) (void)hipFree(*d);
         *d = nullptr;
     }
@@ -564,14 +564,14 @@ int32_t mzk_srs_len(uint64_t handle, uint64_t* out_n_points) {
     *out_n_points = s->n;
     return MZK_OK;
 }
-// HBM a registered SRS holds: its points (boundary form + the MSM's internal reduced-radix form) and its fixed-base table
+// HBM a registered SRS holds: its points (boundary form + the MSM's internal reduced-radix form) and its tables (fixed-base; FK23's transformed SRS vector)
 int32_t mzk_srs_hbm_bytes(uint64_t handle, uint64_t* out_points_bytes, uint64_t* out_table_bytes) {
     ENTER_HANDLE(handle);
     const Srs* s = srs_find(*cx_, handle);
     if (!s) return MZK_ERR_BAD_HANDLE;
     const uint64_t aff_int = srs_int_point_bytes(s->curve);
     if (out_points_bytes) *out_points_bytes = s->n * srs_point_bytes(s->curve) + (s->d_int ? s->n * aff_int : 0);
-    if (out_table_bytes) *out_table_bytes = s->d_pre ? (uint64_t)s->pre_levels * s->n * aff_int : 0;
+    if (out_table_bytes) *out_table_bytes = (s->d_pre ? (uint64_t)s->pre_levels * s->n * aff_int : 0) + (s->d_fk ? 2 * s->fk_d * ec_ntt_point_bytes(s->curve) : 0);
     return MZK_OK;
 }
 int32_t mzk_launch_count(uint64_t* out_launches) {
@@ -1119,6 +1119,15 @@ int32_t mzk_kzg_open_batch_dev(uint64_t srs_handle, uint32_t K, const void* cons
     if (K && (!d_polys || !lens || !points_mont || !out_proofs_xy_mont || !out_evals_mont)) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
     return kzg_open_batch_dispatch(*s, K, reinterpret_cast<const uint32_t* const*>(d_polys), lens, reinterpret_cast<const uint32_t*>(points_mont),
                                    out_proofs_xy_mont, reinterpret_cast<uint32_t*>(out_evals_mont), (hipStream_t)stream);
+}
+int32_t mzk_kzg_multi_open_rou_dev(uint64_t srs_handle, uint64_t srs_offset, const void* d_poly, uint64_t len, uint32_t log_domain, uint64_t num_points,
+                                   uint64_t* out_proofs_xy_mont, uint64_t* out_evals_mont, void* stream) {
+    ENTER_HANDLE(srs_handle);
+    Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    if (len && !d_poly) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
+    return kzg_multi_open_dispatch(*s, srs_offset, reinterpret_cast<const uint32_t*>(d_poly), len, log_domain, num_points, out_proofs_xy_mont,
+                                   reinterpret_cast<uint32_t*>(out_evals_mont), (hipStream_t)stream);
 }
 
 // ---- page-locked host memory for the host-pointer entry points ------------------------------------------

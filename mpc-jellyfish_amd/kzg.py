@@ -7,6 +7,8 @@
     <G1 as VariableBaseMSM>::msm_bigint     mod.rs:109-111 -> msm_bigint
     open / batch_open                       mod.rs:135-190 -> UnivariateKzgPCS.open / batch_open (one pass: mzk_kzg_open_batch_dev)
     verify / batch_verify                   mod.rs:195-271 -> UnivariateKzgPCS.verify / batch_verify (keys.OpenKey.begin_openings)
+    multi_open_rou[_proofs|_evals], multi_open_rou_eval_domain, trim_fft_size, checked_fft_size
+                                            mod.rs:298-377, pcs/mod.rs:236-322 -> UnivariateKzgPCS.multi_open_rou .. (FK23: mzk_kzg_multi_open_rou_dev)
     UnivariateVerifierParam, trim's 2nd half srs.rs:48-55, 77-93 -> keys.OpenKey, UnivariateUniversalParams.verifier_param
     CanonicalSerialize / Deserialize        srs.rs:18-40   -> UnivariateProverParam.serialize / deserialize,
                                                               UnivariateUniversalParams (points decoded on the GPU)
@@ -292,6 +294,20 @@ def _degree_and_leading_zeros(coeffs: np.ndarray):
     return int(nz[-1]), int(nz[0])
 
 
+def _next_power_of_two(n: int) -> int:
+    """usize::next_power_of_two: 1 for 0"""
+    return 1 if n <= 1 else 1 << (n - 1).bit_length()
+
+
+def checked_fft_size(degree: int) -> int:
+    """pcs/mod.rs:308-322: the FFT size (`num_coeffs`) for a degree -- twice a power of two, else the next power of two; PCSError where
+    usize overflows."""
+    size = 2 * degree if degree > 0 and degree & (degree - 1) == 0 else _next_power_of_two(degree)
+    if degree < 0 or size >= 1 << 64:
+        raise PCSError(f"InvalidParameters: Next power of two overflows! Got: {degree}")
+    return size
+
+
 def msm_bigint(pp: UnivariateProverParam, bigints, base_offset: int = 0, scalars_are_mont: bool = False) -> np.ndarray:
     """sum_i bigints[i] * powers_of_g[base_offset + i] as a Jacobian point (3, fq_limbs), Montgomery.
     Uses min(len) of the two sides like ark-ec.  bigints: (n,4) uint64 host array or int64 CUDA tensor."""
@@ -461,6 +477,109 @@ class UnivariateKzgPCS:
             weights.append(lo | rng.next_u64() << 64)
         b = verifier_param.begin_openings(commitments, points, values, proofs)
         return verifier_param.check(*b.finish(fr_to_mont(c, weights)))
+
+    # ---- UnivariatePCS (pcs/mod.rs:228-306): one polynomial opened over a radix-2 domain ------------------------------------------
+    @staticmethod
+    def trim_fft_size(params, supported_degree: int):
+        """pcs/mod.rs:236-254: `trim` to checked_fft_size(supported_degree).  params: a UnivariateUniversalParams -> (prover param, OpenKey), or
+        a UnivariateProverParam alone -> its trimmed view."""
+        fft_degree = checked_fft_size(supported_degree)
+        pp = params.powers_of_g if isinstance(params, UnivariateUniversalParams) else params
+        try:
+            trimmed = pp.trim(fft_degree)
+        except PCSError as e:
+            raise PCSError(f"InvalidParameters: Requesting degree of {fft_degree} for FFT:\n\t\t{e}") from None
+        return (trimmed, params.verifier_param()) if isinstance(params, UnivariateUniversalParams) else trimmed
+
+    @staticmethod
+    def multi_open_rou_eval_domain(curve, degree: int, num_points: int):
+        """pcs/mod.rs:259-275: the domain of max(checked_fft_size(degree) + 1, num_points) points, rounded up to a power of two."""
+        from .domain import Radix2EvaluationDomain
+        size = max(checked_fft_size(degree) + 1, num_points)
+        try:
+            return Radix2EvaluationDomain.new(curve, size)
+        except ValueError:
+            raise PCSError(f"UpstreamError: Fail to init eval domain of size {size}") from None
+
+    @staticmethod
+    def _rou_check(curve, n: int, domain, degree_limit: int | None):
+        """The reference's refusals for a polynomial of n coefficients, made before the device is touched: those of the evaluations
+        (degree_limit None), or of the proofs under a prover param of degree_limit points."""
+        if domain.curve is not curve or not domain.coset_offset_is_one():
+            raise PCSError("InvalidParameters: multi_open_rou takes the radix-2 domain of the polynomial's field with offset one, not a coset")
+        if degree_limit is None:
+            if n > domain.size:                                            # pcs/poly.rs:141-147
+                raise PCSError(f"InvalidParameters: Polynomial with {n} num_of_coeffs can't be evaluated on a smaller domain with size {domain.size}")
+            return
+        d = _next_power_of_two(max(n, 1) - 1)                              # mod.rs:342-349: the padded degree, from the length as given
+        if d > degree_limit:                                               # (srs_vec comes out shorter than the matrix: toeplitz.rs:127-131)
+            raise PCSError(f"InvalidParameters: the prover parameter holds {degree_limit} points, FK23 at padded degree {d} takes {d}")
+        if d > domain.size:
+            raise PCSError(f"InvalidParameters: Polynomial with {d} num_of_coeffs can't be evaluated on a smaller domain with size {domain.size}")
+
+    @staticmethod
+    def _rou_coeffs(polynomial):
+        """(len, 4) Montgomery coefficients as given: a CUDA tensor stays where it is, a host array stays on the host until the checks passed"""
+        if _is_torch(polynomial):
+            import torch
+            if polynomial.dtype != torch.int64 or not polynomial.is_cuda or polynomial.dim() != 2 or polynomial.shape[1] != 4:
+                raise ValueError("expected a (len, 4) int64 CUDA tensor or a uint64 host array")
+            return polynomial.contiguous()
+        return np.ascontiguousarray(polynomial, dtype=np.uint64).reshape(-1, 4)
+
+    @staticmethod
+    def _rou_device(a):
+        if _is_torch(a):
+            return a
+        import torch
+        return torch.from_numpy(a.view(np.int64)).cuda()
+
+    @staticmethod
+    def _rou_open(pp, a, num_points: int, domain, want_evals: bool):
+        import torch
+        c, t, n, k = pp.curve, UnivariateKzgPCS._rou_device(a), a.shape[0], min(max(num_points, 0), domain.size)
+        proofs = np.zeros((k, 2, c.fq_limbs), dtype=np.uint64)
+        evals = np.zeros((k, 4), dtype=np.uint64) if want_evals else None
+        st = torch.cuda.current_stream(t.device).cuda_stream
+        _lib.check(_lib.ensure_init().mzk_kzg_multi_open_rou_dev(pp.handle, pp.offset, t.data_ptr() if n else None, n, domain.log_size_of_group, k,
+                                                                 C.c_void_p(proofs.ctypes.data), None if evals is None else C.c_void_p(evals.ctypes.data),
+                                                                 C.c_void_p(st)), "mzk_kzg_multi_open_rou_dev")
+        return [Commitment(c, proofs[i]) for i in range(k)], None if evals is None else fr_from_mont(c, evals)
+
+    @staticmethod
+    def multi_open_rou(prover_param: UnivariateProverParam, polynomial, num_points: int, domain):
+        """pcs/mod.rs:281-290: the polynomial opened at the first num_points points w^0, w^1, .. of `domain` (a domain.Radix2EvaluationDomain with
+        offset one; at most its size: the reference's `take`) -> ([Commitment proofs], [evaluation ints]).  One call of the device
+        (mzk_kzg_multi_open_rou_dev): the evaluations by a scalar NTT, the proofs by FK23 in O(d log d) group operations, d the padded degree --
+        next_power_of_two(len - 1) of the coefficient array AS GIVEN (trailing zeros are not trimmed; the proofs do not depend on it, the
+        number of points taken from prover_param does).  The transformed SRS vector stays on the prover param's registration for the next call
+        at the same d.  polynomial: (len, 4) Montgomery coefficients, host array or CUDA tensor.  The evaluation step's checks come first, as
+        in the reference; every refusal raises PCSError before the device is touched."""
+        pp, K = prover_param, UnivariateKzgPCS
+        a = K._rou_coeffs(polynomial)
+        K._rou_check(pp.curve, a.shape[0], domain, None)                   # multi_open_rou_evals's refusals, then multi_open_rou_proofs's
+        K._rou_check(pp.curve, a.shape[0], domain, pp.length)
+        return K._rou_open(pp, a, num_points, domain, True)
+
+    @staticmethod
+    def multi_open_rou_proofs(prover_param: UnivariateProverParam, polynomial, num_points: int, domain) -> list[Commitment]:
+        """mod.rs:299-313: the proofs of multi_open_rou alone."""
+        a = UnivariateKzgPCS._rou_coeffs(polynomial)
+        UnivariateKzgPCS._rou_check(prover_param.curve, a.shape[0], domain, prover_param.length)
+        return UnivariateKzgPCS._rou_open(prover_param, a, num_points, domain, False)[0]
+
+    @staticmethod
+    def multi_open_rou_evals(polynomial, num_points: int, domain) -> list[int]:
+        """mod.rs:316-327: the evaluations of multi_open_rou alone -- the coefficients zero-padded to the domain, one forward NTT
+        (domain.fft_in_place), the first num_points values.  No SRS."""
+        import torch
+        a = UnivariateKzgPCS._rou_coeffs(polynomial)
+        UnivariateKzgPCS._rou_check(domain.curve, a.shape[0], domain, None)
+        t, n, k = UnivariateKzgPCS._rou_device(a), a.shape[0], min(max(num_points, 0), domain.size)
+        buf = torch.zeros((domain.size, 4), dtype=torch.int64, device=t.device)
+        buf[:n] = t
+        domain.fft_in_place(buf)
+        return fr_from_mont(domain.curve, buf[:k].cpu().numpy().view(np.uint64))
 
 
 def jacobian_to_affine(curve, xyz: np.ndarray) -> np.ndarray:

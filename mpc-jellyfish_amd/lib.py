@@ -97,6 +97,7 @@ _SIGS = {
     "mzk_verifier_link_weights": [C.c_uint64, C.c_void_p, C.c_void_p],
     "mzk_verifier_open_begin": [C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_kzg_open_batch_dev": [C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_kzg_multi_open_rou_dev": [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_srs_register_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_srs_register_serialized_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_srs_serialize": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p],
