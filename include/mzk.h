@@ -725,6 +725,77 @@ MZK_API int32_t mzk_kzg_open_batch_dev(uint64_t srs_handle, uint32_t K, const vo
 MZK_API int32_t mzk_kzg_multi_open_rou_dev(uint64_t srs_handle, uint64_t srs_offset, const void* d_poly, uint64_t len, uint32_t log_domain,
                                            uint64_t num_points, uint64_t* out_proofs_xy_mont, uint64_t* out_evals_mont, void* stream);
 
+/* ---- ADVZ verifiable information dispersal: VidScheme for Advz<E, Sha256> (primitives/src/vid/advz.rs; csrc/vid.hip, vid.cuh, sha256.cuh;
+ *      DESIGN.md section 4.17).  A payload becomes K = ceil(elements / payload_chunk_size) polynomials of payload_chunk_size (k) coefficients;
+ *      each of the num_storage_nodes (n >= k) nodes receives the K evaluations at its point w^i of the domain of 2^log_domain points
+ *      (UnivariatePCS::multi_open_rou_eval_domain(k, n): the chunk size passed where a degree is expected), a path in a ternary SHA-256
+ *      tree over the n evaluation vectors, and ONE opening proof of the aggregate polynomial s * sum_j poly_j.  What is restated as the
+ *      reference has it, quirks included, and what is unpinned: DESIGN.md section 4.17. ---- */
+/* SHA-256 (FIPS 180-4) of len bytes -> out32.  Host only: no GPU, no mzk_init. */
+MZK_API int32_t mzk_sha256(const uint8_t* msg, uint64_t len, uint8_t* out32);
+/* expand_message_xmd of RFC 9380 section 5.3.1 over SHA-256: out_len <= 8160 bytes from (msg, dst), dst_len <= 255, with Z_pad of z_pad_len
+ * zero bytes (<= 4096) in front of msg: 64 is the RFC's (SHA-256's block); ark-ff 0.4's DefaultFieldHasher uses the bytes per field element,
+ * 48 for both scalar fields -- the value mzk_hash_to_field_sha256 and the VID scheme use (csrc/sha256.cuh XMD_Z_PAD_ARK).  Host only. */
+MZK_API int32_t mzk_expand_message_xmd_sha256(const uint8_t* msg, uint64_t len, const uint8_t* dst, uint64_t dst_len, uint32_t z_pad_len, uint8_t* out,
+                                              uint64_t out_len);
+/* <DefaultFieldHasher<Sha256, 128> as HashToField<Fr>>::new(dst).hash_to_field(msg, 1)[0]: 48 expanded bytes, big-endian, mod r -> out_mont (4
+ * limbs, Montgomery).  Host only. */
+MZK_API int32_t mzk_hash_to_field_sha256(int32_t curve_id, const uint8_t* msg, uint64_t len, const uint8_t* dst, uint64_t dst_len, uint64_t* out_mont);
+/* bytes_to_field (utilities/src/conversion.rs:379-408) on the device: len bytes at d_bytes (any alignment) -> len / 31 elements of 31 little-endian
+ * bytes each and, when 31 does not divide len, the zero-extended last group followed by one element holding its byte count -- len / 31 +
+ * (len % 31 ? 2 : 0) Montgomery elements at d_out_mont (16-byte aligned).  A multiple of 31 gets NO length element, as in the reference.  One
+ * thread per element; asynchronous on the stream; no scratch.  len >= 2^40: MZK_ERR_INVALID_ARG. */
+MZK_API int32_t mzk_bytes_to_field_dev(int32_t curve_id, const void* d_bytes, uint64_t len, void* d_out_mont, void* stream);
+/* field_to_bytes (conversion.rs:443-523) as written: count = 1 -> the element's low 31 bytes; otherwise 31 bytes of each of the first count - 2
+ * elements, then min(low 64 bits of the LAST element, 32) bytes of the one before it.  It inverts mzk_bytes_to_field_dev for len % 31 != 0 and
+ * for len = 0 and 31; for other multiples of 31 it reads the last data element as a length, as the reference does.  d_out_bytes holds at least
+ * 31 * max(count - 2, 0) + 32 bytes; *out_len (host) = the bytes written.  8 bytes of the shared workspace.  Synchronises the stream. */
+MZK_API int32_t mzk_field_to_bytes_dev(int32_t curve_id, const void* d_elems_mont, uint64_t count, void* d_out_bytes, uint64_t* out_len, void* stream);
+/* VidScheme::commit_only: SHA256(C_0 || C_1 || ..) over the ark uncompressed G1 records (as mzk_srs_serialize writes them, infinity included) of
+ * the K commitments of the payload's polynomials -- polynomial j = elements j k .. of d_elems_mont (n_elems Montgomery elements on the device, 16-byte
+ * aligned), the last one over its own, fewer, coefficients -- by one mzk_msm_batch_dev over the SRS view (srs_offset, srs_len).  n_elems = 0:
+ * SHA256 of nothing.  Refused before any launch -- MZK_ERR_INVALID_ARG: k = 0, n < k, the view outside the SRS or shorter than k points, 2^log_domain < n;
+ * MZK_ERR_UNSUPPORTED: log_domain above the caps of mzk_kzg_multi_open_rou_dev, 2^24 polynomials.  Scratch: K (point + record) bytes of the shared workspace.
+ * Synchronises the stream. */
+MZK_API int32_t mzk_vid_advz_commit_only_dev(uint64_t srs_handle, uint64_t srs_offset, uint64_t srs_len, const void* d_elems_mont, uint64_t n_elems,
+                                             uint32_t payload_chunk_size, uint32_t num_storage_nodes, uint32_t log_domain, uint8_t* out_commit32, void* stream);
+/* Advz::disperse_from_elems (advz.rs:279-391).  In: the payload's elements on the device.  Out, all to the host:
+ *   out_commits_xy_mont  K affine points x || y (Montgomery, (0, 0) = infinity): Common::poly_commits
+ *   out_evals            n x K x 32 bytes: evals[i][j] = poly_j(w^i) as its canonical little-endian bytes, Share i's `evals`
+ *   out_proofs_xy_mont   n affine points: Share i's aggregate_proof, the opening of s * sum_j poly_j at w^i (FK23, mzk_kzg_multi_open_rou_dev)
+ *   out_nodes            every digest of the tree, 32 bytes each, level by level: the n leaves SHA256(u64_le(i) || u64_le(K) || evals[i]), then
+ *                        ceil(n / 3) branches SHA256(c0 || c1 || c2) (32 zero bytes for a missing child), .. -- height = ilog3(n) + 1 branch
+ *                        levels, the root last: sum over the levels of their sizes n, ceil(n / 3), .., 1 (a caller cuts the n paths out of it)
+ *   out_commit32         SHA256 of the commitments' uncompressed records (the VID commitment); out_root32: Common::all_evals_digest
+ *   out_scalar_mont      s = hash_to_field(SHA256(records || root), DST "rick"), 4 limbs
+ * Two phases on the stream around the one forced wait (the host hashes the commitments between them): [zero-padded copy -> batched forward NTT ->
+ * leaf kernel (one read of the NTT output writes evals[i][j] and hashes it) -> one launch per tree level -> batch MSM], then [aggregate -> FK23].
+ * n_elems = 0 is a valid dispersal: K = 0, leaves of 16 bytes, every proof O.  Refusals: those of mzk_vid_advz_commit_only_dev, before any
+ * launch.  Scratch from the shared workspace, in bytes: 32 (K 2^log_domain + n K + nodes + k) + K (point + record) -- beside what the batch MSM and
+ * mzk_kzg_multi_open_rou_dev take.  Synchronises the stream. */
+MZK_API int32_t mzk_vid_advz_disperse_dev(uint64_t srs_handle, uint64_t srs_offset, uint64_t srs_len, const void* d_elems_mont, uint64_t n_elems,
+                                          uint32_t payload_chunk_size, uint32_t num_storage_nodes, uint32_t log_domain, uint64_t* out_commits_xy_mont,
+                                          uint8_t* out_evals, uint64_t* out_proofs_xy_mont, uint8_t* out_nodes, uint8_t* out_commit32, uint8_t* out_root32,
+                                          uint64_t* out_scalar_mont, void* stream);
+/* The Merkle half of Advz::verify_share for n_shares shares in ONE launch, one thread per share (all arguments on the host): share t has
+ * indices[t], evals[t] (evals_per_share x 32 canonical little-endian bytes) and paths[t] (height levels from the leaf up, the 2 sibling digests of
+ * each level in child order, zeros for an empty one; height = ilog3(num_storage_nodes) + 1).  out_ok[t] = 1 when indices[t] < num_storage_nodes
+ * and the leaf hashed from evals[t] climbs to root32 with the index's base-3 digits, least significant first, as the traversal key;
+ * out_agg_evals_mont[t] = s * sum_j evals[t][j] (4 limbs, Montgomery): the value the share's KZG opening is checked against
+ * (UnivariateKzgPCS::verify at w^index).  n_shares = 0: nothing.  Scratch: the arguments' bytes + 36 n_shares.  Synchronises the stream. */
+MZK_API int32_t mzk_vid_advz_verify_shares_dev(int32_t curve_id, uint64_t n_shares, uint64_t evals_per_share, uint32_t num_storage_nodes, const uint64_t* indices,
+                                               const uint8_t* evals, const uint8_t* paths, const uint8_t* root32, const uint64_t* scalar_mont, int32_t* out_ok,
+                                               uint64_t* out_agg_evals_mont, void* stream);
+/* Advz::recover_elems' interpolation (reed_solomon_erasure_decode_rou, reed_solomon_code/mod.rs:68-187): k = payload_chunk_size shares with
+ * indices[i] (host) and evals_mont[p][i] (host, n_polys x k Montgomery elements: polynomial p at w^indices[i]) -> d_out_mont (device, 16-byte
+ * aligned): n_polys x k coefficients, polynomial after polynomial.  The interpolant is unique, so the field elements are the reference's: the k x k
+ * matrix of the Lagrange basis is built once (master polynomial in one workgroup, l'(x_i), one inversion and a synthetic division per row),
+ * then out[p][c] = sum_i y[p][i] M[i][c] with n_polys k threads.  Refused before any launch -- MZK_ERR_INVALID_ARG: k = 0, an index >= 2^log_domain,
+ * a duplicate index; MZK_ERR_UNSUPPORTED: k > 1024, the one workgroup (and 32 KiB of LDS) of the master polynomial.  Scratch: 32 (2 k + k^2 + n_polys k)
+ * bytes of the shared workspace, 32 MiB for the matrix at the cap.  Synchronises the stream. */
+MZK_API int32_t mzk_vid_advz_recover_dev(int32_t curve_id, uint32_t payload_chunk_size, uint64_t n_polys, uint32_t log_domain, const uint64_t* indices,
+                                         const uint64_t* evals_mont, void* d_out_mont, void* stream);
+
 /* ---- the prover's rounds on device-resident state: replaces the BODIES of Prover::run_1st_round .. compute_opening_proofs
  *      (plonk/src/proof_system/prover.rs:72-419) as PlonkKzgSnark::batch_prove_internal calls them (snark.rs:263-431).
  * One mzk_prover per (proving key, instance slot): it holds, in HBM, the coefficient forms of the key's fixed polynomials, their

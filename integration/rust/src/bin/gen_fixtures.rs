@@ -28,6 +28,14 @@
 //! `multi_open_cases.json` -> `ref_multi_open.json`: `UnivariatePCS::multi_open_rou` (FK23) of one polynomial over the domain that
 //! `multi_open_rou_eval_domain` picks, SRS rebuilt from (beta, G); `tests/test_kzg_multi_open_ref_gpu.py` holds the device to it.
 //!
+//! `vid_cases.json` (curve, k, n, beta, payload hex) -> `ref_vid.json`: the reference's own `Advz::<E, Sha256>::disperse` over the SRS rebuilt
+//! from (beta, G, the G2 generator) -- `commit`, `Common` and every `Share`; the private fields are reached through the types' serde images
+//! (serde_json of `Share` / `Common`: evals and points as their canonical bytes, the Merkle proof as its node list, of which the two siblings
+//! of every branch level are written out leaf level first, an `Empty` node as 32 zero bytes).  `tests/test_vid_advz_ref_gpu.py` holds the device
+//! to it; until it has been run the Z_pad length of the field hasher is unpinned.  Like the rest of this file the
+//! family has never been compiled here: the field names it reads from the serde images follow advz.rs and merkle_tree/internal.rs as read,
+//! and a first run may have to adjust them.
+//!
 //! NOT COMPILED in this repository's build image (no Rust toolchain); see README.md.
 use ark_ec::{pairing::Pairing, AffineRepr, CurveGroup, VariableBaseMSM};
 use ark_ff::{BigInt, BigInteger, PrimeField, UniformRand, Zero};
@@ -154,6 +162,61 @@ macro_rules! curve_fixtures {
                 out["domain_size"] = json!(domain.size());
                 out["proofs"] = json!(proofs.iter().map(|p| point_json(&p.proof)).collect::<Vec<_>>());
                 out["evals"] = json!(evals.iter().map(hx).collect::<Vec<_>>());
+                out
+            }
+
+            /// `Advz::<E, Sha256>::disperse` (primitives/src/vid/advz.rs) over powers_of_g[i] = beta^i G, h the G2 generator, beta_h = [beta]h
+            pub fn vid(case: &Value) -> Value {
+                use jf_primitives::vid::{advz::Advz, VidScheme};
+                let beta: Fr = fe(case["beta"].as_str().unwrap());
+                let (k, n) = (case["k"].as_u64().unwrap() as usize, case["n"].as_u64().unwrap() as usize);
+                let payload = hex_bytes(case["payload"].as_str().unwrap());
+                let points = if k.is_power_of_two() { 2 * k } else { k.next_power_of_two() } + 1;
+                let mut powers_of_g = Vec::with_capacity(points);
+                let mut cur = G1::from(G1Affine::generator());
+                for _ in 0..points {
+                    powers_of_g.push(cur.into_affine());
+                    cur *= beta;
+                }
+                let h = <E as Pairing>::G2Affine::generator();
+                let srs = UnivariateUniversalParams::<E> { powers_of_g, h, beta_h: (h * beta).into_affine() };
+                let advz = Advz::<E, sha2::Sha256>::new(k, n, &srs).unwrap();
+                let disperse = advz.disperse(&payload).unwrap();
+                for share in disperse.shares.iter() {
+                    advz.verify_share(share, &disperse.common).unwrap().unwrap();
+                }
+                let common = serde_json::to_value(&disperse.common).unwrap();
+                let commits: Vec<G1Affine> = canonical_vec(&common["poly_commits"]);
+                let mut out = case.clone();
+                out["commit"] = json!(hex_of(disperse.commit.as_slice()));
+                out["elems_len"] = common["elems_len"].clone();
+                out["all_evals_digest"] = json!(hex_of(&serde_bytes(&common["all_evals_digest"])));
+                out["poly_commits"] = json!(commits.iter().map(point_json).collect::<Vec<_>>());
+                out["shares"] = json!(disperse
+                    .shares
+                    .iter()
+                    .map(|share| {
+                        let v = serde_json::to_value(share).unwrap();
+                        let evals: Vec<Fr> = canonical_vec(&v["evals"]);
+                        let proof: G1Affine = canonical_one(&v["aggregate_proof"]);
+                        let index = v["index"].as_u64().unwrap();
+                        // MerkleProof { pos, proof: [Leaf, Branch { children }, ..] }: the other two children of every branch, leaf level first
+                        let mut pos = index;
+                        let siblings: Vec<Value> = v["evals_proof"]["proof"].as_array().unwrap()[1..]
+                            .iter()
+                            .map(|branch| {
+                                let kids = branch["Branch"]["children"].as_array().unwrap();
+                                let row: Vec<String> = (0..3u64)
+                                    .filter(|t| *t != pos % 3)
+                                    .map(|t| hex_of(&node_value(&kids[t as usize])))
+                                    .collect();
+                                pos /= 3;
+                                json!(row)
+                            })
+                            .collect();
+                        json!({"index": index, "evals": evals.iter().map(hx).collect::<Vec<_>>(), "aggregate_proof": point_json(&proof), "siblings": siblings})
+                    })
+                    .collect::<Vec<_>>());
                 out
             }
 
@@ -422,6 +485,36 @@ curve_fixtures!(bls, 0u32, ark_bls12_381::Bls12_381, ark_bls12_381::Fr, ark_bls1
                 ark_bls12_381::G2Projective);
 curve_fixtures!(bn, 1u32, ark_bn254::Bn254, ark_bn254::Fr, ark_bn254::Fq, ark_bn254::G1Affine, ark_bn254::G1Projective, ark_bn254::G2Projective);
 
+fn hex_bytes(hex: &str) -> Vec<u8> {
+    (0..hex.len() / 2).map(|i| u8::from_str_radix(&hex[2 * i..2 * i + 2], 16).expect("hex byte")).collect()
+}
+fn hex_of(bytes: &[u8]) -> String {
+    bytes.iter().map(|b| format!("{:02x}", b)).collect()
+}
+/// a serde image of bytes: an array of numbers (a digest's GenericArray), or the `FIELD~..` string jf_utils::canonical writes
+/// (utilities/src/serialize.rs:52-83: TaggedBase64 over serialize_compressed)
+fn serde_bytes(v: &Value) -> Vec<u8> {
+    match v {
+        Value::Array(a) => a.iter().map(|b| b.as_u64().expect("byte") as u8).collect(),
+        Value::String(s) => tagged_base64::TaggedBase64::parse(s).expect("tagged base64").value(),
+        _ => panic!("serde image of bytes"),
+    }
+}
+fn canonical_vec<T: ark_serialize::CanonicalDeserialize>(v: &Value) -> Vec<T> {
+    Vec::<T>::deserialize_compressed(&serde_bytes(v)[..]).expect("canonical image")
+}
+fn canonical_one<T: ark_serialize::CanonicalDeserialize>(v: &Value) -> T {
+    T::deserialize_compressed(&serde_bytes(v)[..]).expect("canonical image")
+}
+/// the digest of a child in a Merkle proof's branch: 32 zero bytes for `Empty`, the `value` of a leaf, branch or forgotten subtree
+fn node_value(v: &Value) -> Vec<u8> {
+    if v.as_str() == Some("Empty") {
+        return vec![0u8; 32];
+    }
+    let inner = v.as_object().and_then(|o| o.values().next()).expect("a Merkle node");
+    serde_bytes(&inner["value"])
+}
+
 fn run_to(dir: &Path, name: &str, out_name: &str, f0: fn(&Value) -> Value, f1: fn(&Value) -> Value) {
     let text = fs::read_to_string(dir.join(format!("{name}.json"))).expect("golden vector file");
     let cases: Vec<Value> = serde_json::from_str(&text).unwrap();
@@ -446,5 +539,6 @@ fn main() {
     run(dir, "link_vectors", bls::link, bn::link);
     run_to(dir, "general_ref_cases", "ref_general_circuits", bls::general, bn::general);
     run_to(dir, "multi_open_cases", "ref_multi_open", bls::multi_open, bn::multi_open);
+    run_to(dir, "vid_cases", "ref_vid", bls::vid, bn::vid);
     let _ = BigInt::<4>::zero().is_zero();
 }

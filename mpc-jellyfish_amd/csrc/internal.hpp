@@ -69,7 +69,7 @@ struct DevOwned {
 };
 
 struct Workspace {
-    DevBuf ntt_scratch, scalars, hist, offs, cursor, sorted, buckets, collect, io, misc, digits, long_desc, long_parts, plonk_polys, plonk_out, pre_cnt, pre_off, pre_ce, pre_cb, poly_tmp, split, link_tmp, occ;
+    DevBuf ntt_scratch, scalars, hist, offs, cursor, sorted, buckets, collect, io, misc, digits, long_desc, long_parts, plonk_polys, plonk_out, pre_cnt, pre_off, pre_ce, pre_cb, poly_tmp, split, link_tmp, occ, vid;
     void* h_collect = nullptr;
     size_t h_collect_cap = 0;
     double heavy_frac = 0.125;          // msm.hip: share of the worst case the heavy buckets' level-1 sums are sized for (grows on overflow, with a re-run)
@@ -253,6 +253,19 @@ int32_t poly_div_roots_dispatch(int curve, const uint32_t* d_poly, uint64_t len,
 constexpr int KZG_MULTI_MAX_LOG = 21;       // cap on log2(2d) and log_domain (include/mzk.h: the workspace formula)
 int32_t kzg_multi_open_dispatch(Srs& s, uint64_t srs_offset, const uint32_t* d_poly, uint64_t len, uint32_t log_domain, uint64_t num_points, uint64_t* out_xy,
                                 uint32_t* out_evals, hipStream_t st);
+// vid.hip: the ADVZ VID scheme behind its entry points' pointer checks (mzk_bytes_to_field_dev .. mzk_vid_advz_recover_dev); all but
+// vid_bytes_to_field_dispatch wait for the stream
+uint64_t vid_field_count(uint64_t len);                       // elements bytes_to_field makes of len bytes
+int32_t vid_bytes_to_field_dispatch(int curve, const uint8_t* d_bytes, uint64_t len, uint32_t* d_out, hipStream_t st);
+int32_t vid_field_to_bytes_dispatch(int curve, const uint32_t* d_elems, uint64_t count, uint8_t* d_out, uint64_t* out_len, hipStream_t st);
+int32_t vid_commit_only_dispatch(Srs& s, uint64_t srs_offset, uint64_t srs_len, const uint32_t* d_elems, uint64_t n_elems, uint32_t k, uint32_t n, uint32_t log_domain,
+                                 uint8_t* out_commit, hipStream_t st);
+int32_t vid_disperse_dispatch(Srs& s, uint64_t srs_offset, uint64_t srs_len, const uint32_t* d_elems, uint64_t n_elems, uint32_t k, uint32_t n, uint32_t log_domain,
+                              uint64_t* out_commits_xy, uint8_t* out_evals, uint64_t* out_proofs_xy, uint8_t* out_nodes, uint8_t* out_commit, uint8_t* out_root,
+                              uint64_t* out_s_mont, hipStream_t st);
+int32_t vid_verify_shares_dispatch(int curve, uint64_t S, uint64_t K, uint32_t n, const uint64_t* index, const uint8_t* evals, const uint8_t* paths, const uint8_t* root,
+                                   const uint64_t* s_mont, int32_t* out_ok, uint64_t* out_agg_mont, hipStream_t st);
+int32_t vid_recover_dispatch(int curve, uint32_t k, uint64_t K, uint32_t log_domain, const uint64_t* index, const uint64_t* y_mont, uint32_t* d_out, hipStream_t st);
 int32_t poly_lincomb_dispatch(int curve, uint32_t n_terms, const uint32_t* const* d_polys, const uint64_t* lens, const uint32_t* scalars, uint32_t* d_out,
                               uint64_t out_len, hipStream_t st);
 int32_t poly_degree_dispatch(const uint32_t* d_poly, uint64_t len, unsigned long long* d_out, hipStream_t st);

@@ -43,7 +43,7 @@ void DevBuf::release() {
 const Workspace::Named Workspace::bufs[] = {
     WS_BUF(ntt_scratch), WS_BUF(scalars), WS_BUF(hist), WS_BUF(offs), WS_BUF(cursor), WS_BUF(sorted), WS_BUF(buckets), WS_BUF(collect),
     WS_BUF(io), WS_BUF(misc), WS_BUF(digits), WS_BUF(long_desc), WS_BUF(long_parts), WS_BUF(plonk_polys), WS_BUF(plonk_out), WS_BUF(pre_cnt),
-    WS_BUF(pre_off), WS_BUF(pre_ce), WS_BUF(pre_cb), WS_BUF(poly_tmp), WS_BUF(split), WS_BUF(link_tmp), WS_BUF(occ)};
+    WS_BUF(pre_off), WS_BUF(pre_ce), WS_BUF(pre_cb), WS_BUF(poly_tmp), WS_BUF(split), WS_BUF(link_tmp), WS_BUF(occ), WS_BUF(vid)};
 #undef WS_BUF
 static_assert(sizeof(Workspace) == sizeof(Workspace::bufs) / sizeof(Workspace::bufs[0]) * sizeof(DevBuf) + sizeof(void*) + sizeof(size_t) + sizeof(double) + sizeof(hipEvent_t),
               "a DevBuf of Workspace is missing from Workspace::bufs");
@@ -1128,6 +1128,68 @@ int32_t mzk_kzg_multi_open_rou_dev(uint64_t srs_handle, uint64_t srs_offset, con
     if (len && !d_poly) { set_error("null pointer"); return MZK_ERR_INVALID_ARG; }
     return kzg_multi_open_dispatch(*s, srs_offset, reinterpret_cast<const uint32_t*>(d_poly), len, log_domain, num_points, out_proofs_xy_mont,
                                    reinterpret_cast<uint32_t*>(out_evals_mont), (hipStream_t)stream);
+}
+
+// ---- ADVZ verifiable information dispersal (vid.hip) ----
+int32_t mzk_bytes_to_field_dev(int32_t curve_id, const void* d_bytes, uint64_t len, void* d_out_mont, void* stream) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || (len && (!d_bytes || !d_out_mont)) || (reinterpret_cast<uintptr_t>(d_out_mont) & 15) || len >= (1ull << 40)) {
+        set_error("bad argument (d_out_mont 16-byte aligned, fewer than 2^40 bytes)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return vid_bytes_to_field_dispatch(curve_id, reinterpret_cast<const uint8_t*>(d_bytes), len, reinterpret_cast<uint32_t*>(d_out_mont), (hipStream_t)stream);
+}
+int32_t mzk_field_to_bytes_dev(int32_t curve_id, const void* d_elems_mont, uint64_t count, void* d_out_bytes, uint64_t* out_len, void* stream) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || !out_len || (count && (!d_elems_mont || !d_out_bytes)) || (reinterpret_cast<uintptr_t>(d_elems_mont) & 15) || count >= (1ull << 40)) {
+        set_error("bad argument (d_elems_mont 16-byte aligned, fewer than 2^40 elements)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return vid_field_to_bytes_dispatch(curve_id, reinterpret_cast<const uint32_t*>(d_elems_mont), count, reinterpret_cast<uint8_t*>(d_out_bytes), out_len,
+                                       (hipStream_t)stream);
+}
+int32_t mzk_vid_advz_commit_only_dev(uint64_t srs_handle, uint64_t srs_offset, uint64_t srs_len, const void* d_elems_mont, uint64_t n_elems, uint32_t payload_chunk_size,
+                                     uint32_t num_storage_nodes, uint32_t log_domain, uint8_t* out_commit32, void* stream) {
+    ENTER_HANDLE(srs_handle);
+    Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    if (!out_commit32 || (n_elems && !d_elems_mont) || (reinterpret_cast<uintptr_t>(d_elems_mont) & 15)) { set_error("null or misaligned pointer"); return MZK_ERR_INVALID_ARG; }
+    return vid_commit_only_dispatch(*s, srs_offset, srs_len, reinterpret_cast<const uint32_t*>(d_elems_mont), n_elems, payload_chunk_size, num_storage_nodes, log_domain,
+                                    out_commit32, (hipStream_t)stream);
+}
+int32_t mzk_vid_advz_disperse_dev(uint64_t srs_handle, uint64_t srs_offset, uint64_t srs_len, const void* d_elems_mont, uint64_t n_elems, uint32_t payload_chunk_size,
+                                  uint32_t num_storage_nodes, uint32_t log_domain, uint64_t* out_commits_xy_mont, uint8_t* out_evals, uint64_t* out_proofs_xy_mont,
+                                  uint8_t* out_nodes, uint8_t* out_commit32, uint8_t* out_root32, uint64_t* out_scalar_mont, void* stream) {
+    ENTER_HANDLE(srs_handle);
+    Srs* s = srs_find(*cx_, srs_handle);
+    if (!s) return MZK_ERR_BAD_HANDLE;
+    if (!out_proofs_xy_mont || !out_nodes || !out_commit32 || !out_root32 || !out_scalar_mont || (n_elems && (!d_elems_mont || !out_commits_xy_mont || !out_evals)) ||
+        (reinterpret_cast<uintptr_t>(d_elems_mont) & 15)) {
+        set_error("null or misaligned pointer");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return vid_disperse_dispatch(*s, srs_offset, srs_len, reinterpret_cast<const uint32_t*>(d_elems_mont), n_elems, payload_chunk_size, num_storage_nodes, log_domain,
+                                 out_commits_xy_mont, out_evals, out_proofs_xy_mont, out_nodes, out_commit32, out_root32, out_scalar_mont, (hipStream_t)stream);
+}
+int32_t mzk_vid_advz_verify_shares_dev(int32_t curve_id, uint64_t n_shares, uint64_t evals_per_share, uint32_t num_storage_nodes, const uint64_t* indices,
+                                       const uint8_t* evals, const uint8_t* paths, const uint8_t* root32, const uint64_t* scalar_mont, int32_t* out_ok,
+                                       uint64_t* out_agg_evals_mont, void* stream) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || !root32 || !scalar_mont || (n_shares && (!indices || !paths || !out_ok || !out_agg_evals_mont || (evals_per_share && !evals)))) {
+        set_error("bad argument");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return vid_verify_shares_dispatch(curve_id, n_shares, evals_per_share, num_storage_nodes, indices, evals, paths, root32, scalar_mont, out_ok, out_agg_evals_mont,
+                                      (hipStream_t)stream);
+}
+int32_t mzk_vid_advz_recover_dev(int32_t curve_id, uint32_t payload_chunk_size, uint64_t n_polys, uint32_t log_domain, const uint64_t* indices, const uint64_t* evals_mont,
+                                 void* d_out_mont, void* stream) {
+    ENTER_CUR();
+    if (!valid_curve(curve_id) || !indices || (n_polys && (!evals_mont || !d_out_mont)) || (reinterpret_cast<uintptr_t>(d_out_mont) & 15)) {
+        set_error("bad argument (d_out_mont 16-byte aligned)");
+        return MZK_ERR_INVALID_ARG;
+    }
+    return vid_recover_dispatch(curve_id, payload_chunk_size, n_polys, log_domain, indices, evals_mont, reinterpret_cast<uint32_t*>(d_out_mont), (hipStream_t)stream);
 }
 
 // ---- page-locked host memory for the host-pointer entry points ------------------------------------------

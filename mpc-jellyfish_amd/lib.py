@@ -98,6 +98,17 @@ _SIGS = {
     "mzk_verifier_open_begin": [C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_kzg_open_batch_dev": [C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_kzg_multi_open_rou_dev": [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_sha256": [C.c_void_p, C.c_uint64, C.c_void_p],
+    "mzk_expand_message_xmd_sha256": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64],
+    "mzk_hash_to_field_sha256": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p],
+    "mzk_bytes_to_field_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p],
+    "mzk_field_to_bytes_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p],
+    "mzk_vid_advz_commit_only_dev": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p],
+    "mzk_vid_advz_disperse_dev": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mzk_vid_advz_verify_shares_dev": [C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p],
+    "mzk_vid_advz_recover_dev": [C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "mzk_srs_register_serialized": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
     "mzk_srs_register_serialized_dev": [C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p],
     "mzk_srs_serialize": [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p],
